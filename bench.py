@@ -6,8 +6,18 @@ A "step" is one pass of the hot path over one batch: out[T, R] = (X[T, G] . W[G,
 Default workload (N=1) = BASELINE.json configs[1] in its dense north-star form ("c2-dense"):
 T=365 daily steps, 0.25-degree grid G=720x1440=1,036,800, R=24,378 impact regions, fp32, W a
 dense (gridcell x region) matrix generated on the device (101 GB, hash of (g, r, seed)); inputs
-are resident in HBM before the timed region.  The same run also times "c2-real" / "c3-real" (the
+are resident in HBM before the timed region.  With --full the same run also times "c2-real" / "c3-real" (the
 sparse segment-table form of configs[1] / [2]) and reports them under "secondary".
+
+A plain run (no --full) does only what the headline needs: set up the workload, warm up, time exactly --steps steps,
+write the outputs of the last timed step if --dump-outputs DIR is given, print the line.  Its `roofline` and
+`cpu_baseline` are null.  --full adds everything else this script measures or checks: the secondary workloads, CPU
+baselines, the dominant kernel's own timings and roofline, the boundary legs, and the N > 1 gather checks.
+
+--dump-outputs DIR: DIR/out.npy holds what a caller of the timed path receives from its last timed step -- the (T, R)
+block in the workload's dtype, on rank 0 of a sharded run the reassembled (T_job, R) series.  Above DUMP_LIMIT bytes
+it is a fixed seeded sample of its rows.  The inputs depend only on the arguments, so two builds can be compared
+output for output.
 
 Workloads (--workload):
   c1          configs[0]: 2-degree grid, 100 regions, fp64 -- the reference's own CPU-sized case; the
@@ -29,13 +39,13 @@ LOCAL_RANK / WORLD_SIZE in the environment) or by this script itself: a plain `p
 relays rank 0's JSON line and returns the child's exit status (a rank whose LOCAL_RANK has no device exits
 non-zero with a one-line reason).  --dry-run rehearses exactly that plumbing on CPU (gloo, no kernels).
 
-The default N=1 run carries every BASELINE config in its line: c2-dense is the headline; "secondary" holds c1,
+The default N=1 run with --full carries every BASELINE config in its line: c2-dense is the headline; "secondary" holds c1,
 c2-real, c3-real, one rank's share of c4 (1,369 rows on the c2-dense operand) and of c5 in both structures
 (2,282 rows; block-local fp32, uniform fp32 and fp64), each with its own roofline and cpu_baseline.
 
-Output (rank 0): ONE JSON line on stdout, below 6 KB -- the contract's keys, `roofline`, `cpu_baseline` and one short row per
-workload of the run (compact_line()) -- and the full record (every secondary in full, boundary legs, CPU legs) as one
-`BENCH_DETAIL {...}` line on stderr and in gpurun_out/bench_line_n<N>.json.
+Output (rank 0): ONE JSON line on stdout, below 6 KB -- the contract's keys, `roofline`, `cpu_baseline` and, with --full, one
+short row per workload of the run (compact_line()) -- and the full record (every secondary in full, boundary legs, CPU
+legs) as one `BENCH_DETAIL {...}` line on stderr; with --full also written to the files emit() names.
 """
 import argparse
 import json
@@ -67,6 +77,12 @@ def parse():
     ap.add_argument("--R", type=int, default=24378)
     ap.add_argument("--ksplit", type=int, default=0)
     ap.add_argument("--land-frac", type=float, default=0.30, help="experiment knob for c2-real")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline (secondaries, CPU baselines, kernel timings and roofline, "
+                         "boundary legs, N > 1 gather checks); --no-secondary, --no-cpu-baseline, --ref-budget-s, "
+                         "--max-auto-steps and --budget-s tune it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/out.npy (a seeded row sample above 64 MB)")
     ap.add_argument("--no-secondary", action="store_true")
     ap.add_argument("--dry-run", action="store_true",
                     help="rehearse the launcher and the rank plumbing on CPU (gloo, no kernels, value 0)")
@@ -83,7 +99,10 @@ def parse():
     ap.add_argument("--diag-lib", nargs="?", const="libwagg_diag.so", default=None, metavar="NAME",
                     help="load climate_toolbox_amd/lib/NAME (default libwagg_diag.so, `make diag`) instead of libwagg.so: "
                          "the build with the ablation knobs, or an experiment's variant; timing experiments only")
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return a
 
 
 def self_launch(a):
@@ -156,6 +175,7 @@ def dry_run(a, rank, local_rank, world):
 
 
 COMPACT_LIMIT = 6144     # bytes: the driver parsed a 17 KB line in round 4 and failed on 28.5 KB in round 5; stay far below both
+DUMP_LIMIT = 64 * 10**6  # bytes: --dump-outputs writes at most this much in all
 
 
 def _sig(x, n=6):
@@ -220,10 +240,16 @@ def compact_line(line, limit=COMPACT_LIMIT):
     return json.dumps(c, separators=(",", ":"))
 
 
-def emit(line, world):
-    """rank 0: detail to stderr and to gpurun_out/, the compact line -- the ONLY thing on stdout -- last."""
+def emit(line, world, detail_files=True):
+    """rank 0: the detail to stderr, then the compact line -- the ONLY thing on stdout; with ``detail_files`` (--full)
+    both records are also written to the files below."""
     full = json.dumps(line)
     text = compact_line(line)
+    sys.stderr.write("BENCH_DETAIL " + full + "\n")
+    sys.stderr.flush()
+    print(text, flush=True)
+    if not detail_files:
+        return
     try:                                        # (gpurun merges gpurun_out/ back)
         os.makedirs(os.path.join(ROOT, "gpurun_out"), exist_ok=True)
         with open(os.path.join(ROOT, "gpurun_out", "bench_line_n%d.json" % world), "w") as f:
@@ -232,9 +258,6 @@ def emit(line, world):
             f.write(text + "\n")
     except OSError:
         pass
-    sys.stderr.write("BENCH_DETAIL " + full + "\n")
-    sys.stderr.flush()
-    print(text, flush=True)
 
 
 def load_traffic(workload):
@@ -638,7 +661,7 @@ def main():
 
     # proof that the collective backend saw every rank: an all-reduce of ones on device tensors (= N only if all took part)
     rccl_ranks = None
-    if use_dist:
+    if use_dist and a.full:
         one = torch.ones(1, dtype=torch.float32, device="cpu" if rehearse else "cuda")
         dist.all_reduce(one)
         rccl_ranks = int(round(float(one.item())))
@@ -658,10 +681,11 @@ def main():
     from climate_toolbox_amd.timeshard import ShardedStep, shard_bounds
 
     global EVENT_OVERHEAD_MS
-    try:
-        EVENT_OVERHEAD_MS = engine.profile_event_overhead(128)[0]
-    except Exception as e:                                   # a diagnostic library without the symbol: the line says so
-        sys.stderr.write("bench.py: no event-overhead measurement (%s)\n" % e)
+    if a.full:
+        try:
+            EVENT_OVERHEAD_MS = engine.profile_event_overhead(128)[0]
+        except Exception as e:                               # a diagnostic library without the symbol: the line says so
+            sys.stderr.write("bench.py: no event-overhead measurement (%s)\n" % e)
     G, R = a.nlat * a.nlon, a.R
     scaling = "weak"
     C5_TOTAL, C4_TOTAL = 50 * 365, 10950
@@ -691,10 +715,24 @@ def main():
         return ShardedStep(apply_fn, lambda: torch.empty((Tn, Rr), dtype=dtype, device="cuda"), rows=rows_all, dst=0,
                            distributed=use_dist)
 
+    outputs = {}                         # --dump-outputs: name -> host array
+
+    def keep_output(st):
+        """What a caller of the timed path receives from its last step -- this rank's block, on a sharded run the
+        reassembled series (rank 0 only) -- as a host array; above DUMP_LIMIT bytes a fixed seeded sample of its rows."""
+        out = st.finish() if st.distributed else st.bufs[(st.k - 1) & 1]
+        if out is None:                  # (not the gather's destination)
+            return
+        row_bytes = out[0].numel() * out.element_size()
+        if out.shape[0] * row_bytes > DUMP_LIMIT:
+            keep = np.sort(np.random.default_rng(0).choice(out.shape[0], max(1, DUMP_LIMIT // row_bytes), replace=False))
+            out = out[torch.from_numpy(keep).to(out.device)]
+        outputs["out"] = out.cpu().numpy()
+
     def gather_check(st, Tn):
         """rank 0, distributed runs: the reassembled series holds this rank's last block in this rank's rows (the other
         ranks' rows are theirs to vouch for: the CPU gloo tests compare every block)."""
-        if not use_dist or rank != 0:
+        if not (use_dist and a.full) or rank != 0:
             return None
         got = st.finish()
         return bool(got is not None and got.shape[0] == sum(st.rows) and torch.equal(got[:Tn], st.bufs[(st.k - 1) & 1]))
@@ -703,7 +741,7 @@ def main():
         """N > 1 lines: what the driver needs to check the collective -- `gather_ms`: one BLOCKING gather of the real block
         (event pair / wall clock around timeshard.gather_time_shards, max over ranks); `per_rank_ms`: every rank's median
         step (all-gathered), so a straggler shows; `rccl_ranks`: the all-reduce proof from start-up."""
-        if not use_dist:
+        if not (use_dist and a.full):
             return {}
         from climate_toolbox_amd.timeshard import gather_time_shards
         block = st.bufs[(st.k - 1) & 1]
@@ -878,7 +916,7 @@ def main():
     def profile_reset():
         engine.profile_enable(True)       # (resets the ring: the timings read afterwards are those of the timed steps only)
 
-    def run_sparse(dtype, small=False, steps=None, warmup=None, extras=True, auto=False):
+    def run_sparse(dtype, small=False, steps=None, warmup=None, auto=False, keep_out=False):
         steps, warmup = steps or a.steps, a.warmup if warmup is None else warmup
         T, rows_all, _ = rows_for("c1" if small else "c2-real")
         T_job = sum(rows_all)
@@ -898,21 +936,20 @@ def main():
         plan_build_s = time.perf_counter() - t0
         Rr = len(uniq)
         st = stepper(lambda out: plan.apply(Xs, out=out), T, rows_all, Rr, Xs.dtype)
-        dt, per_step, steps, warm_done = timed_steps(torch, dist, st.step, st.finish, steps, warmup, world, profile_reset, auto_steps=auto,
-                                                     profile_read=engine.profile_read)
-        kst = kernel_stats(engine.profile_read(), steps, LAUNCHES_PER_APPLY)
-        engine.profile_enable(False)
-        kmed = kst["kernel_ms_median"] * 1e-3          # the roofline is priced on the MEDIAN launch
+        prof = {"profile_reset": profile_reset, "profile_read": engine.profile_read} if a.full else {}
+        dt, per_step, steps, warm_done = timed_steps(torch, dist, st.step, st.finish, steps, warmup, world, auto_steps=auto, **prof)
+        if a.full:
+            kst = kernel_stats(engine.profile_read(), steps, LAUNCHES_PER_APPLY)
+            engine.profile_enable(False)
+            kmed = kst["kernel_ms_median"] * 1e-3      # the roofline is priced on the MEDIAN launch
+        if keep_out:
+            keep_output(st)
         gok = gather_check(st, T)
         gt = gather_timing(st, T, per_step)
         plan.status()
         b = 4 if dtype == "float32" else 8
         nnz = plan.info["nnz"]
-        abytes = sparse_algorithmic_bytes(T, Gs, Rr, nnz, b)
         wl = "c1" if small else ("c2-real" if dtype == "float32" else "c3-real")
-        traffic, tsrc = load_traffic(wl)
-        kname = PLAN_KERNEL.get(int(plan.info.get("kernel_form", -1)),
-                                "sparse_lcv_kernel<float>" if b == 4 else "sparse_lcv_kernel<double>")
         res = {
             "workload": wl, "dtype": "f32" if b == 4 else "f64", "T": T, "T_job": T_job, "G": Gs, "R": Rr, "nnz": int(nnz),
             "value": T_job * Gs * Rr * steps / dt, "unit": "gridcell-region-timesteps/s", "steps": steps, "warmup": warmup,
@@ -921,13 +958,18 @@ def main():
             **({"gather_ok": gok} if gok is not None else {}), **gt,
             "plan_build_s": round(plan_build_s, 4),      # wagg_plan_create on the coded table (host-side chunking + upload), once per table
             "plan": {k: int(v) for k, v in plan.info.items()},
-            "roofline": net_of_events(on_traffic({"bound": "hbm", "achieved": abytes / kmed / 1e9, "peak": PEAK_HBM_GBS, "unit": "GB/s",
-                                                  "frac": abytes / kmed / 1e9 / PEAK_HBM_GBS, "frac_basis": "median kernel time",
-                                                  "traffic": traffic, "traffic_source": tsrc,
-                                                  "kernel": kname, **kst, "algorithmic_bytes_per_launch": abytes},
-                                                 kmed), abytes / 1e9, PEAK_HBM_GBS),
         }
-        if rank == 0 and world == 1 and not a.no_cpu_baseline:
+        if a.full:
+            abytes = sparse_algorithmic_bytes(T, Gs, Rr, nnz, b)
+            traffic, tsrc = load_traffic(wl)
+            kname = PLAN_KERNEL.get(int(plan.info.get("kernel_form", -1)),
+                                    "sparse_lcv_kernel<float>" if b == 4 else "sparse_lcv_kernel<double>")
+            res["roofline"] = net_of_events(on_traffic({"bound": "hbm", "achieved": abytes / kmed / 1e9, "peak": PEAK_HBM_GBS, "unit": "GB/s",
+                                                        "frac": abytes / kmed / 1e9 / PEAK_HBM_GBS, "frac_basis": "median kernel time",
+                                                        "traffic": traffic, "traffic_source": tsrc,
+                                                        "kernel": kname, **kst, "algorithmic_bytes_per_launch": abytes},
+                                                       kmed), abytes / 1e9, PEAK_HBM_GBS)
+        if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:
             Xh_cpu = Xs.cpu().numpy()
             res["cpu_baseline"] = cpu_baseline_sparse(Xh_cpu, cell, codes, w_eff, Rr, Gs,
                                                       "the FULL workload (all %d timesteps, full segment table)" % T)
@@ -935,7 +977,7 @@ def main():
                 res["cpu_baseline"]["reference_shaped"] = cpu_reference_shaped(Xh_cpu, lat, lon, df, wname, lev,
                                                                                budget_s=6.0 if small else a.ref_budget_s)
             del Xh_cpu
-        if world == 1 and not small and extras:
+        if a.full and world == 1 and not small:
             # the same field in (gridcell, time) order -- the reference's (lat, lon, time) fixture layout
             XT = Xs.t().contiguous()
             gout = torch.empty((T, Rr), dtype=Xs.dtype, device="cuda")
@@ -978,7 +1020,7 @@ def main():
                 del eout
             res["fused_snyder_edd"] = edd
             del tmax
-        if world == 1 and not small and extras and dtype == "float32":
+        if a.full and world == 1 and not small and dtype == "float32":
             res.update(boundary_legs(Xs, lat, lon, df, plan, T, Gs, Rr))
             if "cpu_baseline" in res and "host_resident" in res:
                 cb = res["cpu_baseline"]["cpu_best"]
@@ -993,7 +1035,7 @@ def main():
                             "packed by up to 12 host threads); "
                             "the all-cores CPU restatement reads X from DRAM.  The device-resident step beside them is what a "
                             "pipeline that keeps the field in HBM pays"}
-        if world == 1 and not small and extras and dtype == "float64":
+        if a.full and world == 1 and not small and dtype == "float64":
             # the fp64 field (c3) in host memory: whole rows page-locked in place against lines only (47 % of a fp64 row)
             from climate_toolbox_amd import _lib as L_
             try:
@@ -1019,7 +1061,7 @@ def main():
     cpu_dense_memo = {}
     c5_tables = {}                       # block-local? -> (rowptr, col, val) host CSR of the synthetic c5 table
 
-    def run_dense_family(wl, plan=None, steps=None, warmup=None, keep_plan=False, share=False, auto=False, min_steps=10):
+    def run_dense_family(wl, plan=None, steps=None, warmup=None, keep_plan=False, share=False, auto=False, min_steps=10, keep_out=False):
         """c2-dense / c4 (full matrix), c5-uniform[-f64] (entry lists), c5-block[-f64] (tile-sparse)."""
         steps, warmup = steps or a.steps, a.warmup if warmup is None else warmup
         T, rows_all, scal = rows_for(wl, share)
@@ -1052,38 +1094,43 @@ def main():
             fill, bl = 1.0, False
             plan = plan or engine.DensePlan.synth(G, R, seed=2)
         st = stepper(lambda out: plan.apply(X, out=out, ksplit=a.ksplit), T, rows_all, R, X.dtype)
-        dt, per_step, steps, warm_done = timed_steps(torch, dist, st.step, st.finish, steps, warmup, world, profile_reset, auto_steps=auto,
-                                                     min_steps=min_steps, profile_read=engine.profile_read)
-        kst = kernel_stats(engine.profile_read(), steps, LAUNCHES_PER_APPLY)
-        engine.profile_enable(False)
+        prof = {"profile_reset": profile_reset, "profile_read": engine.profile_read} if a.full else {}
+        dt, per_step, steps, warm_done = timed_steps(torch, dist, st.step, st.finish, steps, warmup, world, auto_steps=auto,
+                                                     min_steps=min_steps, **prof)
+        if a.full:
+            kst = kernel_stats(engine.profile_read(), steps, LAUNCHES_PER_APPLY)
+            engine.profile_enable(False)
+        if keep_out:
+            keep_output(st)
         gok = gather_check(st, T)
         gt = gather_timing(st, T, per_step)
         form = int(plan.info["form"])
-        # one apply = one dominant-kernel launch (a full-form apply of several row blocks is one launch too); the roofline
-        # is priced on the MEDIAN launch
-        kmed = kst["kernel_ms_median"] * 1e-3
         if wl.startswith("c5-uniform"):
             nnz = int(plan.info["nnz"])
         elif wl.startswith("c5-block"):
             nnz = int(round(plan.info["n_tiles"] * (16 if f64 else 32) * 256 * fill))
         else:
             nnz = G * R
-        flops = 2.0 * T * nnz                                   # algorithmic: 2 T nnz (dense: nnz = G R)
-        traffic, tsrc = load_traffic(wl)
-        kname = {0: "dense_mfma_kernel", 1: "dense_pieces_kernel", 2: "spmm_kernel (vector ALU, entry lists)"}[form]
-        if f64:
-            kname = kname.replace("dense_mfma_kernel", "dense_mfma_kernel<double>").replace("dense_pieces_kernel", "dense_pieces_kernel<double>").replace("spmm_kernel", "spmm_kernel<double>")
-        # entry lists run on the vector ALU: fp32 FMA peak = the fp32 MFMA peak (157.3), fp64 FMA = 78.6
-        peak = PEAK_F64_MFMA_TFLOPS if f64 else PEAK_F32_MFMA_TFLOPS
         res = {"workload": wl, "dtype": "f64" if f64 else "f32", "T": T, "T_job": T_job, "G": G, "R": R, "nnz": nnz,
                "value": T_job * G * R * steps / dt, "unit": "gridcell-region-timesteps/s", "steps": steps, "warmup": warmup,
                "warmup_done": warm_done,
                "ms_per_step": dt / steps * 1e3, **step_stats(per_step),
-               "plan": {k: (int(v) if isinstance(v, int) else float("%.4g" % v)) for k, v in plan.info.items()}, "scaling": scal,
-               "roofline": net_of_events({"bound": "mfma" if form != 2 else "valu", "achieved": flops / kmed / 1e12, "peak": peak,
-                                          "unit": "TFLOP/s", "frac": flops / kmed / 1e12 / peak, "frac_basis": "median kernel time",
-                                          "traffic": traffic, "traffic_source": tsrc, "kernel": kname,
-                                          **kst, "algorithmic_flops_per_launch": flops}, flops / 1e12, peak)}
+               "plan": {k: (int(v) if isinstance(v, int) else float("%.4g" % v)) for k, v in plan.info.items()}, "scaling": scal}
+        if a.full:
+            # one apply = one dominant-kernel launch (a full-form apply of several row blocks is one launch too); the roofline
+            # is priced on the MEDIAN launch
+            kmed = kst["kernel_ms_median"] * 1e-3
+            flops = 2.0 * T * nnz                               # algorithmic: 2 T nnz (dense: nnz = G R)
+            traffic, tsrc = load_traffic(wl)
+            kname = {0: "dense_mfma_kernel", 1: "dense_pieces_kernel", 2: "spmm_kernel (vector ALU, entry lists)"}[form]
+            if f64:
+                kname = kname.replace("dense_mfma_kernel", "dense_mfma_kernel<double>").replace("dense_pieces_kernel", "dense_pieces_kernel<double>").replace("spmm_kernel", "spmm_kernel<double>")
+            # entry lists run on the vector ALU: fp32 FMA peak = the fp32 MFMA peak (157.3), fp64 FMA = 78.6
+            peak = PEAK_F64_MFMA_TFLOPS if f64 else PEAK_F32_MFMA_TFLOPS
+            res["roofline"] = net_of_events({"bound": "mfma" if form != 2 else "valu", "achieved": flops / kmed / 1e12, "peak": peak,
+                                             "unit": "TFLOP/s", "frac": flops / kmed / 1e12 / peak, "frac_basis": "median kernel time",
+                                             "traffic": traffic, "traffic_source": tsrc, "kernel": kname,
+                                             **kst, "algorithmic_flops_per_launch": flops}, flops / 1e12, peak)
         if gok is not None:
             res["gather_ok"] = gok
         res.update(gt)
@@ -1093,7 +1140,7 @@ def main():
         if wl != "c2-dense":
             res["rows"] = ("one rank's share: %d of the job's %d rows (shard 0 of %d)"
                            % (T, C4_TOTAL if wl == "c4" else C5_TOTAL, a.shards or 8)) if world == 1 else "rows %r" % (rows_all,)
-        if rank == 0 and world == 1 and not a.no_cpu_baseline:
+        if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:
             key = (fill, bl)                                    # c4 contracts the c2-dense operand: one CPU window serves both
             if key not in cpu_dense_memo:
                 cpu_dense_memo[key] = cpu_baseline_dense(min(T, 365), G, R, 2, fill, bl)
@@ -1118,8 +1165,9 @@ def main():
         return r
 
     if a.workload in DENSE_FAMILY:
-        want_secondary = a.workload == "c2-dense" and world == 1 and not a.no_secondary
-        main_res, plan = run_dense_family(a.workload, keep_plan=want_secondary or (a.workload == "c2-dense" and world > 1 and not a.no_secondary))
+        want_secondary = a.full and a.workload == "c2-dense" and world == 1 and not a.no_secondary
+        want_strong = a.full and a.workload == "c2-dense" and world > 1 and not a.no_secondary
+        main_res, plan = run_dense_family(a.workload, keep_plan=want_secondary or want_strong, keep_out=bool(a.dump_outputs))
         scaling = main_res.get("scaling", "weak")
         if want_secondary:
             # every other BASELINE config on this GPU (N = 1): c4's rank share on the SAME 101 GB operand, then the rest.
@@ -1134,7 +1182,7 @@ def main():
             for wl in ("c5-block", "c5-block-f64", "c5-uniform", "c5-uniform-f64"):
                 torch.cuda.empty_cache()
                 budgeted(wl, lambda wl=wl: run_dense_family(wl, warmup=2, share=True, auto=True))
-        elif a.workload == "c2-dense" and world > 1 and not a.no_secondary:
+        elif want_strong:
             # multi-GPU run: after the weak-scaled headline the STRONG splits of the two 8-GPU configs BASELINE names --
             # configs[3] (10,950 rows over the ranks, on the operand already resident) and configs[4] (18,250 rows,
             # entry lists) -- so that the scaling line speaks to them too.  Every rank takes part (the gather is inside).
@@ -1146,10 +1194,14 @@ def main():
             budgeted("c5-uniform", lambda: run_dense_family("c5-uniform", steps=3, warmup=1))
             a.shards = a_shards
     elif a.workload == "c1":
-        main_res = run_sparse("float64", small=True)
+        main_res = run_sparse("float64", small=True, keep_out=bool(a.dump_outputs))
     else:
-        main_res = run_sparse("float32" if a.workload == "c2-real" else "float64")
+        main_res = run_sparse("float32" if a.workload == "c2-real" else "float64", keep_out=bool(a.dump_outputs))
     T_job = main_res["T_job"]
+    if a.dump_outputs and rank == 0:
+        os.makedirs(a.dump_outputs, exist_ok=True)
+        for name, arr in outputs.items():
+            np.save(os.path.join(a.dump_outputs, name + ".npy"), arr)
 
     if rank == 0:
         wl = main_res["workload"]
@@ -1175,7 +1227,7 @@ def main():
                                    % (wl, main_res["T"], T_job, main_res["G"], main_res["R"], what, world),
                        "T_per_gpu": main_res["T"], "T_job": T_job, "G": main_res["G"], "R": main_res["R"],
                        "parallelism": "time-shard x%d" % world},
-            "roofline": main_res["roofline"],
+            "roofline": main_res.get("roofline"),
             "cpu_baseline": main_res.get("cpu_baseline"),
         }
         for k in ("plan_build_s", "plan_build", "gather_ok", "host_resident", "dropin_ms", "agglev_ISO", "layout_gridcell_time",
@@ -1223,17 +1275,18 @@ def main():
                 row["gather_ms"] = round(r["gather_ms"], 3)
                 row["gather_ok"] = r.get("gather_ok")
             return row
-        rows = [brief(main_res)] + [brief(r) for r in secondary]
-        line["summary"] = {"columns": "step_ms / kernel_ms = [median, min, max]; frac = roofline fraction on the median kernel time; "
-                                      "cpu_port_s = oracle/wagg_oracle.c on its sample (1 thread for the segment-table rows); "
-                                      "cpu_reference_shaped_s = the reference's NumPy / pandas shape, full workload (scaled from rows_timed)",
-                           "rows": rows}
+        rows = ([brief(main_res)] + [brief(r) for r in secondary]) if a.full else []
+        if rows:
+            line["summary"] = {"columns": "step_ms / kernel_ms = [median, min, max]; frac = roofline fraction on the median kernel time; "
+                                          "cpu_port_s = oracle/wagg_oracle.c on its sample (1 thread for the segment-table rows); "
+                                          "cpu_reference_shaped_s = the reference's NumPy / pandas shape, full workload (scaled from rows_timed)",
+                               "rows": rows}
         # the reference-shaped CPU legs run on the segment-table workloads: the headline line names the c2-real pair at top level
         for r in rows:
             if r.get("wl") == "c2-real" and "cpu_reference_shaped_s" in r:
                 line["cpu_reference_shaped_s"] = dict(r["cpu_reference_shaped_s"], workload="c2-real", c_port_s=r["cpu_port_s"],
                                                       gpu_step_s=round(r["step_ms"][0] * 1e-3, 7))
-        emit(line, world)
+        emit(line, world, detail_files=a.full)
     if use_dist:
         dist.barrier()
         dist.destroy_process_group()

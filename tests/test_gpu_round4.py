@@ -325,7 +325,7 @@ def test_bench_over_rccl_with_one_rank():
     import sys
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     env.update(WAGG_BENCH_FORCE_DIST="1", HSA_ENABLE_IPC_MODE_LEGACY="0", MASTER_PORT="29531")
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "c2-real", "--steps", "3", "--no-cpu-baseline"],
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "c2-real", "--steps", "3", "--full", "--no-cpu-baseline"],
                        capture_output=True, text=True, env=env, timeout=600)
     assert p.returncode == 0, p.stderr[-3000:]
     from tests.bench_io import split_bench_output
@@ -506,7 +506,7 @@ def test_bench_multi_rank_control_flow_rehearsal():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     env.update(WAGG_BENCH_REHEARSE="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "3", "--nlat", "180", "--nlon", "360", "--R", "600",
-                        "--steps", "2", "--warmup", "1", "--no-cpu-baseline"], capture_output=True, text=True, env=env, timeout=900)
+                        "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline"], capture_output=True, text=True, env=env, timeout=900)
     assert p.returncode == 0, p.stderr[-3000:]
     from tests.bench_io import split_bench_output
     line, rec = split_bench_output(p)              # one stdout line under 6 KB; `rec` = the detail from stderr
@@ -531,7 +531,7 @@ def test_bench_multi_rank_control_flow_rehearsal():
         assert sec[wl]["rccl_ranks"] == 3 and sec[wl]["gather_ms"] > 0 and len(sec[wl]["per_rank_ms"]) == 3
     # a spent wall-clock budget drops the secondaries instead of running into the driver's limit
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "3", "--nlat", "180", "--nlon", "360", "--R", "600",
-                        "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--budget-s", "0"], capture_output=True, text=True, env=env,
+                        "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--budget-s", "0"], capture_output=True, text=True, env=env,
                        timeout=900)
     assert p.returncode == 0, p.stderr[-3000:]
     line, rec = split_bench_output(p)

@@ -8,7 +8,7 @@ REPO=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$REPO/gpurun_out/pmc_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 500 rocprofv3 --pmc $CNT --output-format csv -d $OUT -o bench -- python3 $REPO/bench.py --steps 2 --warmup 1 --no-cpu-baseline "$@" > $OUT/bench.json 2> $OUT/err.log || { echo failed; tail -5 $OUT/err.log; exit 1; }
+timeout -k 10 500 rocprofv3 --pmc $CNT --output-format csv -d $OUT -o bench -- python3 $REPO/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline "$@" > $OUT/bench.json 2> $OUT/err.log || { echo failed; tail -5 $OUT/err.log; exit 1; }
 python3 - "$(find $OUT -name 'bench_counter_collection.csv' | head -1)" "$KSUB" <<'PY'
 import csv,sys,collections
 rows=list(csv.DictReader(open(sys.argv[1])))

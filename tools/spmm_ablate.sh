@@ -23,7 +23,7 @@ else
   for v in $VARIANTS; do
     tag=${v//,/_}
     echo -n "$tag "
-    python3 bench.py --workload c5-uniform --diag-lib libwagg_abl_$tag.so --steps 3 --warmup 1 --no-cpu-baseline 2>/dev/null | \
+    python3 bench.py --full --workload c5-uniform --diag-lib libwagg_abl_$tag.so --steps 3 --warmup 1 --no-cpu-baseline 2>/dev/null | \
       python3 -c "import json,sys; r=json.loads(sys.stdin.readline()); print('kernel_ms', round(r['roofline']['kernel_ms_avg'],2))"
   done
 fi
