@@ -45,6 +45,7 @@ EXPORTS = (
     "wagg_apply_sharded_f32", "wagg_apply_sharded_f64", "wagg_dense_apply_sharded_f32", "wagg_dense_apply_sharded_f64",
     "wagg_apply", "wagg_struct_size", "wagg_struct_ordinals", "wagg_plan_get_info_sized", "wagg_dense_get_info_sized",
     "wagg_host_stats_read_sized",
+    "wagg_plan_create_many", "wagg_plan_many_info", "wagg_plan_get_den_many",
 )
 STRUCT_PLAN_INFO, STRUCT_DENSE_INFO, STRUCT_HOST_STATS, STRUCT_APPLY_DESC = 0, 1, 2, 3
 PLAN_SEGMENT, PLAN_DENSE = 0, 1
@@ -166,6 +167,10 @@ def load():
     L.wagg_factorize_bytes.argtypes = [C.c_char_p, C.c_int64, u8p, C.c_int64, i32p, i64p, i64p]
     L.wagg_plan_create.argtypes = [i32p, i32p, f64p, C.c_int64, C.c_int64, C.c_int32, C.c_int64,
                                    C.c_int, C.POINTER(vp)]
+    L.wagg_plan_create_many.argtypes = [i32p, i32p, C.POINTER(f64p), C.c_int, C.c_int64, C.c_int64, C.c_int32, C.c_int64,
+                                        C.POINTER(i32p), i32p, C.c_int, C.c_int, C.POINTER(vp)]
+    L.wagg_plan_many_info.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), i32p, i64p]
+    L.wagg_plan_get_den_many.argtypes = [vp, C.c_int, C.c_int, f64p]
     L.wagg_plan_destroy.argtypes = [vp]
     L.wagg_plan_get_info.argtypes = [vp, C.POINTER(PlanInfo)]
     L.wagg_plan_get_info_sized.argtypes = [vp, vp, C.c_uint64]

@@ -266,9 +266,55 @@ def _plan_for(cell_idx, codes, w_eff, G, R, row_len, is_f32=False, layout="TG", 
     return plan
 
 
+_MANY_DENSE = set()   # keys of many-plan tables that the dense family serves better (the caller then makes single calls)
+
+
+def _many_plan_for(cell_idx, codes, w_effs, G, R, row_len, levels, is_f32=False, layout="TG"):
+    """The cached many-plan (engine.ManyPlan) of these weight columns and levels, LEASED as in _plan_for; None when the
+    table belongs to the dense family (the single-call path serves it).  The key covers the table, every weight column
+    and every level column; single plans keep their own keys (_plan_for)."""
+    from .engine import ManyPlan
+    key, _ = _fingerprint(cell_idx, codes, *w_effs, *[c for c, _r in levels],
+                          extra=repr(("many", len(w_effs), [int(r) for _c, r in levels], int(G), int(R), int(row_len), bool(is_f32), layout)))
+    while True:
+        with _CACHE_LOCK:
+            if key in _MANY_DENSE:
+                return None
+            plan = _PLAN_CACHE.get(key)
+            if plan is not None:
+                _PLAN_CACHE.move_to_end(key)
+        if plan is None:
+            break
+        plan._lease.acquire()
+        if plan._h.value:
+            return plan
+        plan._lease.release()
+        with _CACHE_LOCK:
+            if _PLAN_CACHE.get(key) is plan:
+                del _PLAN_CACHE[key]
+    import torch
+    with _CACHE_LOCK:
+        _evict_plans(_PLAN_CACHE_MAX_FRAC * torch.cuda.mem_get_info()[1], keep=_PLAN_CACHE_MAX - 1)
+    plan = ManyPlan(cell_idx, codes, w_effs, G, R, row_len=row_len, levels=levels)
+    if _wants_dense(plan.info["n_ucells"], G, layout, R=R, nseg=len(cell_idx), is_f32=is_f32):
+        plan.close()
+        with _CACHE_LOCK:
+            _MANY_DENSE.add(key)
+        return None
+    plan._lease.acquire()
+    with _CACHE_LOCK:
+        old = _PLAN_CACHE.get(key)
+        _PLAN_CACHE[key] = plan          # (a concurrent build of the same key: the older one stays with its caller, then goes)
+    if old is not None and old is not plan and old._lease.acquire(blocking=False):
+        old.close()
+        old._lease.release()
+    return plan
+
+
 def _clear_plans():
     """Close every cached plan that no call is using (clear_caches)."""
     with _CACHE_LOCK:
+        _MANY_DENSE.clear()
         for key in list(_PLAN_CACHE):
             plan = _PLAN_CACHE[key]
             if plan._lease.acquire(blocking=False):

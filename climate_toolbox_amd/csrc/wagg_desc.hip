@@ -44,8 +44,23 @@ int run_segment(const wagg_apply_desc &d) {
     const T *x = static_cast<const T *>(d.x), *x2 = static_cast<const T *>(d.x2);
     T *out = static_cast<T *>(d.out);
     const wagg_plan *plan = static_cast<const wagg_plan *>(d.plan);
+    // many-plans (wagg_plan_create_many): looked at only where the single-plan path would use the handle anyway
+    auto many = [&]() -> int {
+        if (d.transform != WAGG_XF_NONE) return unsupported(d, "a many-plan aggregates the field as it is (no fused transform)");
+        if (d.source == WAGG_SRC_DEVICE) {
+            if constexpr (f32) return entry::apply_many_f32(plan, x, d.T, d.ldx, d.layout, out, d.ldo, d.out_layout, d.stream);
+            else return entry::apply_many_f64(plan, x, d.T, d.ldx, d.layout, out, d.ldo, d.out_layout, d.stream);
+        }
+        if constexpr (f32) return entry::apply_many_host_f32(plan, x, d.T, d.ldx, d.layout, out, d.ldo, d.out_layout, d.flags);
+        else return entry::apply_many_host_f64(plan, x, d.T, d.ldx, d.layout, out, d.ldo, d.out_layout, d.flags);
+    };
+    auto any_many = [&](const wagg_plan *const *plans) {
+        for (int i = 0; i < d.n_plans; ++i) if (entry::is_many_plan(plans[i])) return true;
+        return false;
+    };
     switch (d.source) {
         case WAGG_SRC_DEVICE:
+            if (entry::is_many_plan(plan)) return many();
             if (d.transform == WAGG_XF_NONE) {
                 if constexpr (f32) return entry::apply_f32(plan, x, d.T, d.ldx, d.layout, out, d.ldo, d.out_layout, d.stream);
                 else return entry::apply_f64(plan, x, d.T, d.ldx, d.layout, out, d.ldo, d.out_layout, d.stream);
@@ -58,11 +73,13 @@ int run_segment(const wagg_apply_desc &d) {
             else return entry::apply_edd_f64(plan, x, x2, d.T, d.ldx, d.layout, d.offset, d.thresholds, d.n_thr, out, d.ldo, d.out_pstride, d.out_layout, d.stream);
         case WAGG_SRC_HOST:
             if (d.transform == WAGG_XF_NONE) {
+                if (entry::is_many_plan(plan)) return many();
                 if constexpr (f32) return entry::apply_host_ex_f32(plan, x, d.T, d.ldx, d.layout, out, d.ldo, d.out_layout, d.flags);
                 else return entry::apply_host_ex_f64(plan, x, d.T, d.ldx, d.layout, out, d.ldo, d.out_layout, d.flags);
             }
             if (d.layout != WAGG_LAYOUT_TG || d.out_layout != WAGG_OUT_TR)
                 return unsupported(d, "fused transforms of host-resident fields take (time, gridcell) data and give (time, region) results");
+            if (entry::is_many_plan(plan)) return many();
             if (d.transform == WAGG_XF_POLY) {
                 if constexpr (f32) return entry::apply_poly_host_f32(plan, x, d.T, d.ldx, d.offset, d.pow_first, d.n_pow, out, d.ldo, d.out_pstride, d.flags);
                 else return entry::apply_poly_host_f64(plan, x, d.T, d.ldx, d.offset, d.pow_first, d.n_pow, out, d.ldo, d.out_pstride, d.flags);
@@ -73,6 +90,7 @@ int run_segment(const wagg_apply_desc &d) {
             if (d.transform != WAGG_XF_NONE) return unsupported(d, "the multi-device host pipeline has no fused transforms");
             if (d.layout != WAGG_LAYOUT_TG || d.out_layout != WAGG_OUT_TR) return unsupported(d, "(time, gridcell) data and (time, region) results only");
             const wagg_plan *const *plans = static_cast<const wagg_plan *const *>(d.plan);
+            if (any_many(plans)) return unsupported(d, "a many-plan has no multi-device form");
             if constexpr (f32) return entry::apply_host_multi_f32(plans, d.devices, d.n_plans, x, d.T, d.ldx, out, d.ldo, d.flags);
             else return entry::apply_host_multi_f64(plans, d.devices, d.n_plans, x, d.T, d.ldx, out, d.ldo, d.flags);
         }
@@ -82,6 +100,7 @@ int run_segment(const wagg_apply_desc &d) {
             wagg_shard_group *g = static_cast<wagg_shard_group *>(d.group);
             const wagg_plan *const *plans = static_cast<const wagg_plan *const *>(d.plan);
             const T *const *xs = static_cast<const T *const *>(d.x);
+            if (any_many(plans)) return unsupported(d, "a many-plan has no sharded form");
             if constexpr (f32) return entry::apply_sharded_f32(g, plans, xs, d.rows, d.ldx, out, d.ldo, d.root);
             else return entry::apply_sharded_f64(g, plans, xs, d.rows, d.ldx, out, d.ldo, d.root);
         }

@@ -37,5 +37,11 @@ int dense_apply_host_multi_f32(wagg_dense *const *plans, const int *devices, int
 int dense_apply_host_multi_f64(wagg_dense *const *plans, const int *devices, int n_devices, const double *X_host, int64_t T, int64_t ldx, double *out_host, int64_t ldo, int flags);
 int dense_apply_sharded_f32(wagg_shard_group *g, wagg_dense *const *plans, const float *const *X_dev, const int64_t *rows, int64_t ldx, float *out_root, int64_t ldo, int root);
 int dense_apply_sharded_f64(wagg_shard_group *g, wagg_dense *const *plans, const double *const *X_dev, const int64_t *rows, int64_t ldx, double *out_root, int64_t ldo, int root);
+// many-plans (wagg_plan_create_many): the concatenated result of every (level, weighting) plane, from one pass over X
+int apply_many_f32(const wagg_plan *plan, const float *X_dev, int64_t T, int64_t ldx, int layout, float *out_dev, int64_t ldo, int out_layout, void *stream);
+int apply_many_f64(const wagg_plan *plan, const double *X_dev, int64_t T, int64_t ldx, int layout, double *out_dev, int64_t ldo, int out_layout, void *stream);
+int apply_many_host_f32(const wagg_plan *plan, const float *X_host, int64_t T, int64_t ldx, int layout, float *out_host, int64_t ldo, int out_layout, int flags);
+int apply_many_host_f64(const wagg_plan *plan, const double *X_host, int64_t T, int64_t ldx, int layout, double *out_host, int64_t ldo, int out_layout, int flags);
+bool is_many_plan(const wagg_plan *plan);
 }  // namespace entry
 }  // namespace wagg

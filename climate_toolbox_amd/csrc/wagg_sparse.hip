@@ -541,14 +541,15 @@ __global__ __launch_bounds__(STHREADS, 4) void sparse_stream_kernel(PlanView<T> 
 // ---------------------------------------------------------------------------------------------
 constexpr int LV_LW = 8, LV_CW = 8, LV_THREADS = (LV_LW + LV_CW) * 64, LV_TB = 64;
 constexpr int LV_ROWB = 1024;                   // bytes of an image row: 256 floats / 128 doubles = the cells of a chunk
-template <typename T, int NPOW = 1> struct LvLds {
+template <typename T, int NPOW = 1, int NW = 1> struct LvLds {
     static constexpr int E = 16 / (int)sizeof(T);                               // elements of a 16-byte piece
-    static constexpr int scr_rows = NPOW > E ? NPOW : E;                        // result rows (entry, power) of one batch
+    static constexpr int PL = NPOW * NW;                                        // result planes (powers x weightings)
+    static constexpr int scr_rows = PL > E ? PL : E;                            // result rows (entry, plane) of one batch
     static constexpr size_t scr_wave = (size_t)scr_rows * 64 * sizeof(T);       // 1 KiB (2 KiB: fp64 with 3 or 4 powers)
     static constexpr size_t img = 0;                                            // [2][64][1024 B]
     static constexpr size_t scr = img + 2 * (size_t)LV_TB * LV_ROWB;            // [8 consumer waves][scr_wave] result scratch
-    static constexpr size_t seg_w = scr + LV_CW * scr_wave;                     // [2][LC_SEGS] T
-    static constexpr size_t seg_u = seg_w + 2 * sizeof(T) * LC_SEGS;            // [2][LC_SEGS] i32 (packed)
+    static constexpr size_t seg_w = scr + LV_CW * scr_wave;                     // [NW][2][LC_SEGS] T
+    static constexpr size_t seg_u = seg_w + NW * 2 * sizeof(T) * LC_SEGS;       // [2][LC_SEGS] i32 (packed)
     static constexpr size_t ent_r = seg_u + 2 * sizeof(int32_t) * LC_SEGS;      // [2][LC_ENT] i32
     static constexpr size_t ent_d = ent_r + 2 * sizeof(int32_t) * LC_ENT;       // [2][LC_ENT] T
     static constexpr size_t ent_s = ent_d + 2 * sizeof(T) * LC_ENT;             // [2][LC_ENT + 2] u16
@@ -572,7 +573,11 @@ template <typename T, int NPOW = 1> struct LvLds {
 // arithmetic (about 15 vector instructions per value, wagg_common.h::snyder_edd1_finite) runs on eight waves beside the
 // gather instead of on the waves that issue it (rounds 1-2: one stage per threshold on the loader waves of
 // sparse_lc_kernel, 0.29 ms per threshold; now 0.07).
-template <typename T, bool VEC, int NPOW = 1, bool EDD = false, bool GT = false>
+// NWT > 1 (many-plans, wagg_plan_create_many; NPOW = 1, no transform, (time, gridcell) data on a whole-line chunking): the
+// loaders stage the segment weights of NWT weightings of one structure (pv.seg_w, pv.seg_wx[0 .. NWT - 2]); the consumers keep
+// NWT sums per entry, each the NWT = 1 chain (same segments in the same order, one FMA each), so plane k is bit for bit the
+// single-weighting result; weighting k goes to out + k * out_pstride.  LDS: + (NWT - 1) * 4 KiB (fp32) / 8 KiB (fp64).
+template <typename T, bool VEC, int NPOW = 1, bool EDD = false, bool GT = false, int NWT = 1>
 __global__ __launch_bounds__(LV_THREADS) void sparse_lcv_kernel(PlanView<T> pv, const T *__restrict__ X, int64_t Ttot,
                                                                 int64_t ldx, int64_t G, T *__restrict__ out, int64_t ldo,
                                                                 int n_norm, long long n_items,
@@ -594,7 +599,9 @@ __global__ __launch_bounds__(LV_THREADS) void sparse_lcv_kernel(PlanView<T> pv, 
     typedef T vecE __attribute__((ext_vector_type(E)));
     typedef int int4v __attribute__((ext_vector_type(4)));
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-    using L = LvLds<T, NPOW>;
+    static_assert(NWT == 1 || (NPOW == 1 && !EDD && !GT), "weight planes: plain aggregation of (time, gridcell) data only");
+    using L = LvLds<T, NPOW, NWT>;
+    constexpr int PL = L::PL;                        // result planes of the pass
     char *img = smem_raw + L::img;
     T *sm_w = reinterpret_cast<T *>(smem_raw + L::seg_w);
     int32_t *sm_u = reinterpret_cast<int32_t *>(smem_raw + L::seg_u);
@@ -664,7 +671,7 @@ __global__ __launch_bounds__(LV_THREADS) void sparse_lcv_kernel(PlanView<T> pv, 
         // finite-data forms and the general ones below: that choice then depends on referenced data only, and is the same whether
         // the unreferenced quads of a line hold the field's values (device apply, whole lines from the host) or a dummy (the
         // quads-only rows of the host path).  (GT: one bit per load of the wave -- a load's cells belong to one quad.)
-        struct Regs { vecE v[TPW]; int mu; T mw; int er, es; T ed; int unref; };
+        struct Regs { vecE v[TPW]; int mu; T mw[NWT]; int er, es; T ed; int unref; };
         static_assert(LC_SEGS <= LV_LW * 64, "one metadata element per loader thread");
         auto issue = [&](Regs &R, const StreamDesc &d, int cell0, int tb) {
             if constexpr (GT) {
@@ -678,7 +685,9 @@ __global__ __launch_bounds__(LV_THREADS) void sparse_lcv_kernel(PlanView<T> pv, 
             {
                 const int k = tid < d.ns ? tid : d.ns - 1;
                 R.mu = pv.seg_u[d.sb + k];
-                R.mw = pv.seg_w[d.sb + k];
+                R.mw[0] = pv.seg_w[d.sb + k];
+#pragma unroll
+                for (int kw = 1; kw < NWT; ++kw) R.mw[kw] = pv.seg_wx[kw - 1][d.sb + k];
                 R.er = pv.ent_region[d.e0 + (tid < d.ne ? tid : d.ne - 1)];
                 R.ed = pv.ent_den[d.e0 + (tid < d.ne ? tid : d.ne - 1)];
                 R.es = pv.ent_seg_begin[d.e0 + (tid < d.ne ? tid : d.ne)];
@@ -746,7 +755,11 @@ __global__ __launch_bounds__(LV_THREADS) void sparse_lcv_kernel(PlanView<T> pv, 
             if (VEC && !EDD && (knob & 0x4000)) {            // (timing only: the rows came by LDS-DMA; 13 younger loads may stay out)
                 asm volatile("s_waitcnt vmcnt(13)" ::: "memory");
                 if (lane == 0) hdr[buf * 16 + 8 + wave] = 0;
-                if (tid < d.ns) { sm_u[buf * LC_SEGS + tid] = R.mu; sm_w[buf * LC_SEGS + tid] = R.mw; }
+                if (tid < d.ns) {
+                    sm_u[buf * LC_SEGS + tid] = R.mu;
+#pragma unroll
+                    for (int kw = 0; kw < NWT; ++kw) sm_w[(kw * 2 + buf) * LC_SEGS + tid] = R.mw[kw];
+                }
                 if (tid < d.ne) { sm_er[buf * LC_ENT + tid] = R.er; sm_ed[buf * LC_ENT + tid] = R.ed; }
                 if (tid <= d.ne) sm_es[buf * (LC_ENT + 2) + tid] = (uint16_t)(R.es - d.sb);
                 if (tid == 0) { hdr[buf * 16 + 0] = d.ne; hdr[buf * 16 + 1] = d.ns; hdr[buf * 16 + 2] = 0; hdr[buf * 16 + 3] = tb; }
@@ -819,7 +832,11 @@ __global__ __launch_bounds__(LV_THREADS) void sparse_lcv_kernel(PlanView<T> pv, 
                 for (int c = 0; c < E; ++c) v[c ^ (i % E)] = R.v[i][c];
                 *reinterpret_cast<vecE *>(im + (size_t)(tw0 + i) * LV_ROWB + 16 * (lane ^ (m / E))) = v;
             }
-            if (tid < d.ns) { sm_u[buf * LC_SEGS + tid] = R.mu; sm_w[buf * LC_SEGS + tid] = R.mw; }
+            if (tid < d.ns) {
+                sm_u[buf * LC_SEGS + tid] = R.mu;
+#pragma unroll
+                for (int kw = 0; kw < NWT; ++kw) sm_w[(kw * 2 + buf) * LC_SEGS + tid] = R.mw[kw];
+            }
             if (tid < d.ne) { sm_er[buf * LC_ENT + tid] = R.er; sm_ed[buf * LC_ENT + tid] = R.ed; }
             if (tid <= d.ne) sm_es[buf * (LC_ENT + 2) + tid] = (uint16_t)(R.es - d.sb);
             if (tid == 0) { hdr[buf * 16 + 0] = d.ne; hdr[buf * 16 + 1] = d.ns; hdr[buf * 16 + 2] = 0; hdr[buf * 16 + 3] = tb; }
@@ -878,8 +895,8 @@ __global__ __launch_bounds__(LV_THREADS) void sparse_lcv_kernel(PlanView<T> pv, 
     } else {
         // ==================== consumer waves: lane = timestep, entries from the item's shared counter ====================
         const int cw = wave - LV_LW;
-        constexpr int EPB = E / NPOW > 0 ? E / NPOW : 1;          // entries per result batch
-        constexpr int ROWS = EPB * NPOW;                          // its rows (entry, power): E per 16-byte-per-lane store
+        constexpr int EPB = E / PL > 0 ? E / PL : 1;              // entries per result batch
+        constexpr int ROWS = EPB * PL;                            // its rows (entry, plane): E per 16-byte-per-lane store
         constexpr int LPE = 64 / E;                               // lanes per row of that store
         T *scr = reinterpret_cast<T *>(smem_raw + L::scr + cw * L::scr_wave);
         // (LDS addresses as plain integers: the low half of a generic pointer into LDS is its LDS address; the image starts
@@ -924,29 +941,42 @@ __global__ __launch_bounds__(LV_THREADS) void sparse_lcv_kernel(PlanView<T> pv, 
                         for (int q = 0; q < EPB; ++q) if (q == kb) es[q] = e;       // (static indices: es stays in scalar registers)
                         const int s0 = __builtin_amdgcn_readfirstlane((int)sm_es[buf * (LC_ENT + 2) + e]);
                         const int s1 = __builtin_amdgcn_readfirstlane((int)sm_es[buf * (LC_ENT + 2) + e + 1]);
-                        T acc[NPOW];
+                        T acc[PL];
                         pair2 acc2[NPOW];
 #pragma unroll
-                        for (int pw = 0; pw < NPOW; ++pw) { acc[pw] = T(0); acc2[pw] = pair2{T(0), T(0)}; }
+                        for (int pw = 0; pw < PL; ++pw) acc[pw] = T(0);
+#pragma unroll
+                        for (int pw = 0; pw < NPOW; ++pw) acc2[pw] = pair2{T(0), T(0)};
                         for (int base = (knob & 256) ? s1 : s0; base < s1; base += 64) {
                             // lane j holds segment base + j (padding lanes: cell 0, weight 0: they add exactly 0 to finite data)
                             const int n = s1 - base < 64 ? s1 - base : 64;
                             const int k = base + (lane < n ? lane : 0);
                             int ul = (sm_u[buf * LC_SEGS + k] & 0xff) * (GT ? CELLB : (int)sizeof(T));   // byte offset of the cell in a row (GT: of its row)
-                            T wl = sm_w[buf * LC_SEGS + k];
-                            if (lane >= n) { ul = 0; wl = T(0); }
+                            T wl[NWT];
+#pragma unroll
+                            for (int kw = 0; kw < NWT; ++kw) wl[kw] = sm_w[(kw * 2 + buf) * LC_SEGS + k];
+                            if (lane >= n) {
+                                ul = 0;
+#pragma unroll
+                                for (int kw = 0; kw < NWT; ++kw) wl[kw] = T(0);
+                            }
                             for (int j0 = 0; j0 < n; j0 += 8) {
-                                T xv[8], wv[8], xh[EDD ? 8 : 1];
+                                T xv[8], wv[8], xh[EDD ? 8 : 1], wx[NWT][8];     // (wx: weightings 1 .. NWT - 1; wx[0] unused)
 #pragma unroll
                                 for (int j = 0; j < 8; ++j) {     // 8 independent LDS reads in flight
                                     const unsigned u = (unsigned)__builtin_amdgcn_readlane(ul, j0 + j);
-                                    if constexpr (sizeof(T) == 4) {
-                                        wv[j] = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, wl), j0 + j));
-                                    } else {
-                                        const long long wb = __builtin_bit_cast(long long, wl);
-                                        const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(wb & 0xffffffffll), j0 + j);
-                                        const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(wb >> 32), j0 + j);
-                                        wv[j] = __builtin_bit_cast(double, ((long long)hi << 32) | (long long)lo);
+#pragma unroll
+                                    for (int kw = 0; kw < NWT; ++kw) {
+                                        T wb1;
+                                        if constexpr (sizeof(T) == 4) {
+                                            wb1 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, wl[kw]), j0 + j));
+                                        } else {
+                                            const long long wb = __builtin_bit_cast(long long, wl[kw]);
+                                            const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(wb & 0xffffffffll), j0 + j);
+                                            const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(wb >> 32), j0 + j);
+                                            wb1 = __builtin_bit_cast(double, ((long long)hi << 32) | (long long)lo);
+                                        }
+                                        if (kw == 0) wv[j] = wb1; else wx[kw][j] = wb1;
                                     }
                                     xv[j] = *(lds_cptr)(uintptr_t)(rb ^ u);
                                     // (degree days: tasmax of the same cell sits 512 bytes further on -- the XOR never reaches
@@ -984,6 +1014,22 @@ __global__ __launch_bounds__(LV_THREADS) void sparse_lcv_kernel(PlanView<T> pv, 
                                             }
                                         }
                                     }
+                                } else if constexpr (NWT > 1) {
+#pragma unroll
+                                    for (int j = 0; j < 8; ++j) {
+#pragma unroll
+                                        for (int kw = 0; kw < NWT; ++kw) {                              // one plane per weighting
+                                            const T wk = kw == 0 ? wv[j] : wx[kw][j];
+                                            if constexpr (ODD) {
+                                                const T p = xv[j] * wk;
+                                                acc[kw] += (p == p) ? p : T(0);
+                                            } else if constexpr (sizeof(T) == 4) {
+                                                acc[kw] = __builtin_fmaf(xv[j], wk, acc[kw]);
+                                            } else {
+                                                acc[kw] = __builtin_fma(xv[j], wk, acc[kw]);
+                                            }
+                                        }
+                                    }
                                 } else {
 #pragma unroll
                                     for (int j = 0; j < 8; ++j) {
@@ -1007,15 +1053,15 @@ __global__ __launch_bounds__(LV_THREADS) void sparse_lcv_kernel(PlanView<T> pv, 
                         }
                         const T dn = sm_ed[buf * LC_ENT + e];
 #pragma unroll
-                        for (int pw = 0; pw < NPOW; ++pw) {
+                        for (int pw = 0; pw < PL; ++pw) {
                             if constexpr (PK && !ODD) acc[pw] = acc2[pw][0] + acc2[pw][1];
-                            scr[(kb * NPOW + pw) * 64 + lane] = acc[pw] / dn;                    // :77-80
+                            scr[(kb * PL + pw) * 64 + lane] = acc[pw] / dn;                      // :77-80
                         }
                     }
                     // (LDS operations of one wave execute in order: the reads below see the writes above)
                     for (int pass = 0; pass < (ROWS + E - 1) / E; ++pass) {
                         const int row = pass * E + lane / LPE, piece = lane % LPE;
-                        const int kq = row / NPOW, pw = row % NPOW;
+                        const int kq = row / PL, pw = row % PL;
                         int e = ne;
 #pragma unroll
                         for (int q = 0; q < EPB; ++q) if (q == kq) e = es[q];
@@ -1426,6 +1472,168 @@ static int check_apply_args(const wagg_plan *plan, const void *X, int64_t T, int
     WAGG_REQUIRE(X != nullptr && out != nullptr, "X/out is NULL");
     WAGG_REQUIRE(ldx >= (layout == WAGG_LAYOUT_TG ? plan->info.G : T), "ldx %lld too small", (long long)ldx);
     WAGG_REQUIRE(ldo >= (out_layout == WAGG_OUT_TR ? (int64_t)plan->info.R : T), "ldo %lld too small", (long long)ldo);
+    return WAGG_OK;
+}
+
+// ---- many-plans (wagg_plan_create_many): K weightings x (fine level + derived coarse levels) from one pass over X -------------
+// Derived level of a many-plan: out[t][c] = (sum of the partial rows cidx[cb[c]] .. cidx[cb[c + 1] - 1] of the buffer)[t] / den[c]
+// -- the rows of the fine regions of c -- for a 64-timestep tile per workgroup.  A large coarse region (a country: hundreds
+// of partial rows) is cut into S fixed strided slices (slice s: rows s, s + S, ...), each summed by its own threads, and the
+// slices are added in slice order: the same bits on every run.  A region without rows gives 0 / den (S7).
+constexpr int LVC_THREADS = 1024;
+template <typename T, bool TR>
+__global__ __launch_bounds__(LVC_THREADS) void combine_level_kernel(const T *__restrict__ P, int64_t ldp, const int32_t *__restrict__ cb,
+                                                                    const int32_t *__restrict__ cidx, const T *__restrict__ den,
+                                                                    int64_t Ttot, T *__restrict__ out, int64_t ldo) {
+    constexpr int V = 16 / sizeof(T);
+    typedef T vecv __attribute__((ext_vector_type(V)));
+    constexpr int TQ = 64 / V;                      // threads per 64-timestep row
+    constexpr int S = LVC_THREADS / TQ;             // slices: 64 (fp32) / 32 (fp64)
+    __shared__ T part[S][64 + 1];
+    const int64_t c = blockIdx.x, t0 = (int64_t)blockIdx.y * 64;
+    const int tq = threadIdx.x % TQ, sl = threadIdx.x / TQ;
+    const int32_t kb = cb[c], ke = cb[c + 1];
+    vecv s;
+#pragma unroll
+    for (int q = 0; q < V; ++q) s[q] = T(0);
+    const T *p = P + t0 + V * tq;                   // (rows are ldp >= T rounded up to 64: the tile is inside the row)
+    for (int32_t k = kb + sl; k < ke; k += S) s += *reinterpret_cast<const vecv *>(p + (int64_t)cidx[k] * ldp);
+#pragma unroll
+    for (int q = 0; q < V; ++q) part[sl][V * tq + q] = s[q];
+    __syncthreads();
+    if (threadIdx.x < 64) {
+        T sum = T(0);
+        for (int q = 0; q < S; ++q) sum += part[q][threadIdx.x];
+        const int64_t t = t0 + threadIdx.x;
+        if (t < Ttot) out[TR ? t * ldo + c : c * ldo + t] = sum / den[c];
+    }
+}
+
+// one pass of sparse_lcv_kernel over NW weightings: fp32 up to four, fp64 up to two (the staged weights of a third would not
+// fit the CU's LDS next to the fp64 image)
+static_assert(LvLds<float, 1, MANY_MAX_W>::total <= 160 * 1024, "fp32: four weightings in one pass");
+static_assert(LvLds<double, 1, 2>::total <= 160 * 1024, "fp64: two weightings in one pass");
+constexpr int many_pass_w(bool f64) { return f64 ? 2 : MANY_MAX_W; }
+template <typename T, bool VEC, int NW> static constexpr LcvEntry<T> lcv_many_entry() {
+    return {sparse_lcv_kernel<T, VEC, 1, false, false, NW>, LvLds<T, 1, NW>::total};
+}
+template <typename T> static LcvEntry<T> lcv_many_pick(bool vec, int nw) {
+    if constexpr (sizeof(T) == 4) {
+        static const LcvEntry<T> t[2][4] = {{lcv_many_entry<T, false, 1>(), lcv_many_entry<T, false, 2>(), lcv_many_entry<T, false, 3>(), lcv_many_entry<T, false, 4>()},
+                                            {lcv_many_entry<T, true, 1>(), lcv_many_entry<T, true, 2>(), lcv_many_entry<T, true, 3>(), lcv_many_entry<T, true, 4>()}};
+        return t[vec ? 1 : 0][nw - 1];
+    } else {
+        static const LcvEntry<T> t[2][2] = {{lcv_many_entry<T, false, 1>(), lcv_many_entry<T, false, 2>()},
+                                            {lcv_many_entry<T, true, 1>(), lcv_many_entry<T, true, 2>()}};
+        return t[vec ? 1 : 0][nw - 1];
+    }
+}
+
+// the weightings of a many-plan share one pass over X: (time, gridcell) data on the whole-line chunking of T, the
+// loader/consumer kernel allowed by the plan's flags.  Anything else runs the single-plan path once per weighting.
+template <typename T> static bool many_fused(const wagg_plan *plan, int layout) {
+    const wagg_plan *p0 = plan->many_w[0];
+    return layout == WAGG_LAYOUT_TG && (sizeof(T) == 4 ? p0->has_lines : p0->has_lines64) &&
+           !(p0->flags & (WAGG_PLAN_NO_LC | WAGG_PLAN_NO_STREAM | WAGG_PLAN_LC_MFMA));
+}
+
+// out: the concatenated result (plane (l, k) at column / row many_col(l, k)); compact: as in launch_sparse
+template <typename T, int TB>
+static int launch_many(const wagg_plan *plan, const T *X, int64_t Ttot, int64_t ldx, int layout, T *out, int64_t ldo,
+                       int out_layout, hipStream_t stream, int compact = COMPACT_NONE) {
+    const int K = (int)plan->many_w.size();
+    const wagg_plan *p0 = plan->many_w[0];
+    auto plane = [&](int l, int k) { const int64_t off = plan->many_col(l, k); return out + (out_layout == WAGG_OUT_TR ? off : off * ldo); };
+    if (!many_fused<T>(plan, layout)) {
+        if (plan->many_nlv > 0) {
+            set_error("many-plan with derived levels: they need %s (time, gridcell) data on the plan's whole-line chunking%s",
+                      sizeof(T) == 4 ? "fp32" : "fp64",
+                      layout != WAGG_LAYOUT_TG ? " -- this is (gridcell, time) data"
+                      : (p0->flags & (WAGG_PLAN_NO_LC | WAGG_PLAN_NO_STREAM | WAGG_PLAN_LC_MFMA)) ? " -- the plan's flags rule its kernel out"
+                                                                                                  : " -- the table has none (no row length, or too scattered)");
+            return WAGG_EUNSUPPORTED;
+        }
+        WAGG_REQUIRE(!compact, "compact rows need the whole-line chunking of this plan and data type");
+        for (int k = 0; k < K; ++k)     // the single-plan kernels with weighting k's weights and den: the same bits as its own plan
+            if (int rc = launch_sparse<T, TB>(plan->many_w[k], X, Ttot, ldx, layout, plane(0, k), ldo, out_layout, stream)) return rc;
+        return WAGG_OK;
+    }
+    if (Ttot == 0) return WAGG_OK;
+    auto chunking = [&](const wagg_plan *p) -> const SparsePlanDev & { return sizeof(T) == 4 ? p->dl : p->dl64; };
+    const SparsePlanDev &d = chunking(p0);
+    WAGG_REQUIRE(d.n_part > 0, "many-plan: the whole-line chunking has no partial rows");
+    const int64_t Gcomp = compact == COMPACT_QUADS ? d.Gq : d.Gc;
+    WAGG_REQUIRE(!compact || (Gcomp > 0 && ldx >= Gcomp && d.g0_normal == 0), "compact rows: the whole-line kernel does not take the whole plan");
+    const int64_t Gk = compact ? Gcomp : (int64_t)p0->info.G;
+    auto wts = [&](int k) -> const T * { if constexpr (sizeof(T) == 4) return chunking(plan->many_w[k]).seg_w32.p; else return chunking(plan->many_w[k]).seg_w64.p; };
+    auto den_fine = [&](int k) -> const T * { if constexpr (sizeof(T) == 4) return chunking(plan->many_w[k]).den32.p; else return chunking(plan->many_w[k]).den64.p; };
+    PlanView<T> pv;
+    std::memset(&pv, 0, sizeof(pv));
+    pv.xoff = T(0); pv.xpow = 0; pv.X2 = nullptr; pv.n_thr = 1;
+    pv.grp_chunk_begin = d.grp_chunk_begin.p; pv.grp_giant = d.grp_giant.p;
+    pv.chunk_u_begin = d.chunk_u_begin.p; pv.chunk_e_begin = d.chunk_e_begin.p;
+    pv.ucell = compact == COMPACT_QUADS ? d.ucell_q.p : (compact ? d.ucell_c.p : d.ucell.p);
+    pv.ent_region = d.ent_region.p; pv.ent_seg_begin = d.ent_seg_begin.p; pv.seg_u = d.seg_u.p;
+    if constexpr (sizeof(T) == 4) pv.ent_den = d.ent_den32.p; else pv.ent_den = d.ent_den64.p;
+    pv.den = pv.ent_den;               // partial rows: nothing is divided before the rows are combined (ent_den = 1.0)
+    pv.chunk_desc = d.chunk_desc.p; pv.g0_normal = d.g0_normal; pv.c0_normal = d.c0_normal;
+    const int64_t ldws = (Ttot + 63) / 64 * 64, kpstride = ldws * d.n_part;
+    T *ws = static_cast<T *>(plan->staging(stream, sizeof(T) * (size_t)kpstride * (size_t)K));
+    if (!ws) { set_error("staging buffer of %.1f MB: allocation failed", (double)(sizeof(T) * kpstride * K) * 1e-6); return WAGG_ENOMEM; }
+    const bool vec = ((reinterpret_cast<uintptr_t>(X) & 15) == 0) && ((ldx * sizeof(T)) % 16 == 0);
+    const int n_norm = (int)d.n_groups - d.g0_normal;
+    if (n_norm > 0) {
+        const long long n_items = (long long)n_norm * ((Ttot + LV_TB - 1) / LV_TB);
+        const long long nw = n_items < plan->ncu ? n_items : plan->ncu;
+        const int per_pass = many_pass_w(sizeof(T) == 8);
+        for (int k0 = 0; k0 < K; k0 += per_pass) {           // (fp64 with three or four weightings: two passes)
+            const int nwk = K - k0 < per_pass ? K - k0 : per_pass;
+            pv.seg_w = wts(k0);
+            for (int i = 0; i < 3; ++i) pv.seg_wx[i] = i + 1 < nwk ? wts(k0 + 1 + i) : nullptr;
+            const LcvEntry<T> ke = lcv_many_pick<T>(vec, nwk);
+            WAGG_HIP(allow_dynamic_lds((const void *)ke.kern, ke.lds));
+            launch_timed(true, ke.kern, dim3((unsigned)nw), dim3(LV_THREADS), ke.lds, stream, pv, X, Ttot, ldx, Gk,
+                         ws + (int64_t)k0 * kpstride, ldws, n_norm, n_items, (unsigned long long *)nullptr, 0, kpstride, T(0));
+            WAGG_HIP(hipGetLastError());
+        }
+    }
+    if (d.g0_normal > 0) {                                    // giant groups: the chunk-walking kernel, once per weighting
+        pv.n_groups = d.g0_normal;
+        const int64_t n_tb = (Ttot + TB - 1) / TB, nblk = (int64_t)pv.n_groups * n_tb;
+        WAGG_REQUIRE(nblk < (int64_t)0x7fffffff, "grid too large: %lld", (long long)nblk);
+        const size_t shmem = SparseLds<T, TB>::total;
+        auto kern = vec ? sparse_gather_kernel<T, TB, WAGG_LAYOUT_TG, WAGG_OUT_RT, true> : sparse_gather_kernel<T, TB, WAGG_LAYOUT_TG, WAGG_OUT_RT, false>;
+        WAGG_HIP(allow_dynamic_lds((const void *)kern, shmem));
+        for (int k = 0; k < K; ++k) {
+            pv.seg_w = wts(k);
+            launch_timed(n_norm == 0, kern, dim3((unsigned)nblk), dim3(UC), shmem, stream, pv, X, Ttot, ldx, (int64_t)p0->info.G,
+                         ws + (int64_t)k * kpstride, ldws);
+            WAGG_HIP(hipGetLastError());
+        }
+    }
+    const bool tr = out_layout == WAGG_OUT_TR;
+    const unsigned ntt = (unsigned)((Ttot + 63) / 64);
+    for (int k = 0; k < K && p0->info.R > 0; ++k) {           // the fine level: combine_parts_kernel as for the single plan
+        dim3 tg((unsigned)((p0->info.R + 63) / 64), ntt, 1);
+        auto ck = tr ? combine_parts_kernel<T, true> : combine_parts_kernel<T, false>;
+        hipLaunchKernelGGL(ck, tg, dim3(CB_THREADS), 0, stream, (const T *)(ws + (int64_t)k * kpstride), ldws,
+                           (const int32_t *)d.part_begin.p, den_fine(k), (int64_t)p0->info.R, Ttot, plane(0, k), ldo, (int64_t)0, (int64_t)0);
+        WAGG_HIP(hipGetLastError());
+    }
+    for (int l = 0; l < plan->many_nlv; ++l) {                // derived levels: the same partial rows, grouped by coarse region
+        const ManyLevel &lv = plan->many_lv[l];
+        if (lv.R == 0) continue;
+        const int32_t *cb = sizeof(T) == 4 ? lv.cpart_begin32.p : lv.cpart_begin64.p;
+        const int32_t *ci = sizeof(T) == 4 ? lv.cpart_idx32.p : lv.cpart_idx64.p;
+        auto lk = tr ? combine_level_kernel<T, true> : combine_level_kernel<T, false>;
+        for (int k = 0; k < K; ++k) {
+            const T *den;
+            if constexpr (sizeof(T) == 4) den = lv.den32[k].p; else den = lv.den64[k].p;
+            hipLaunchKernelGGL(lk, dim3((unsigned)lv.R, ntt), dim3(LVC_THREADS), 0, stream, (const T *)(ws + (int64_t)k * kpstride), ldws,
+                               cb, ci, den, Ttot, plane(l + 1, k), ldo);
+            WAGG_HIP(hipGetLastError());
+        }
+    }
     return WAGG_OK;
 }
 
@@ -2399,3 +2607,229 @@ int wagg::entry::apply_edd_f64(const wagg_plan *plan, const double *tasmin_dev, 
     return wagg::apply_edd<double, 32>(plan, tasmin_dev, tasmax_dev, T, ldx, layout, offset, thresholds, n_thr, out_dev,
                                        ldo, out_pstride, out_layout, (hipStream_t)stream);
 }
+
+// ---------------------------------------------------------------------------------------------
+// many-plans: K weightings x (fine level + derived coarse levels) of one table (include/wagg.h)
+// ---------------------------------------------------------------------------------------------
+extern "C" int wagg_plan_create_many(const int32_t *cell_idx, const int32_t *region_code, const double *const *w_eff, int n_weights,
+                                     int64_t nseg, int64_t G, int32_t R, int64_t row_len, const int32_t *const *level_code,
+                                     const int32_t *level_R, int n_levels, int flags, wagg_plan **out) {
+    using namespace wagg;
+    WAGG_REQUIRE(out != nullptr, "out is NULL");
+    *out = nullptr;
+    WAGG_REQUIRE(n_weights >= 1 && n_weights <= MANY_MAX_W, "n_weights = %d: a many-plan takes 1 .. %d weightings", n_weights, MANY_MAX_W);
+    WAGG_REQUIRE(w_eff != nullptr, "w_eff is NULL");
+    WAGG_REQUIRE(n_levels >= 0 && n_levels <= MANY_MAX_LEVELS, "n_levels = %d: a many-plan derives 0 .. %d coarse levels", n_levels, MANY_MAX_LEVELS);
+    WAGG_REQUIRE(n_levels == 0 || (level_code != nullptr && level_R != nullptr), "level_code / level_R is NULL");
+    WAGG_REQUIRE(nseg >= 0 && G > 0 && R >= 0, "bad sizes nseg=%lld G=%lld R=%d", (long long)nseg, (long long)G, R);
+    WAGG_REQUIRE(nseg == 0 || (cell_idx && region_code), "NULL segment arrays");
+    for (int k = 0; k < n_weights; ++k) WAGG_REQUIRE(nseg == 0 || w_eff[k] != nullptr, "weight column %d is NULL", k);
+    for (int l = 0; l < n_levels; ++l) {
+        WAGG_REQUIRE(level_R[l] >= 0, "level_R[%d] = %d < 0", l, level_R[l]);
+        WAGG_REQUIRE(nseg == 0 || level_code[l] != nullptr, "level_code[%d] is NULL", l);
+    }
+    const int K = n_weights;
+    int64_t out_cols = (int64_t)K * R;
+    for (int l = 0; l < n_levels; ++l) out_cols += (int64_t)K * level_R[l];
+    WAGG_REQUIRE(out_cols < (int64_t)0x7fffffff, "the concatenated result has %lld columns (must fit int32)", (long long)out_cols);
+    std::unique_ptr<wagg_plan> plan(new (std::nothrow) wagg_plan());
+    if (!plan) { set_error("out of host memory"); return WAGG_ENOMEM; }
+    std::vector<std::vector<double>> cols((size_t)K);
+    try {
+        // every check runs here, before any device call
+        std::vector<uint8_t> kept((size_t)nseg, 0);       // a row is kept if some weighting keeps it
+        for (int64_t i = 0; i < nseg; ++i) {
+            const int32_t r = region_code[i];
+            WAGG_REQUIRE(r < R, "region_code[%lld]=%d out of range [0,%d)", (long long)i, r, R);
+            WAGG_REQUIRE(cell_idx[i] >= 0 && cell_idx[i] < G, "cell_idx[%lld]=%d out of range", (long long)i, cell_idx[i]);
+            bool any = false;
+            for (int k = 0; k < K; ++k) any = any || !std::isnan(w_eff[k][i]);
+            kept[(size_t)i] = any ? 1 : 0;
+        }
+        plan->many_nlv = n_levels;
+        for (int l = 0; l < n_levels; ++l) {
+            ManyLevel &lv = plan->many_lv[l];
+            lv.R = level_R[l];
+            lv.fine_to_coarse.assign((size_t)R, -1);
+            const int32_t *lc = level_code[l];
+            for (int64_t i = 0; i < nseg; ++i) {
+                const int32_t c = lc[i] < 0 ? -1 : lc[i];
+                WAGG_REQUIRE(c < lv.R, "level_code[%d][%lld]=%d out of range [0,%d)", l, (long long)i, c, lv.R);
+                if (!kept[(size_t)i]) continue;
+                const int32_t r = region_code[i] < 0 ? -1 : region_code[i];
+                WAGG_REQUIRE((r < 0) == (c < 0), "level %d does not nest in the fine level: row %lld has fine code %d and coarse code %d "
+                             "(a label is null on one level only)", l, (long long)i, r, c);
+                if (r < 0) continue;
+                int32_t &m = lv.fine_to_coarse[(size_t)r];
+                WAGG_REQUIRE(m < 0 || m == c, "level %d does not nest in the fine level: row %lld puts fine region %d in coarse region %d, "
+                             "an earlier row put it in %d", l, (long long)i, r, c, m);
+                m = c;
+            }
+            // coarse denominators in row order, fp64: what wagg_plan_create over the coarse codes computes (aggregations.py:79)
+            lv.den.assign((size_t)K, std::vector<double>((size_t)lv.R, 0.0));
+            for (int k = 0; k < K; ++k)
+                for (int64_t i = 0; i < nseg; ++i) {
+                    const int32_t c = lc[i];
+                    if (c < 0 || std::isnan(w_eff[k][i])) continue;
+                    lv.den[(size_t)k][(size_t)c] += w_eff[k][i];
+                }
+        }
+        // weighting k's column over the kept rows: NaN where it drops a row another weighting keeps becomes 0 (S6), so all K
+        // plans coalesce the same rows into the same segments and chunk them alike (with K = 1: the column as it is)
+        for (int k = 0; k < K; ++k) {
+            cols[(size_t)k].resize((size_t)nseg);
+            for (int64_t i = 0; i < nseg; ++i) {
+                const double w = w_eff[k][i];
+                cols[(size_t)k][(size_t)i] = !kept[(size_t)i] ? std::numeric_limits<double>::quiet_NaN() : (std::isnan(w) ? 0.0 : w);
+            }
+        }
+    } catch (const std::bad_alloc &) {
+        set_error("out of host memory");
+        return WAGG_ENOMEM;
+    }
+    for (int k = 0; k < K; ++k) {
+        wagg_plan *sub = nullptr;
+        const int rc = wagg_plan_create(cell_idx, region_code, cols[(size_t)k].data(), nseg, G, R, row_len, flags, &sub);
+        if (rc != WAGG_OK) return rc;
+        plan->many_w.push_back(sub);
+        const wagg_plan_info &a = plan->many_w[0]->info, &b = sub->info;
+        if (a.nnz != b.nnz || a.n_chunks != b.n_chunks || a.n_partial_rows != b.n_partial_rows || a.n_partial_rows64 != b.n_partial_rows64 ||
+            sub->has_lines != plan->many_w[0]->has_lines || sub->has_lines64 != plan->many_w[0]->has_lines64) {
+            set_error("many-plan: the chunkings of weighting %d differ from those of weighting 0", k);
+            return WAGG_EINTERNAL;
+        }
+    }
+    const wagg_plan *p0 = plan->many_w[0];
+    plan->info = p0->info;
+    plan->info.R = (int32_t)out_cols;
+    plan->many_R0 = R;
+    plan->device = p0->device; plan->ncu = p0->ncu; plan->flags = p0->flags;
+    try {
+        plan->den_host.reserve((size_t)out_cols);
+        for (int k = 0; k < K; ++k) plan->den_host.insert(plan->den_host.end(), plan->many_w[k]->den_host.begin(), plan->many_w[k]->den_host.end());
+        for (int l = 0; l < n_levels; ++l)
+            for (int k = 0; k < K; ++k) plan->den_host.insert(plan->den_host.end(), plan->many_lv[l].den[(size_t)k].begin(), plan->many_lv[l].den[(size_t)k].end());
+        for (int l = 0; l < n_levels; ++l) {
+            ManyLevel &lv = plan->many_lv[l];
+            for (int k = 0; k < K; ++k) {
+                const std::vector<double> &dd = lv.den[(size_t)k];
+                std::vector<float> d32(dd.size());
+                for (size_t c = 0; c < dd.size(); ++c) d32[c] = (float)dd[c];
+                WAGG_HIP(lv.den32[k].upload(d32));
+                WAGG_HIP(lv.den64[k].upload(dd));
+            }
+            // coarse region c = the partial rows of its fine regions (ascending fine code), for each whole-line chunking
+            std::vector<int32_t> fb((size_t)lv.R + 1, 0), fine((size_t)R);
+            for (int32_t r = 0; r < R; ++r) if (lv.fine_to_coarse[(size_t)r] >= 0) ++fb[(size_t)lv.fine_to_coarse[(size_t)r] + 1];
+            for (int32_t c = 0; c < lv.R; ++c) fb[(size_t)c + 1] += fb[(size_t)c];
+            {
+                std::vector<int32_t> pos(fb.begin(), fb.end() - 1);
+                for (int32_t r = 0; r < R; ++r) if (lv.fine_to_coarse[(size_t)r] >= 0) fine[(size_t)pos[(size_t)lv.fine_to_coarse[(size_t)r]]++] = r;
+            }
+            for (int w = 0; w < 2; ++w) {
+                const bool has = w == 0 ? p0->has_lines : p0->has_lines64;
+                if (!has) continue;
+                const SparsePlanDev &d = w == 0 ? p0->dl : p0->dl64;
+                std::vector<int32_t> pb((size_t)R + 1);
+                WAGG_HIP(staged_d2h(pb.data(), d.part_begin.p, sizeof(int32_t) * pb.size()));
+                std::vector<int32_t> cb((size_t)lv.R + 1, 0), ci;
+                ci.reserve((size_t)d.n_part);
+                for (int32_t c = 0; c < lv.R; ++c) {
+                    for (int32_t j = fb[(size_t)c]; j < fb[(size_t)c + 1]; ++j)
+                        for (int32_t p = pb[(size_t)fine[(size_t)j]]; p < pb[(size_t)fine[(size_t)j] + 1]; ++p) ci.push_back(p);
+                    cb[(size_t)c + 1] = (int32_t)ci.size();
+                }
+                WAGG_HIP((w == 0 ? lv.cpart_begin32 : lv.cpart_begin64).upload(cb));
+                WAGG_HIP((w == 0 ? lv.cpart_idx32 : lv.cpart_idx64).upload(ci));
+            }
+        }
+        WAGG_HIP(hipDeviceSynchronize());
+    } catch (const std::bad_alloc &) {
+        set_error("out of host memory");
+        return WAGG_ENOMEM;
+    }
+    *out = plan.release();
+    return WAGG_OK;
+}
+
+extern "C" int wagg_plan_many_info(const wagg_plan *plan, int *n_weights, int *n_levels, int32_t *level_R, int64_t *out_cols) {
+    WAGG_REQUIRE(plan != nullptr, "plan is NULL");
+    const bool many = plan->is_many();
+    if (n_weights) *n_weights = many ? (int)plan->many_w.size() : 0;
+    if (n_levels) *n_levels = many ? plan->many_nlv : 0;
+    if (level_R) for (int l = 0; many && l < plan->many_nlv; ++l) level_R[l] = plan->many_lv[l].R;
+    if (out_cols) *out_cols = plan->info.R;
+    return WAGG_OK;
+}
+
+extern "C" int wagg_plan_get_den_many(const wagg_plan *plan, int weighting, int level, double *den_host) {
+    WAGG_REQUIRE(plan != nullptr && den_host != nullptr, "NULL argument");
+    WAGG_REQUIRE(plan->is_many(), "not a many-plan (wagg_plan_create_many)");
+    WAGG_REQUIRE(weighting >= 0 && weighting < (int)plan->many_w.size(), "weighting %d out of range", weighting);
+    WAGG_REQUIRE(level >= 0 && level <= plan->many_nlv, "level %d out of range", level);
+    const int32_t n = level == 0 ? plan->many_R0 : plan->many_lv[level - 1].R;
+    if (n) std::memcpy(den_host, plan->den_host.data() + plan->many_col(level, weighting), sizeof(double) * (size_t)n);
+    return WAGG_OK;
+}
+
+namespace wagg {
+template <typename T>
+static int apply_many_dev(const wagg_plan *plan, const T *X, int64_t Tn, int64_t ldx, int layout, T *out, int64_t ldo,
+                          int out_layout, void *stream) {
+    int rc = check_apply_args(plan, X, Tn, ldx, layout, out, ldo, out_layout);
+    if (rc != WAGG_OK) return rc;
+    return launch_many<T, (sizeof(T) == 4 ? 64 : 32)>(plan, X, Tn, ldx, layout, out, ldo, out_layout, (hipStream_t)stream);
+}
+
+// host-resident field through a many-plan: the row-block pipeline of a single plan with one output block per row block that is
+// out_cols wide, so the field crosses PCIe once (lines-only / quads-only packing: the structure is the same for all planes)
+template <typename T>
+static int apply_many_host(const wagg_plan *plan, const T *X, int64_t Tn, int64_t ldx, int layout, T *out, int64_t ldo,
+                           int out_layout, int flags) {
+    clear_error();
+    int rc = check_apply_args(plan, X, Tn, ldx, layout, out, ldo, out_layout);
+    if (rc != WAGG_OK || Tn == 0) return rc;
+    WAGG_REQUIRE((flags & ~(WAGG_HOST_PIN | WAGG_HOST_WHOLE | WAGG_HOST_LINES | WAGG_HOST_LINES_WHOLE)) == 0, "unknown host flags 0x%x", flags);
+    if ((rc = check_plan_device(plan)) != WAGG_OK) return rc;
+    constexpr int TB = sizeof(T) == 4 ? 64 : 32;
+    if (layout == WAGG_LAYOUT_TG && out_layout == WAGG_OUT_TR && !(flags & WAGG_HOST_WHOLE)) {
+        const wagg_plan *p0 = plan->many_w[0];
+        const bool fused = many_fused<T>(plan, layout);
+        const SparsePlanDev *dc = fused ? (sizeof(T) == 4 ? &p0->dl : &p0->dl64) : nullptr;
+        return host_rows_pipeline<T>(plan, X, Tn, ldx, out, ldo, flags, 1, 0,
+                                     [&](const T *xd, int64_t rows, int64_t ldx_dev, T *od, hipStream_t st, int compact) {
+                                         return launch_many<T, TB>(plan, xd, rows, ldx_dev, WAGG_LAYOUT_TG, od, ldo, WAGG_OUT_TR, st, compact);
+                                     }, dc, true);
+    }
+    const int64_t xrows = layout == WAGG_LAYOUT_TG ? Tn : plan->info.G;
+    const int64_t orows = out_layout == WAGG_OUT_TR ? Tn : plan->info.R;
+    ScratchBuf<T> dx, dout;
+    WAGG_HIP(dx.alloc((size_t)(xrows * ldx)));
+    WAGG_HIP(dout.alloc((size_t)(orows * ldo)));
+    const int64_t xcols = layout == WAGG_LAYOUT_TG ? plan->info.G : Tn, ocols = out_layout == WAGG_OUT_TR ? plan->info.R : Tn;
+    const bool pin = (flags & WAGG_HOST_PIN) != 0;
+    if ((rc = copy_to_device(dx.p, X, sizeof(T) * (size_t)((xrows - 1) * ldx + xcols), pin)) != WAGG_OK) return rc;
+    WAGG_HIP(hipMemset(dout.p, 0, sizeof(T) * (size_t)(orows * ldo)));
+    if ((rc = launch_many<T, TB>(plan, dx.p, Tn, ldx, layout, dout.p, ldo, out_layout, nullptr)) != WAGG_OK) return rc;
+    WAGG_HIP(hipDeviceSynchronize());
+    return copy_rows_to_host(out, dout.p, orows, sizeof(T) * (size_t)ldo, sizeof(T) * (size_t)ocols, pin);
+}
+}  // namespace wagg
+
+int wagg::entry::apply_many_f32(const wagg_plan *plan, const float *X, int64_t T, int64_t ldx, int layout, float *out, int64_t ldo,
+                                int out_layout, void *stream) {
+    return wagg::apply_many_dev<float>(plan, X, T, ldx, layout, out, ldo, out_layout, stream);
+}
+int wagg::entry::apply_many_f64(const wagg_plan *plan, const double *X, int64_t T, int64_t ldx, int layout, double *out, int64_t ldo,
+                                int out_layout, void *stream) {
+    return wagg::apply_many_dev<double>(plan, X, T, ldx, layout, out, ldo, out_layout, stream);
+}
+int wagg::entry::apply_many_host_f32(const wagg_plan *plan, const float *X, int64_t T, int64_t ldx, int layout, float *out, int64_t ldo,
+                                     int out_layout, int flags) {
+    return wagg::apply_many_host<float>(plan, X, T, ldx, layout, out, ldo, out_layout, flags);
+}
+int wagg::entry::apply_many_host_f64(const wagg_plan *plan, const double *X, int64_t T, int64_t ldx, int layout, double *out, int64_t ldo,
+                                     int out_layout, int flags) {
+    return wagg::apply_many_host<double>(plan, X, T, ldx, layout, out, ldo, out_layout, flags);
+}
+bool wagg::entry::is_many_plan(const wagg_plan *plan) { return plan != nullptr && plan->is_many(); }

@@ -75,6 +75,22 @@ struct SparsePlanDev {
 };
 constexpr int COMPACT_NONE = 0, COMPACT_LINES = 1, COMPACT_QUADS = 2;       // which row launch_sparse is handed
 
+// What a many-plan (wagg_plan_create_many) adds: K weightings of one table and n_levels coarse levels derived from the fine
+// one.  The weightings are K plans built from the same kept rows (a row another weighting keeps has weight 0 where this one is
+// NaN), so their chunkings are the same structure and only the segment weights and denominators differ; the kernels read the
+// structure of weighting 0.  Coarse region c of a level is the sum of the partial rows in cpart_idx[cpart_begin[c] ..
+// cpart_begin[c + 1]) of a whole-line chunking (the rows of its fine regions in fine-code order), divided by its den.
+constexpr int MANY_MAX_W = 4, MANY_MAX_LEVELS = 3;
+struct ManyLevel {
+    int32_t R = 0;
+    std::vector<int32_t> fine_to_coarse;             // [R fine] coarse code, -1: the fine region has no kept row
+    std::vector<std::vector<double>> den;            // [K][R] fp64, row order (= wagg_plan_get_den of a plan over the coarse codes)
+    DevBuf<float> den32[MANY_MAX_W];                 // [K] device copies
+    DevBuf<double> den64[MANY_MAX_W];
+    DevBuf<int32_t> cpart_begin32, cpart_idx32;      // over the partial rows of the fp32 whole-line chunking (dl)
+    DevBuf<int32_t> cpart_begin64, cpart_idx64;      // ... of the fp64 one (dl64)
+};
+
 }  // namespace wagg
 
 struct wagg_plan {
@@ -93,6 +109,18 @@ struct wagg_plan {
     // set by a kernel whose consumer-wave barrier timed out (host-mapped, so the host can read it
     // without touching the stream); checked by the next apply, wagg_plan_status and the *_host_ forms
     int *timeout_host = nullptr, *timeout_dev = nullptr;
+    // many-plans only (wagg_plan_create_many): `many_w[k]` = the plan of weighting k (owned); this handle's info.R is the width
+    // of the concatenated result (out_cols) and den_host its denominators in that order; its own chunkings stay empty
+    std::vector<wagg_plan *> many_w;
+    wagg::ManyLevel many_lv[wagg::MANY_MAX_LEVELS];
+    int many_nlv = 0;
+    int32_t many_R0 = 0;
+    bool is_many() const { return !many_w.empty(); }
+    int64_t many_col(int level, int k) const {       // first column of plane (level, k): level-major, then weighting
+        int64_t off = 0;
+        for (int l = 0; l < level; ++l) off += (int64_t)many_w.size() * (l == 0 ? many_R0 : many_lv[l - 1].R);
+        return off + (int64_t)k * (level == 0 ? many_R0 : many_lv[level - 1].R);
+    }
     // Region-major staging buffers of the (time, region) output form, one per stream that has applied
     // this plan (kept until the plan is destroyed; blocks of the scratch pool, wagg_scratch.hip).  A stream-ordered hipMallocAsync / hipFreeAsync pair
     // per apply made every call block for the whole kernel (0.28 ms enqueue against 0.01 ms without).
@@ -119,6 +147,7 @@ struct wagg_plan {
     // the stream is about to be destroyed (the host pipeline's own compute stream): its staging goes with it, so the
     // list stays bounded and a later stream that happens to get the same handle starts clean
     void drop_staging(hipStream_t st) const {
+        for (const wagg_plan *p : many_w) p->drop_staging(st);
         std::lock_guard<std::mutex> lock(ws_mu);
         for (size_t i = 0; i < ws.size(); ++i)
             if (ws[i].stream == st) {
@@ -128,6 +157,7 @@ struct wagg_plan {
             }
     }
     ~wagg_plan() {
+        for (wagg_plan *p : many_w) delete p;
         if (timeout_host) wagg::note_cleanup(hipHostFree(timeout_host), "hipHostFree(status word)");
         // (straight back to the driver: hipFree waits for whatever the last apply on that stream left running, which a
         //  block handed to the pool's next taker would not)
@@ -141,6 +171,7 @@ template <typename T> struct PlanView {
     const int32_t *grp_chunk_begin, *grp_giant, *chunk_u_begin, *chunk_e_begin, *ucell;
     const int32_t *ent_region, *ent_seg_begin, *seg_u;
     const T *seg_w, *den, *ent_den;   // ent_den[e] = den[ent_region[e]]
+    const T *seg_wx[3];          // many-plans (wagg_plan_create_many): the segment weights of weightings 1 .. NW - 1 of a pass
     const int32_t *chunk_desc;   // [n_chunks][8]: u0, nq, e0, ne, sb, ns, 0, 0
     int n_groups;
     int g0_normal;               // groups [0, g0_normal) are giant, the rest own exactly one chunk

@@ -270,6 +270,116 @@ class SparsePlan:
         return out
 
 
+def _many_args(cell_idx, region_code, w_effs, levels):
+    """ctypes arguments of wagg_plan_create_many (and the arrays behind them, which the caller keeps alive for the call)."""
+    ci = np.ascontiguousarray(cell_idx, dtype=np.int32)
+    rc = np.ascontiguousarray(region_code, dtype=np.int32)
+    ws = [np.ascontiguousarray(w, dtype=np.float64) for w in w_effs]
+    lcs = [np.ascontiguousarray(c, dtype=np.int32) for c, _ in levels]
+    if not (ci.ndim == 1 and ci.shape == rc.shape and all(a.shape == ci.shape for a in ws + lcs)):
+        raise ValueError("cell_idx, region_code, every weight column and every level column must be 1-D and of equal length")
+    f64p, i32p = C.POINTER(C.c_double), C.POINTER(C.c_int32)
+    wp = (f64p * max(1, len(ws)))(*[_np_ptr(w, C.c_double) for w in ws])
+    lp = (i32p * max(1, len(lcs)))(*[_np_ptr(c, C.c_int32) for c in lcs])
+    lr = (C.c_int32 * max(1, len(levels)))(*[int(r) for _, r in levels])
+    keep = (ci, rc, ws, lcs, wp, lp, lr)
+    return keep, (_np_ptr(ci, C.c_int32), _np_ptr(rc, C.c_int32), wp, len(ws), len(ci)), (lp, lr, len(levels))
+
+
+class ManyPlan:
+    """K weightings x (the fine level + nested coarse levels) of one coded segment table (``wagg_plan_create_many``).
+    ``w_effs``: K backup-filled weight columns (K <= 4); ``levels``: up to three ``(coarse_code, R_coarse)`` pairs, each
+    code column nesting in ``region_code`` (-1 = null).  One apply reads X once (one PCIe crossing for a host-resident
+    field) and returns views ``[level][weighting]`` into ONE result whose region axis concatenates every plane
+    (level-major, then weighting; level 0 is the fine one)."""
+
+    def __init__(self, cell_idx, region_code, w_effs, G, R, row_len=0, levels=(), flags=0, device=None):
+        require_gpu()
+        L = _lib.load()
+        levels = [(c, int(r)) for c, r in levels]
+        keep, head, tail = _many_args(cell_idx, region_code, w_effs, levels)
+        self._h = C.c_void_p()
+        self._lease = threading.Lock()       # held by whoever is applying a cached plan (_plans.py)
+        self.G, self.R = int(G), int(R)
+        with _on_device(device):
+            self.device = _current_device()
+            _lib.check(L.wagg_plan_create_many(*head, self.G, self.R, int(row_len), tail[0], tail[1], tail[2], int(flags),
+                                               C.byref(self._h)), "wagg_plan_create_many")
+        del keep
+        k, nl, oc = C.c_int(0), C.c_int(0), C.c_int64(0)
+        lr = (C.c_int32 * 4)()
+        _lib.check(L.wagg_plan_many_info(self._h, C.byref(k), C.byref(nl), lr, C.byref(oc)), "wagg_plan_many_info")
+        self.n_weights, self.n_levels, self.out_cols = k.value, nl.value, int(oc.value)
+        self.level_R = [self.R] + [int(lr[i]) for i in range(self.n_levels)]
+        self.offsets = []                    # offsets[l][k]: first column of plane (l, k)
+        off = 0
+        for Rl in self.level_R:
+            self.offsets.append([off + i * Rl for i in range(self.n_weights)])
+            off += self.n_weights * Rl
+        info = _lib.PlanInfo()
+        _lib.check(L.wagg_plan_get_info_sized(self._h, C.byref(info), C.sizeof(info)), "wagg_plan_get_info_sized")
+        self.info = {k: getattr(info, k) for k, _ in _lib.PlanInfo._fields_}   # the fine level's chunkings; R = out_cols
+        self.info["nnz"] *= self.n_weights                                       # (device bytes: one segment table per weighting)
+        self.den = []
+        for lv, Rl in enumerate(self.level_R):
+            row = []
+            for i in range(self.n_weights):
+                d = np.empty(Rl, dtype=np.float64)
+                _lib.check(L.wagg_plan_get_den_many(self._h, i, lv, _np_ptr(d, C.c_double)), "wagg_plan_get_den_many")
+                row.append(d)
+            self.den.append(row)
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value and _lib is not None and _lib._lib is not None:
+            _lib._lib.wagg_plan_destroy(self._h)
+            self._h = C.c_void_p()
+
+    __del__ = close
+
+    def status(self, stream=None):
+        """Synchronise the stream and raise if an apply on this plan failed on the device (``wagg_plan_status``)."""
+        _lib.check(_lib.load().wagg_plan_status(self._h, _stream_handle(stream)), "wagg_plan_status")
+
+    def split(self, full, out_layout="TR"):
+        """Views [level][weighting] of a concatenated result."""
+        if out_layout == "TR":
+            return [[full[:, o:o + Rl] for o in offs] for offs, Rl in zip(self.offsets, self.level_R)]
+        return [[full[o:o + Rl] for o in offs] for offs, Rl in zip(self.offsets, self.level_R)]
+
+    def apply(self, X, layout="TG", out_layout="TR", out=None, stream=None):
+        """Every plane from one pass over the device tensor X; asynchronous on torch's current stream (or `stream`).
+        ``out``: the concatenated (T, out_cols) / (out_cols, T) result to fill (else a new one)."""
+        import torch
+        X = _check_X(X, layout)
+        T = X.shape[0] if layout == "TG" else X.shape[1]
+        if (X.shape[1] if layout == "TG" else X.shape[0]) != self.G:
+            raise ValueError("X has the wrong number of grid cells (plan expects %d)" % self.G)
+        shape = (T, self.out_cols) if out_layout == "TR" else (self.out_cols, T)
+        if out is None:
+            out = torch.empty(shape, dtype=X.dtype, device=X.device)
+        elif tuple(out.shape) != shape or out.dtype != X.dtype or (shape[1] > 1 and out.stride(1) != 1):
+            raise ValueError("out must be a %s %s tensor with contiguous rows" % (shape, X.dtype))
+        _lib.run("wagg_apply (many)", plan_kind=_lib.PLAN_SEGMENT, plan=self._h, elem=_elem(X.dtype), source=_lib.SRC_DEVICE,
+                 x=X.data_ptr(), T=T, ldx=_ld(X), layout=_LAYOUTS[layout], out=out.data_ptr(), ldo=_ld(out),
+                 out_layout=_OUTS[out_layout], stream=_stream_handle(stream))
+        return self.split(out, out_layout)
+
+    def apply_host(self, X, flags=0, out=None, layout="TG", out_layout="TR"):
+        """Blocking host form: numpy in, views [level][weighting] of one numpy result out; the field crosses PCIe once
+        for all planes (``_lib.HOST_PIN | _lib.HOST_LINES`` as for :meth:`SparsePlan.apply_host`)."""
+        X = np.ascontiguousarray(X)
+        if X.dtype not in (np.float32, np.float64) or X.ndim != 2:
+            raise TypeError("X must be a 2-D float32/float64 array")
+        T = X.shape[0] if layout == "TG" else X.shape[1]
+        shape = (T, self.out_cols) if out_layout == "TR" else (self.out_cols, T)
+        out = _host_out(out, shape, X.dtype)
+        with _on_device(self.device):
+            _lib.run("wagg_apply (many, host)", plan_kind=_lib.PLAN_SEGMENT, plan=self._h, elem=_elem(X.dtype), source=_lib.SRC_HOST,
+                     x=X.ctypes.data, T=T, ldx=X.shape[1], layout=_LAYOUTS[layout], out=out.ctypes.data, ldo=max(1, shape[1]),
+                     out_layout=_OUTS[out_layout], flags=int(flags))
+        return self.split(out, out_layout)
+
+
 class DensePlan:
     """Dense-family plan: W as a (gridcell x region) matrix resident in HBM contracted on the matrix
     cores (full or tile-sparse form; fp32 or fp64 weights), or per-wave entry lists for scattered,

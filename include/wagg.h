@@ -82,7 +82,7 @@ typedef struct wagg_plan_info {
 
 /* ---- process / device ------------------------------------------------------------------- */
 int wagg_version(void);                 /* 10000*major + 100*minor + patch; 0.4.0: sized struct getters, wagg_apply_desc,
-                                           wagg_host_stats has 18 fields */
+                                           wagg_host_stats has 18 fields; 0.5.0: many-plans (wagg_plan_create_many) */
 int wagg_device_count(void);            /* number of visible HIP devices (0 if none), never <0  */
 /* Time-axis sharding rule of the multi-GPU form (one process per GPU; climate_toolbox_amd/timeshard.py):
  * rank `rank` of `world` owns rows [*start, *stop) of T; the first T mod world ranks hold one row more. */
@@ -622,6 +622,32 @@ typedef struct wagg_apply_desc {
     void *stream;
 } wagg_apply_desc;
 int wagg_apply(const wagg_apply_desc *desc);
+
+/* ---- many-plans: several weightings and nested levels of one table, one pass over X (0.5.0) ---------------------------
+ * wagg_plan_create_many builds ONE plan for n_weights weight columns of the same segment table (w_eff[k]: nseg values each,
+ * backup-filled as for wagg_plan_create) and n_levels coarse levels derived from the fine one (level_code[l]: nseg coarse
+ * codes in [0, level_R[l]), < 0 = null label).  Limits: 1 <= n_weights <= 4, 0 <= n_levels <= 3.
+ *   kept rows  a row is kept if any weighting keeps it; a weighting whose w_eff is NaN on a kept row gives it weight 0 (S6)
+ *   nesting    over the rows with some weight that is not NaN: the fine code is null iff the coarse one is, and every fine
+ *              code maps to exactly one coarse code -- else WAGG_EINVAL naming the first offending row.  Every check runs
+ *              before any device call.
+ *   den        level 0 (fine): per weighting, what wagg_plan_create of that column gives; coarse levels: fp64 sums in row
+ *              order, bit for bit wagg_plan_get_den of a wagg_plan_create over the coarse codes.
+ * The result of an apply concatenates every plane along the region axis, level-major, then weighting: plane (l, k) takes
+ * columns [off(l, k), off(l, k) + R_l) of a (time, region) result (rows of a (region, time) one), R_0 = R, off(l, k) =
+ * sum of n_weights * R_j over j < l, plus k * R_l.  wagg_plan_get_info's R is that width (out_cols), which ldo must reach.
+ * wagg_apply takes a many-plan as plan_kind WAGG_PLAN_SEGMENT with source WAGG_SRC_DEVICE or WAGG_SRC_HOST (one crossing of
+ * PCIe for all planes; WAGG_HOST_LINES as for a single plan) and transform WAGG_XF_NONE; anything else is WAGG_EUNSUPPORTED.
+ * (time, gridcell) data on a plan with a whole-line chunking for the element type reads X once for all weightings (fp32: up
+ * to four per pass, fp64: two) and derives the coarse levels from the fine partial sums; fine planes are bit for bit the
+ * results of single plans over the same kept rows.  Other layouts / plans run the single-plan kernels once per weighting, and
+ * derived levels there are WAGG_EUNSUPPORTED.                                                                                    */
+int wagg_plan_create_many(const int32_t *cell_idx, const int32_t *region_code, const double *const *w_eff, int n_weights,
+                          int64_t nseg, int64_t G, int32_t R, int64_t row_len, const int32_t *const *level_code,
+                          const int32_t *level_R, int n_levels, int flags, wagg_plan **out);
+/* n_weights = n_levels = 0 for a plan of wagg_plan_create; level_R: n_levels values (may be NULL); out_cols: result width */
+int wagg_plan_many_info(const wagg_plan *plan, int *n_weights, int *n_levels, int32_t *level_R, int64_t *out_cols);
+int wagg_plan_get_den_many(const wagg_plan *plan, int weighting, int level, double *den_host /* R_level values */);
 
 #ifdef __cplusplus
 }
