@@ -51,6 +51,8 @@ STRUCT_PLAN_INFO, STRUCT_DENSE_INFO, STRUCT_HOST_STATS, STRUCT_APPLY_DESC = 0, 1
 PLAN_SEGMENT, PLAN_DENSE = 0, 1
 SRC_DEVICE, SRC_HOST, SRC_HOST_MULTI, SRC_SHARDED = 0, 1, 2, 3
 XF_NONE, XF_POLY, XF_EDD = 0, 1, 2
+# wagg_apply_desc.flags with a dense-family plan: fp32 full form through the fp32 MFMA kernel instead of the split form
+APPLY_EXACT_F32 = 0x10000
 T_F32, T_F64 = 7, 8
 
 

@@ -25,6 +25,7 @@
 //   * fp32 partial slabs per (tile, k-slice), then one reduce kernel fuses the division by den[r]
 //     (deterministic, no atomics).
 #include <algorithm>
+#include <cfloat>
 #include <chrono>
 #include <cmath>
 #include <limits>
@@ -215,6 +216,8 @@ __global__ void dense_reduce_kernel(const T *__restrict__ slabs, int n_nt, int S
     }
     out[t * ldo + r] = s / den[r];
 }
+
+#include "wagg_dense_split.inc"
 
 // (slot, element) of a packed W tile -> (column inside the tile, k inside the tile)
 template <typename T> __device__ __forceinline__ void slot_to_ck(int slot, int &cl, int &k0) {
@@ -422,6 +425,19 @@ static int dense_finish_den(wagg_dense *d) {
     return dense_den_to_host(d);
 }
 
+// column maxima of a full-form fp32 plan (the split form's column scales), whichever builder made it; other plans have none
+static int dense_finish_scales(wagg_dense *d, hipStream_t st = nullptr) {
+    if (d->f64 || d->tiled || d->spmm) return WAGG_OK;
+    const int kt_per_block = 128;
+    const int n_strips = (d->n_kt + kt_per_block - 1) / kt_per_block;
+    WAGG_HIP(d->wmax.alloc((size_t)d->n_nt * D_BN));
+    WAGG_HIP(hipMemsetAsync(d->wmax.p, 0, sizeof(float) * d->wmax.n, st));
+    hipLaunchKernelGGL(dense_colmax_kernel, dim3((unsigned)d->n_nt, (unsigned)n_strips), dim3(512), 0, st,
+                       reinterpret_cast<const f32x4 *>(d->W.p), d->n_kt, kt_per_block, reinterpret_cast<unsigned *>(d->wmax.p));
+    WAGG_HIP(hipGetLastError());
+    return WAGG_OK;
+}
+
 // stored-tile lists of the tile-sparse form from the sorted keys nt * n_kt + kt
 static hipError_t dense_set_tiles(wagg_dense *d, const std::vector<int64_t> &tiles, std::vector<int32_t> *nt_out = nullptr,
                                   hipStream_t st = nullptr) {
@@ -513,10 +529,11 @@ constexpr double SPMM_MAX_FILL = 0.10;
 //                   stream that every one of the n_rb region blocks pulls through the LDS-DMA path (b G n_rb bytes per row)
 // Rates in flop/s and byte/s; fp32 / fp64.
 struct FormRates { double full, tiled, entries_scale, dma; };
-// fp32: full 204.3 ms for 2,282 rows x 8,100 x 96 tiles; tile-sparse (a workgroup walks an equal share of the stored tiles:
-// dense_pieces_kernel) 144 TF on the stored tiles' flops (c5-block: 8.39 ms), fp64 73 TF (16.58 ms); c5-uniform-f64 of
-// bench.py for the fp64 entry-list scale
-constexpr FormRates FORM_RATES_F32 = {142e12, 144e12, 1.0, 10.1e12};
+// fp32: full 204.3 ms for 2,282 rows x 8,100 x 96 tiles on the fp32 pipe (142 TF), since the split form (f16 pipe, row maxima
+// and split pack included) 2.99x that: c2-dense 42.6 against 127.3 ms a step on one box, A/B -> 420 TF; tile-sparse (a
+// workgroup walks an equal share of the stored tiles: dense_pieces_kernel) 144 TF on the stored tiles' flops (c5-block:
+// 8.39 ms), fp64 73 TF (16.58 ms); c5-uniform-f64 of bench.py for the fp64 entry-list scale
+constexpr FormRates FORM_RATES_F32 = {420e12, 144e12, 1.0, 10.1e12};
 constexpr FormRates FORM_RATES_F64 = {70e12, 73e12, 0.44, 10.1e12};
 // The entry loop slows down as the lists grow (the first 16 groups of a wave's list are preloaded across the previous chunk;
 // what follows is fetched inside the loop): flop/s on the WALKED entries against the mean list length per wave and chunk,
@@ -540,7 +557,11 @@ static FormCost table_form_cost(int64_t G, int elem_bytes, int64_t n_tiles_store
     FormCost c;
     // (full form with few column tiles: a launch has at most n_nt x 64 k-slices of workgroups per row block -- R = 600 fills
     //  192 of 256 CUs; the tile-sparse form hands every CU an equal share of the stored tiles whatever their layout)
-    const double util = n_nt * 64.0 < 256.0 ? n_nt * 64.0 / 256.0 : 1.0;
+    // (pick_ksplit keeps >= 32 k tiles per slice: a short K has fewer than 64 slices -- G = 700: 8 -- and at the split form's
+    //  rate that, not the MFMA pipe, is what a small full-form launch is paid by)
+    const int64_t n_kt = n_tiles_all / (n_nt > 0 ? n_nt : 1);
+    const double s_max = n_kt / 32 >= 64 ? 64.0 : (n_kt / 32 >= 16 ? (double)(n_kt / 32 / 8 * 8) : 8.0);
+    const double util = n_nt * s_max < 256.0 ? n_nt * s_max / 256.0 : 1.0;
     c.t_full = tile_flop * (double)n_tiles_all / (rt.full * util);
     c.t_tiled = tile_flop * (double)n_tiles_stored / rt.tiled;
     const double rate = rt.entries_scale * entry_loop_rate((double)walked / (double)(n_lists > 0 ? n_lists : 1));
@@ -584,6 +605,8 @@ static int create_synth(int64_t G, int32_t R, uint32_t seed, double fill, wagg_d
                        reinterpret_cast<vec_t *>(d->W.p), G, R, d->n_kt, d->w_slots(), seed, (float)fill);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) rc = dense_finish_den<T>(d); else { set_error("synth launch: %s", hipGetErrorString(e)); rc = WAGG_EHIP; }
+    if (rc == WAGG_OK) rc = dense_finish_scales(d);
+    if (rc == WAGG_OK && hipDeviceSynchronize() != hipSuccess) { set_error("synth: column maxima"); rc = WAGG_EHIP; }
     if (rc != WAGG_OK) { delete d; *out = nullptr; }
     return rc;
 }
@@ -649,6 +672,8 @@ static int create_host(const T *W_host, int64_t G, int32_t R, wagg_dense **out) 
     if (e == hipSuccess) e = hipDeviceSynchronize();
     if (e != hipSuccess) { set_error("dense upload: %s", hipGetErrorString(e)); delete d; *out = nullptr; return WAGG_EHIP; }
     rc = dense_finish_den<T>(d);
+    if (rc == WAGG_OK) rc = dense_finish_scales(d);
+    if (rc == WAGG_OK && hipDeviceSynchronize() != hipSuccess) { set_error("dense upload: column maxima"); rc = WAGG_EHIP; }
     if (rc != WAGG_OK) { delete d; *out = nullptr; }
     return rc;
 }
@@ -835,6 +860,7 @@ static int create_from_table(const int32_t *cell_idx, const int64_t *rowptr, con
     hipError_t e = hipMemcpyAsync(d->den64.p, se.den.p, sizeof(double) * (size_t)R, hipMemcpyDeviceToDevice, ctx.st);
     if (e != hipSuccess) { set_error("densify den: %s", hipGetErrorString(e)); return fail(WAGG_EHIP); }
     rc = dense_den_to_host(d, ctx.st);
+    if (rc == WAGG_OK) rc = dense_finish_scales(d, ctx.st);
     if (rc != WAGG_OK) return fail(rc);
     e = ctx.sync();                                   // the plan is complete before anyone applies it on another stream
     if (e != hipSuccess) { set_error("plan build: %s", hipGetErrorString(e)); return fail(WAGG_EHIP); }
@@ -891,9 +917,59 @@ static const void *pick_mfma_kernel(int MT, bool tiled, bool rm = false) {
 #undef WAGG_PICK
 }
 
+// split form (fp32 full-form plans, the default): MT from the same set as the fp32 kernel
+static const void *pick_split_kernel(int MT) {
+#define WAGG_PICK(M) case M: return (const void *)dense_split_kernel<M>
+    switch (MT) {
+        WAGG_PICK(1); WAGG_PICK(2); WAGG_PICK(3); WAGG_PICK(4); WAGG_PICK(5); WAGG_PICK(6); WAGG_PICK(8);
+        WAGG_PICK(10); WAGG_PICK(12); WAGG_PICK(14); WAGG_PICK(16); WAGG_PICK(18); WAGG_PICK(20);
+        WAGG_PICK(21); WAGG_PICK(22); WAGG_PICK(23);
+        default: return nullptr;
+    }
+#undef WAGG_PICK
+}
+
+// One launch group of the split form (rows already cut into n_mb row blocks of MT x 16): row maxima, split pack, the
+// f16-pipe contraction, the reduce that takes the scales off.  No pack-free pass: the split needs the packed copy.
+static int dense_apply_split(wagg_dense *d, const float *X_dev, int64_t Tn, int64_t ldx, const PackXfT<float> &xf,
+                             float *out_dev, int64_t ldo, int MT, int n_mb, int S, hipStream_t st) {
+    const int n_nt = d->n_nt, n_kt = d->n_kt, bm = MT * 16;
+    const int kt_per_slice = (n_kt + S - 1) / S;
+    const int64_t nblk = (int64_t)n_nt * n_mb * S;
+    WAGG_REQUIRE(nblk < (int64_t)0x7fffffff, "grid too large");
+    const void *kern = pick_split_kernel(MT);
+    if (!kern) { set_error("no split kernel for MT=%d", MT); return WAGG_EINVAL; }
+    const size_t need = (size_t)nblk * bm * D_BN;
+    if (d->slabs.n < need) WAGG_HIP(d->slabs.alloc(need));
+    const int64_t x_slots = (int64_t)n_mb * n_kt * bm * 8;
+    if (d->xp.n < (size_t)x_slots * 4) WAGG_HIP(d->xp.alloc((size_t)x_slots * 4));
+    if (d->xmax.n < (size_t)Tn) WAGG_HIP(d->xmax.alloc((size_t)Tn));
+    const int aligned = ((ldx * sizeof(float)) % 16 == 0) && ((reinterpret_cast<uintptr_t>(X_dev) & 15) == 0) &&
+                        (xf.mode != XF_EDD || (reinterpret_cast<uintptr_t>(xf.X2) & 15) == 0);
+    const size_t shmem = 2 * (size_t)d_buf_bytes(MT);
+    WAGG_HIP(allow_dynamic_lds(kern, shmem));
+    unsigned *xmax = reinterpret_cast<unsigned *>(d->xmax.p);
+    WAGG_HIP(hipMemsetAsync(xmax, 0, sizeof(unsigned) * (size_t)Tn, st));
+    const int64_t gx = (d->G + 4095) / 4096 < 64 ? (d->G + 4095) / 4096 : 64;
+    hipLaunchKernelGGL(dense_rowmax_kernel, dim3((unsigned)gx, (unsigned)Tn), dim3(256), 0, st, X_dev, ldx, d->G, xf, xmax);
+    hipLaunchKernelGGL(dense_pack_x_split_kernel, dim3(256 * 16), dim3(256), 0, st, X_dev, Tn, ldx, d->G, n_kt, bm, x_slots, aligned,
+                       (const unsigned *)xmax, reinterpret_cast<f16x8 *>(d->xp.p), xf, d->inf_dev);
+    WAGG_HIP(hipGetLastError());
+    const f16x8 *xp = reinterpret_cast<const f16x8 *>(d->xp.p);
+    const float *wp = d->W.p, *wmax = d->wmax.p;
+    float *slabs = d->slabs.p;
+    int n_kt_a = n_kt, n_nt_a = n_nt, n_mb_a = n_mb, S_a = S, kps = kt_per_slice;
+    void *args[] = {&xp, &wp, &wmax, &n_kt_a, &n_nt_a, &n_mb_a, &S_a, &kps, &slabs};
+    WAGG_HIP(launch_timed_ptr(true, kern, dim3((unsigned)nblk), dim3(D_THREADS), args, shmem, st));
+    hipLaunchKernelGGL(dense_reduce_split_kernel, dim3((unsigned)((d->R + 255) / 256), (unsigned)Tn), dim3(256), 0, st,
+                       (const float *)slabs, n_nt, S, bm, d->R, (const float *)d->den32.p, (const unsigned *)xmax, wmax, out_dev, ldo);
+    WAGG_HIP(hipGetLastError());
+    return WAGG_OK;
+}
+
 template <typename T>
 static int dense_apply(wagg_dense *d, const T *X_dev, int64_t Tn, int64_t ldx, const PackXfT<T> &xf,
-                       T *out_dev, int64_t ldo, int ksplit, void *stream) {
+                       T *out_dev, int64_t ldo, int ksplit, void *stream, bool exact = false) {
     typedef typename DT<T>::vec vec_t;
     WAGG_REQUIRE(d != nullptr, "dense plan is NULL");
     WAGG_REQUIRE(d->f64 == (sizeof(T) == 8), "this plan holds %s weights: use the matching wagg_dense_apply_*",
@@ -914,7 +990,7 @@ static int dense_apply(wagg_dense *d, const T *X_dev, int64_t Tn, int64_t ldx, c
             PackXfT<T> xg = xf;
             if (xg.X2) xg.X2 += t0 * ldx;
             const int64_t rows = Tn - t0 < ROWS_MAX ? Tn - t0 : ROWS_MAX;
-            if (int rc = dense_apply<T>(d, X_dev + t0 * ldx, rows, ldx, xg, out_dev + t0 * ldo, ldo, ksplit, stream)) return rc;
+            if (int rc = dense_apply<T>(d, X_dev + t0 * ldx, rows, ldx, xg, out_dev + t0 * ldo, ldo, ksplit, stream, exact)) return rc;
         }
         return WAGG_OK;
     }
@@ -943,12 +1019,16 @@ static int dense_apply(wagg_dense *d, const T *X_dev, int64_t Tn, int64_t ldx, c
             if (MT_tail >= 4 && MT - MT_tail >= 2) {
                 PackXfT<T> xt = xf;
                 if (xt.X2) xt.X2 += head * ldx;
-                if (int rc = dense_apply<T>(d, X_dev, head, ldx, xf, out_dev, ldo, ksplit, stream)) return rc;
-                return dense_apply<T>(d, X_dev + head * ldx, tail, ldx, xt, out_dev + head * ldo, ldo, ksplit, stream);
+                if (int rc = dense_apply<T>(d, X_dev, head, ldx, xf, out_dev, ldo, ksplit, stream, exact)) return rc;
+                return dense_apply<T>(d, X_dev + head * ldx, tail, ldx, xt, out_dev + head * ldo, ldo, ksplit, stream, exact);
             }
         }
     }
     int S = ksplit ? ksplit : pick_ksplit((int64_t)n_nt * n_mb, n_kt);
+    // fp32 full form: the split form unless the caller asked for the exact kernel (WAGG_APPLY_EXACT_F32)
+    if constexpr (sizeof(T) == 4) {
+        if (!d->tiled && !exact && d->wmax.p != nullptr) return dense_apply_split(d, X_dev, Tn, ldx, xf, out_dev, ldo, MT, n_mb, S, (hipStream_t)stream);
+    }
     // tile-sparse form: no k-slices -- the launch walks PIECES, an equal share of all stored tiles per workgroup (see the kernel)
     const wagg_dense::TilePieces *tp = nullptr;
     if (d->tiled) {
@@ -1047,19 +1127,19 @@ static int dense_apply(wagg_dense *d, const T *X_dev, int64_t Tn, int64_t ldx, c
 
 template <typename T>
 static int apply_poly(wagg_dense *d, const T *X_dev, int64_t Tn, int64_t ldx, double offset, int power, T *out_dev,
-                      int64_t ldo, int ksplit, void *stream) {
+                      int64_t ldo, int ksplit, void *stream, bool exact = false) {
     WAGG_REQUIRE(power >= 1 && power <= 16, "power must lie in [1, 16], got %d", power);
     PackXfT<T> xf;
     xf.mode = power; xf.off = (T)offset;
-    return dense_apply<T>(d, X_dev, Tn, ldx, xf, out_dev, ldo, ksplit, stream);
+    return dense_apply<T>(d, X_dev, Tn, ldx, xf, out_dev, ldo, ksplit, stream, exact);
 }
 
 template <typename T>
 static int apply_edd(wagg_dense *d, const T *tasmin, const T *tasmax, int64_t Tn, int64_t ldx, double offset,
-                     double threshold, T *out_dev, int64_t ldo, int ksplit, void *stream) {
+                     double threshold, T *out_dev, int64_t ldo, int ksplit, void *stream, bool exact = false) {
     PackXfT<T> xf;
     xf.mode = XF_EDD; xf.off = (T)offset; xf.thr = (T)threshold; xf.X2 = tasmax;
-    return dense_apply<T>(d, tasmin, Tn, ldx, xf, out_dev, ldo, ksplit, stream);
+    return dense_apply<T>(d, tasmin, Tn, ldx, xf, out_dev, ldo, ksplit, stream, exact);
 }
 
 }  // namespace wagg
@@ -1175,6 +1255,7 @@ extern "C" int wagg_dense_clone(const wagg_dense *src, int device, wagg_dense **
         if (e == hipSuccess) e = clone_buf(d->W, device, src->W, src->device);
         if (e == hipSuccess) e = clone_buf(d->den32, device, src->den32, src->device);
         if (e == hipSuccess) e = clone_buf(d->den64, device, src->den64, src->device);
+        if (e == hipSuccess) e = clone_buf(d->wmax, device, src->wmax, src->device);
         if (e == hipSuccess) e = clone_buf(d->tile_kt, device, src->tile_kt, src->device);
         if (e == hipSuccess) e = clone_buf(d->sp.ent, device, src->sp.ent, src->device);
         if (e == hipSuccess) e = clone_buf(d->sp.grp_off, device, src->sp.grp_off, src->device);
@@ -1209,16 +1290,16 @@ extern "C" int wagg_dense_get_den(const wagg_dense *d, double *den_host) {
 }
 
 int wagg::entry::dense_apply_f32(wagg_dense *d, const float *X_dev, int64_t T, int64_t ldx,
-                                    float *out_dev, int64_t ldo, int ksplit, void *stream) {
-    return wagg::dense_apply<float>(d, X_dev, T, ldx, wagg::PackXfT<float>{}, out_dev, ldo, ksplit, stream);
+                                    float *out_dev, int64_t ldo, int ksplit, void *stream, bool exact) {
+    return wagg::dense_apply<float>(d, X_dev, T, ldx, wagg::PackXfT<float>{}, out_dev, ldo, ksplit, stream, exact);
 }
 int wagg::entry::dense_apply_f64(wagg_dense *d, const double *X_dev, int64_t T, int64_t ldx,
                                     double *out_dev, int64_t ldo, int ksplit, void *stream) {
     return wagg::dense_apply<double>(d, X_dev, T, ldx, wagg::PackXfT<double>{}, out_dev, ldo, ksplit, stream);
 }
 int wagg::entry::dense_apply_poly_f32(wagg_dense *d, const float *X_dev, int64_t T, int64_t ldx, double offset,
-                                         int power, float *out_dev, int64_t ldo, int ksplit, void *stream) {
-    return wagg::apply_poly<float>(d, X_dev, T, ldx, offset, power, out_dev, ldo, ksplit, stream);
+                                         int power, float *out_dev, int64_t ldo, int ksplit, void *stream, bool exact) {
+    return wagg::apply_poly<float>(d, X_dev, T, ldx, offset, power, out_dev, ldo, ksplit, stream, exact);
 }
 int wagg::entry::dense_apply_poly_f64(wagg_dense *d, const double *X_dev, int64_t T, int64_t ldx, double offset,
                                          int power, double *out_dev, int64_t ldo, int ksplit, void *stream) {
@@ -1226,8 +1307,8 @@ int wagg::entry::dense_apply_poly_f64(wagg_dense *d, const double *X_dev, int64_
 }
 int wagg::entry::dense_apply_edd_f32(wagg_dense *d, const float *tasmin_dev, const float *tasmax_dev, int64_t T,
                                         int64_t ldx, double offset, double threshold, float *out_dev, int64_t ldo,
-                                        int ksplit, void *stream) {
-    return wagg::apply_edd<float>(d, tasmin_dev, tasmax_dev, T, ldx, offset, threshold, out_dev, ldo, ksplit, stream);
+                                        int ksplit, void *stream, bool exact) {
+    return wagg::apply_edd<float>(d, tasmin_dev, tasmax_dev, T, ldx, offset, threshold, out_dev, ldo, ksplit, stream, exact);
 }
 int wagg::entry::dense_apply_edd_f64(wagg_dense *d, const double *tasmin_dev, const double *tasmax_dev, int64_t T,
                                         int64_t ldx, double offset, double threshold, double *out_dev, int64_t ldo,
@@ -1244,7 +1325,8 @@ static int check_dense_device(const wagg_dense *d) {
 }
 
 template <typename T>
-static int dense_apply_host(wagg_dense *d, const T *X_host, int64_t Tn, int64_t ldx, T *out_host, int64_t ldo, int flags) {
+static int dense_apply_host(wagg_dense *d, const T *X_host, int64_t Tn, int64_t ldx, T *out_host, int64_t ldo, int flags,
+                            bool exact = false) {
     clear_error();
     WAGG_REQUIRE(d != nullptr, "dense plan is NULL");
     WAGG_REQUIRE(Tn >= 0, "T < 0");
@@ -1259,14 +1341,14 @@ static int dense_apply_host(wagg_dense *d, const T *X_host, int64_t Tn, int64_t 
         WAGG_HIP(dout.alloc((size_t)(Tn * ldo)));
         const bool pin = (flags & WAGG_HOST_PIN) != 0;
         if (int rc = copy_to_device(dx.p, X_host, sizeof(T) * (size_t)((Tn - 1) * ldx + d->G), pin)) return rc;
-        const int rc = dense_apply<T>(d, dx.p, Tn, ldx, PackXfT<T>{}, dout.p, ldo, 0, nullptr);
+        const int rc = dense_apply<T>(d, dx.p, Tn, ldx, PackXfT<T>{}, dout.p, ldo, 0, nullptr, exact);
         if (rc != WAGG_OK) return rc;
         WAGG_HIP(hipDeviceSynchronize());
         return copy_rows_to_host(out_host, dout.p, Tn, sizeof(T) * (size_t)ldo, sizeof(T) * (size_t)d->R, pin);
     }
     return stream_host_rows<T>(X_host, Tn, ldx, d->G, out_host, ldo, d->R, flags, d->spmm ? SpT<T>::TB : DT<T>::MT_MAX * 16, 1, nullptr,
                                [&](int, const T *xd, int64_t rows, T *od, hipStream_t st) {
-                                   return dense_apply<T>(d, xd, rows, ldx, PackXfT<T>{}, od, ldo, 0, (void *)st);
+                                   return dense_apply<T>(d, xd, rows, ldx, PackXfT<T>{}, od, ldo, 0, (void *)st, exact);
                                },
                                [](int, hipStream_t) {});
 }
@@ -1307,8 +1389,8 @@ static int dense_apply_host_multi(wagg_dense *const *plans, const int *devices, 
 }  // namespace wagg
 
 int wagg::entry::dense_apply_host_f32(wagg_dense *d, const float *X_host, int64_t T, int64_t ldx,
-                                         float *out_host, int64_t ldo, int flags) {
-    return wagg::dense_apply_host<float>(d, X_host, T, ldx, out_host, ldo, flags);
+                                         float *out_host, int64_t ldo, int flags, bool exact) {
+    return wagg::dense_apply_host<float>(d, X_host, T, ldx, out_host, ldo, flags, exact);
 }
 int wagg::entry::dense_apply_host_f64(wagg_dense *d, const double *X_host, int64_t T, int64_t ldx,
                                          double *out_host, int64_t ldo, int flags) {

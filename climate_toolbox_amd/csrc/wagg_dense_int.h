@@ -74,6 +74,9 @@ struct wagg_dense {
     bool f64 = false;                  // element type of W / X / slabs: fp32 (default) or fp64 (the *_f64 constructors)
     wagg::DevBuf<float> W, den32, slabs, xp;     // W and xp in packed tile order (sized in 4-byte units for both types)
     wagg::DevBuf<double> den64;
+    // full-form fp32 plans: max |w| of every column (n_nt * 256, zero-padded), from which the split form takes its
+    // power-of-two column scales (wagg_dense_split.inc); xmax: the row maxima of the apply in flight (workspace)
+    wagg::DevBuf<float> wmax, xmax;
     std::vector<double> den_host;
     // tile-sparse form: only the non-empty (32-cell x 256-region) tiles of W are stored, grouped by
     // column tile; tile_kt[i] = k tile of stored tile i (+2 padding entries)

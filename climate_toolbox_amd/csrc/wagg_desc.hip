@@ -115,24 +115,29 @@ int run_dense(const wagg_apply_desc &d) {
     const T *x = static_cast<const T *>(d.x), *x2 = static_cast<const T *>(d.x2);
     T *out = static_cast<T *>(d.out);
     wagg_dense *plan = static_cast<wagg_dense *>(const_cast<void *>(d.plan));
+    // WAGG_APPLY_EXACT_F32: fp32 full-form plans run the fp32-pipe kernel instead of the split form (no effect elsewhere)
+    const bool exact = (d.flags & WAGG_APPLY_EXACT_F32) != 0;
+    if (exact && (d.source == WAGG_SRC_HOST_MULTI || d.source == WAGG_SRC_SHARDED))
+        return unsupported(d, "WAGG_APPLY_EXACT_F32 is taken by the device and host sources only");
+    const int host_flags = d.flags & ~WAGG_APPLY_EXACT_F32;
     switch (d.source) {
         case WAGG_SRC_DEVICE:
             if (d.transform == WAGG_XF_NONE) {
-                if constexpr (f32) return entry::dense_apply_f32(plan, x, d.T, d.ldx, out, d.ldo, d.ksplit, d.stream);
+                if constexpr (f32) return entry::dense_apply_f32(plan, x, d.T, d.ldx, out, d.ldo, d.ksplit, d.stream, exact);
                 else return entry::dense_apply_f64(plan, x, d.T, d.ldx, out, d.ldo, d.ksplit, d.stream);
             }
             if (d.transform == WAGG_XF_POLY) {
                 if (d.n_pow != 1) return unsupported(d, "one power per call (n_pow == 1, the power in pow_first)");
-                if constexpr (f32) return entry::dense_apply_poly_f32(plan, x, d.T, d.ldx, d.offset, d.pow_first, out, d.ldo, d.ksplit, d.stream);
+                if constexpr (f32) return entry::dense_apply_poly_f32(plan, x, d.T, d.ldx, d.offset, d.pow_first, out, d.ldo, d.ksplit, d.stream, exact);
                 else return entry::dense_apply_poly_f64(plan, x, d.T, d.ldx, d.offset, d.pow_first, out, d.ldo, d.ksplit, d.stream);
             }
             if (d.n_thr != 1 || d.thresholds == nullptr) return unsupported(d, "one threshold per call (n_thr == 1)");
-            if constexpr (f32) return entry::dense_apply_edd_f32(plan, x, x2, d.T, d.ldx, d.offset, d.thresholds[0], out, d.ldo, d.ksplit, d.stream);
+            if constexpr (f32) return entry::dense_apply_edd_f32(plan, x, x2, d.T, d.ldx, d.offset, d.thresholds[0], out, d.ldo, d.ksplit, d.stream, exact);
             else return entry::dense_apply_edd_f64(plan, x, x2, d.T, d.ldx, d.offset, d.thresholds[0], out, d.ldo, d.ksplit, d.stream);
         case WAGG_SRC_HOST:
             if (d.transform != WAGG_XF_NONE) return unsupported(d, "host-resident fields through a dense-family plan have no fused transforms");
-            if constexpr (f32) return entry::dense_apply_host_f32(plan, x, d.T, d.ldx, out, d.ldo, d.flags);
-            else return entry::dense_apply_host_f64(plan, x, d.T, d.ldx, out, d.ldo, d.flags);
+            if constexpr (f32) return entry::dense_apply_host_f32(plan, x, d.T, d.ldx, out, d.ldo, host_flags, exact);
+            else return entry::dense_apply_host_f64(plan, x, d.T, d.ldx, out, d.ldo, host_flags);
         case WAGG_SRC_HOST_MULTI: {
             if (d.transform != WAGG_XF_NONE) return unsupported(d, "the multi-device host pipeline has no fused transforms");
             wagg_dense *const *plans = static_cast<wagg_dense *const *>(d.plan);

@@ -25,13 +25,14 @@ int apply_edd_host_f32(const wagg_plan *plan, const float *tasmin_host, const fl
 int apply_edd_host_f64(const wagg_plan *plan, const double *tasmin_host, const double *tasmax_host, int64_t T, int64_t ldx, double offset, const double *thresholds, int n_thr, double *out_host, int64_t ldo, int64_t out_pstride, int flags);
 int apply_sharded_f32(wagg_shard_group *g, const wagg_plan *const *plans, const float *const *X_dev, const int64_t *rows, int64_t ldx, float *out_root, int64_t ldo, int root);
 int apply_sharded_f64(wagg_shard_group *g, const wagg_plan *const *plans, const double *const *X_dev, const int64_t *rows, int64_t ldx, double *out_root, int64_t ldo, int root);
-int dense_apply_f32(wagg_dense *d, const float *X_dev, int64_t T, int64_t ldx, float *out_dev, int64_t ldo, int ksplit, void *stream);
+// (fp32 dense applies: exact = WAGG_APPLY_EXACT_F32, today's fp32-pipe kernel instead of the split form)
+int dense_apply_f32(wagg_dense *d, const float *X_dev, int64_t T, int64_t ldx, float *out_dev, int64_t ldo, int ksplit, void *stream, bool exact = false);
 int dense_apply_f64(wagg_dense *d, const double *X_dev, int64_t T, int64_t ldx, double *out_dev, int64_t ldo, int ksplit, void *stream);
-int dense_apply_poly_f32(wagg_dense *d, const float *X_dev, int64_t T, int64_t ldx, double offset, int power, float *out_dev, int64_t ldo, int ksplit, void *stream);
+int dense_apply_poly_f32(wagg_dense *d, const float *X_dev, int64_t T, int64_t ldx, double offset, int power, float *out_dev, int64_t ldo, int ksplit, void *stream, bool exact = false);
 int dense_apply_poly_f64(wagg_dense *d, const double *X_dev, int64_t T, int64_t ldx, double offset, int power, double *out_dev, int64_t ldo, int ksplit, void *stream);
-int dense_apply_edd_f32(wagg_dense *d, const float *tasmin_dev, const float *tasmax_dev, int64_t T, int64_t ldx, double offset, double threshold, float *out_dev, int64_t ldo, int ksplit, void *stream);
+int dense_apply_edd_f32(wagg_dense *d, const float *tasmin_dev, const float *tasmax_dev, int64_t T, int64_t ldx, double offset, double threshold, float *out_dev, int64_t ldo, int ksplit, void *stream, bool exact = false);
 int dense_apply_edd_f64(wagg_dense *d, const double *tasmin_dev, const double *tasmax_dev, int64_t T, int64_t ldx, double offset, double threshold, double *out_dev, int64_t ldo, int ksplit, void *stream);
-int dense_apply_host_f32(wagg_dense *d, const float *X_host, int64_t T, int64_t ldx, float *out_host, int64_t ldo, int flags);
+int dense_apply_host_f32(wagg_dense *d, const float *X_host, int64_t T, int64_t ldx, float *out_host, int64_t ldo, int flags, bool exact = false);
 int dense_apply_host_f64(wagg_dense *d, const double *X_host, int64_t T, int64_t ldx, double *out_host, int64_t ldo, int flags);
 int dense_apply_host_multi_f32(wagg_dense *const *plans, const int *devices, int n_devices, const float *X_host, int64_t T, int64_t ldx, float *out_host, int64_t ldo, int flags);
 int dense_apply_host_multi_f64(wagg_dense *const *plans, const int *devices, int n_devices, const double *X_host, int64_t T, int64_t ldx, double *out_host, int64_t ldo, int flags);

@@ -380,6 +380,10 @@ class ManyPlan:
         return self.split(out, out_layout)
 
 
+def _exact_flag(exact):
+    return _lib.APPLY_EXACT_F32 if exact else 0
+
+
 class DensePlan:
     """Dense-family plan: W as a (gridcell x region) matrix resident in HBM contracted on the matrix
     cores (full or tile-sparse form; fp32 or fp64 weights), or per-wave entry lists for scattered,
@@ -531,22 +535,24 @@ class DensePlan:
     def _run(self, what, **fields):
         _lib.run(what, plan_kind=_lib.PLAN_DENSE, elem=_elem(self.dtype), **fields)
 
-    def apply(self, X, out=None, ksplit=0, stream=None):
+    def apply(self, X, out=None, ksplit=0, stream=None, exact=False):
+        """``exact=True``: an fp32 full-form plan runs the fp32 MFMA kernel instead of the default split form
+        (``WAGG_APPLY_EXACT_F32``; the same for apply_poly / apply_edd / apply_host)."""
         X, T, out = self._prep(X, out)
         self._run("wagg_apply (dense)", plan=self._h, source=_lib.SRC_DEVICE, x=X.data_ptr(), T=T, ldx=_ld(X), out=out.data_ptr(),
-                  ldo=_ld(out), ksplit=int(ksplit), stream=_stream_handle(stream))
+                  ldo=_ld(out), ksplit=int(ksplit), stream=_stream_handle(stream), flags=_exact_flag(exact))
         return out
 
-    def apply_poly(self, X, offset, power, out=None, ksplit=0, stream=None):
+    def apply_poly(self, X, offset, power, out=None, ksplit=0, stream=None, exact=False):
         """Aggregate of (X + offset) ** power (``wagg_dense_apply_poly_*``): the transform of
         tas_poly (transformations.py:188) is evaluated while X is packed."""
         X, T, out = self._prep(X, out)
         self._run("wagg_apply (dense, poly)", plan=self._h, source=_lib.SRC_DEVICE, transform=_lib.XF_POLY, offset=float(offset),
                   pow_first=int(power), n_pow=1, x=X.data_ptr(), T=T, ldx=_ld(X), out=out.data_ptr(), ldo=_ld(out), ksplit=int(ksplit),
-                  stream=_stream_handle(stream))
+                  stream=_stream_handle(stream), flags=_exact_flag(exact))
         return out
 
-    def apply_edd(self, tasmin, tasmax, threshold, offset=0.0, out=None, ksplit=0, stream=None):
+    def apply_edd(self, tasmin, tasmax, threshold, offset=0.0, out=None, ksplit=0, stream=None, exact=False):
         """Aggregate of snyder_edd(tasmin + offset, tasmax + offset, threshold)
         (``wagg_dense_apply_edd_*``; transformations.py:64-87 evaluated while the fields are packed)."""
         tasmin, T, out = self._prep(tasmin, out)
@@ -556,10 +562,10 @@ class DensePlan:
         thr = (C.c_double * 1)(float(threshold))
         self._run("wagg_apply (dense, edd)", plan=self._h, source=_lib.SRC_DEVICE, transform=_lib.XF_EDD, offset=float(offset),
                   thresholds=thr, n_thr=1, x=tasmin.data_ptr(), x2=tasmax.data_ptr(), T=T, ldx=_ld(tasmin), out=out.data_ptr(),
-                  ldo=_ld(out), ksplit=int(ksplit), stream=_stream_handle(stream))
+                  ldo=_ld(out), ksplit=int(ksplit), stream=_stream_handle(stream), flags=_exact_flag(exact))
         return out
 
-    def apply_host(self, X, flags=0, replicas=(), out=None):
+    def apply_host(self, X, flags=0, replicas=(), out=None, exact=False):
         """Host-resident (time, gridcell) array through the plan in row blocks (``wagg_dense_apply_host_*``):
         numpy in, numpy out; flags and ``replicas`` as for :meth:`SparsePlan.apply_host` (``_lib.HOST_LINES`` means nothing
         to a dense-family plan -- every cell of a row is an operand -- and is dropped)."""
@@ -578,7 +584,7 @@ class DensePlan:
             return out
         with _on_device(self.device):
             self._run("wagg_apply (dense, host)", plan=self._h, source=_lib.SRC_HOST, x=X.ctypes.data, T=X.shape[0], ldx=X.shape[1],
-                      out=out.ctypes.data, ldo=max(1, self.R), flags=int(flags))
+                      out=out.ctypes.data, ldo=max(1, self.R), flags=int(flags) | _exact_flag(exact))
         return out
 
     def saw_inf(self, stream=None):

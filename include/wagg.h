@@ -591,6 +591,10 @@ int wagg_dense_apply_sharded_f64(wagg_shard_group *g, wagg_dense *const *plans, 
  *                per call.)
  *   T, ldx, layout / out, ldo, out_layout   as in wagg_apply_f32 (dense-family plans: WAGG_LAYOUT_TG / WAGG_OUT_TR only)
  *   ksplit       dense-family plans: k-slice count, 0 = the library's choice
+ *   flags        WAGG_HOST_* for the host sources; with a dense-family plan also WAGG_APPLY_EXACT_F32 (sources DEVICE and
+ *                HOST): an fp32 full-form plan then runs the fp32 MFMA kernel, bit for bit what library 0.5.0 computed,
+ *                instead of the default split form (f16 high + low parts of both operands, power-of-two scaled, fp32
+ *                accumulation: DESIGN.md gives the error bound).  No effect on other forms or on fp64 plans.
  * A combination the library has no kernel path for returns WAGG_EUNSUPPORTED with a message that names it; nothing is
  * emulated.                                                                                                            */
 #define WAGG_PLAN_SEGMENT 0
@@ -602,6 +606,7 @@ int wagg_dense_apply_sharded_f64(wagg_shard_group *g, wagg_dense *const *plans, 
 #define WAGG_XF_NONE 0
 #define WAGG_XF_POLY 1
 #define WAGG_XF_EDD 2
+#define WAGG_APPLY_EXACT_F32 0x10000
 typedef struct wagg_apply_desc {
     uint64_t struct_size;
     int32_t plan_kind, elem, source, transform;
