@@ -530,7 +530,8 @@ constexpr double SPMM_MAX_FILL = 0.10;
 // Rates in flop/s and byte/s; fp32 / fp64.
 struct FormRates { double full, tiled, entries_scale, dma; };
 // fp32: full 204.3 ms for 2,282 rows x 8,100 x 96 tiles on the fp32 pipe (142 TF), since the split form (f16 pipe, row maxima
-// and split pack included) 2.99x that: c2-dense 42.6 against 127.3 ms a step on one box, A/B -> 420 TF; tile-sparse (a
+// and split pack included) 2.99x that: c2-dense 42.6 against 127.3 ms a step on one box, A/B -> 420 TF (re-derived for the
+// W-in-registers pipeline from the form guard's forced full-form times, 4.07-4.28 ms = 424-446 TF: kept); tile-sparse (a
 // workgroup walks an equal share of the stored tiles: dense_pieces_kernel) 144 TF on the stored tiles' flops (c5-block:
 // 8.39 ms), fp64 73 TF (16.58 ms); c5-uniform-f64 of bench.py for the fp64 entry-list scale
 constexpr FormRates FORM_RATES_F32 = {420e12, 144e12, 1.0, 10.1e12};
@@ -946,7 +947,17 @@ static int dense_apply_split(wagg_dense *d, const float *X_dev, int64_t Tn, int6
     if (d->xmax.n < (size_t)Tn) WAGG_HIP(d->xmax.alloc((size_t)Tn));
     const int aligned = ((ldx * sizeof(float)) % 16 == 0) && ((reinterpret_cast<uintptr_t>(X_dev) & 15) == 0) &&
                         (xf.mode != XF_EDD || (reinterpret_cast<uintptr_t>(xf.X2) & 15) == 0);
-    const size_t shmem = 2 * (size_t)d_buf_bytes(MT);
+#ifdef WAGG_DIAG      // ablation variants (timing only; results are wrong with any bit set): tools/split_ablate.sh
+    if (const char *dbg = MT == D_MT ? getenv("WAGG_SPLIT_DBG") : nullptr) {
+        switch (atoi(dbg)) {
+            case 1: kern = (const void *)dense_split_kernel<D_MT, 1>; break;
+            case 4: kern = (const void *)dense_split_kernel<D_MT, 4>; break;
+            case 5: kern = (const void *)dense_split_kernel<D_MT, 5>; break;
+            default: break;
+        }
+    }
+#endif
+    const size_t shmem = 3 * (size_t)d_xt_bytes(MT);          // the split kernel's ring of three X tiles (W: registers)
     WAGG_HIP(allow_dynamic_lds(kern, shmem));
     unsigned *xmax = reinterpret_cast<unsigned *>(d->xmax.p);
     WAGG_HIP(hipMemsetAsync(xmax, 0, sizeof(unsigned) * (size_t)Tn, st));

@@ -1,6 +1,7 @@
-// Split form of the full-form fp32 contraction (included by wagg_dense.hip): the same work items, LDS image, DMA pieces,
-// swizzle, double buffer and fragment offsets as dense_mfma_kernel<float, 0, false, MT>, but the products run on the f16
-// matrix pipe.  Each operand is an f16 high part plus an f16 low part of a power-of-two scaled copy:
+// Split form of the full-form fp32 contraction (included by wagg_dense.hip): the same work items, packed tile images,
+// swizzle and fragment offsets as dense_mfma_kernel<float, 0, false, MT>, but the products run on the f16 matrix pipe
+// (and the pipeline is its own, see dense_split_kernel).  Each operand is an f16 high part plus an f16 low part of a
+// power-of-two scaled copy:
 //   X row t:     x 2^ex[t] = xh + xl   (dense_pack_x_split_kernel; ex[t] puts the row's largest |x| in [2^14, 2^15))
 //   W column r:  w 2^ew[r] = wh + wl   (here, in registers, from the fp32 W tile; ew[r] from the plan's column maxima)
 // and a 16 x 16 x 32 block is xh.wl + xl.wh + xh.wh: three v_mfma_f32_16x16x32_f16 (16 cycles each) against eight
@@ -32,20 +33,49 @@ __device__ __forceinline__ void split_w8(f32x4 a, f32x4 b, int e, f16x8 &hi, f16
     }
 }
 
-template <int MT>
+// Pipeline (the fp32 kernel's double buffer left the f16 tile -- 3 x 16 cycles a row-block column -- about half a tile for
+// its DMA to land, a vmcnt(0) drain and a barrier every tile):
+//   * W goes straight to registers: lane (lr, kq) of wave w needs exactly the four 16-byte pieces b00 b01 b10 b11 of rows
+//     32 w + lr (+ 16) of the packed W tile, so it loads them with buffer_load_dwordx4 (the packed layout is the LDS image:
+//     the same offsets).  The loads of tile t + 1 are issued right after tile t's pieces have been split, into the same
+//     registers, and have a whole tile to land.
+//   * LDS holds X tiles only, in a ring of three: the DMA pieces of tile t + 2 are issued inside tile t, into the buffer
+//     that tile t - 1 read (every wave passed the barrier behind it).  At the end of tile t a wave waits for its pieces of
+//     tile t + 1 only -- vmcnt(4 + NXP) leaves the W loads of t + 1 and the pieces of t + 2 in flight (vector-memory loads,
+//     LDS-DMA included, retire in issue order) -- and the workgroup takes its one barrier.
+//   * Every wave issues the same number of vector-memory ops on every path (a wave without an i-th X piece fetches piece
+//     (wave + 8 i) mod XPIECES again: the same bytes to the same place, never read before the barrier), so the compiler's
+//     own wait before the split counts exactly: vmcnt(NXP), the pieces of t + 2 stay in flight.
+//   * The split of column block 1's W operands runs between the first six MFMAs (row blocks 0 and 1, column block 0).
+// Per accumulator the three MFMAs keep their order (xh.wl, xl.wh, xh.wh) and k order: the result is the double-buffered
+// kernel's, bit for bit.
+//
+// DBG is a diagnostic knob (WAGG_SPLIT_DBG env, read by the -DWAGG_DIAG build only; tools/split_ablate.sh): bit0 = no W loads
+// and no X DMA in the k-loop, bit2 = no per-tile wait or barrier.  Results are wrong with either bit set.
+
+// buffer descriptor of `bytes` bytes at a wave-uniform address (read back from lane 0, so that the compiler keeps the
+// descriptor in SGPRs instead of looping over the lanes' copies)
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t split_tile_rsrc(const char *base, int bytes) {
+    const uint64_t a = reinterpret_cast<uint64_t>(base);
+    // (readfirstlane returns int: each half goes through uint32_t, or bit 31 of the low half would spread into the high one)
+    const uint64_t u = (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((unsigned)a) |
+                       (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((unsigned)(a >> 32)) << 32;
+    return __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void *>(u), (short)0, bytes, 0x00020000);
+}
+
+template <int MT, int DBG = 0>
 __global__ __launch_bounds__(D_THREADS, 2) void dense_split_kernel(
     const f16x8 *__restrict__ Xp, const float *__restrict__ Wp, const float *__restrict__ wmax, int n_kt, int n_nt, int n_mb,
     int S, int kt_per_slice, float *__restrict__ slabs) {
     static_assert(MT <= D_MT, "accumulators of MT row blocks must fit the register file");
-    extern __shared__ __attribute__((aligned(16))) char lds[];   // [2][BUF_BYTES]
+    extern __shared__ __attribute__((aligned(16))) char lds[];   // [3][XT4]
     constexpr int XT4 = d_xt_bytes(MT);
-    constexpr int BUF_BYTES = d_buf_bytes(MT);
     constexpr int XPIECES = XT4 / 1024;
-    constexpr int NXP = (XPIECES + 7) / 8;
-    constexpr int NP = 4 + NXP;
-    constexpr int DPB = (NP + MT - 1) / MT;
-    static_assert(DPB <= 5, "at most five DMA pieces per row block");
-    static_assert(NP <= 10, "prologue issues at most ten pieces");
+    constexpr int NXP = (XPIECES + 7) / 8;                // X pieces per wave and tile
+    static_assert(NXP <= 6, "at most six X pieces per wave");
+    // the end-of-tile wait: this wave's pieces of tile t + 1 have landed; W of t + 1 (4) and X of t + 2 (NXP) may not have
+    constexpr int VM_KEEP = 4 + NXP;
+    constexpr int WAIT_TILE = (VM_KEEP & 15) | (7 << 4) | (0 << 8) | ((VM_KEEP >> 4) << 14);   // vmcnt(VM_KEEP) lgkmcnt(0)
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -65,50 +95,54 @@ __global__ __launch_bounds__(D_THREADS, 2) void dense_split_kernel(
     const int ew0 = split_exp(wmax[nt * D_BN + wave * 32 + lr]);
     const int ew1 = split_exp(wmax[nt * D_BN + wave * 32 + 16 + lr]);
 
-    const char *xsrc = reinterpret_cast<const char *>(Xp) + ((int64_t)mb * n_kt + kt0) * XT4 + lane * 16;
-    const char *wsrc = reinterpret_cast<const char *>(Wp) + w_first * D_WTB + lane * 16;
-#define WAGG_DMA_X(q, tile, buf)                                                                  \
-    __builtin_amdgcn_global_load_lds((gptr_t)(xsrc + (int64_t)(tile) * XT4 + (q) * 1024),      \
-                                     (lptr_t)(lds + (buf) * BUF_BYTES + (q) * 1024), 16, 0, 0)
-#define WAGG_DMA_W(q, tile, buf)                                                                  \
-    __builtin_amdgcn_global_load_lds((gptr_t)(wsrc + (int64_t)(tile) * D_WTB + (q) * 1024),   \
-                                     (lptr_t)(lds + (buf) * BUF_BYTES + XT4 + (q) * 1024), 16, 0, 0)
-#define WAGG_DMA_PIECE(i, tile, buf)                                                              \
+    const int f = lr >> 1;
+    const unsigned frag0 = (lr * 8 + (kq ^ f)) * 16;       // piece kq: W k = 4 kq + c, X high parts
+    const unsigned frag1 = (lr * 8 + ((kq ^ f) ^ 4)) * 16; // piece kq + 4: W k = 16 + 4 kq + c, X low parts
+    // buffer descriptors of one tile (wave-uniform: the tile's X image, the tile's W image) and 32-bit per-lane offsets; the
+    // range check holds every W load (and the lane part of every X piece) inside its tile
+    const char *xslice = reinterpret_cast<const char *>(Xp) + ((int64_t)mb * n_kt + kt0) * XT4;
+    const char *wslice = reinterpret_cast<const char *>(Wp) + w_first * D_WTB;
+    const unsigned lane16 = lane * 16;
+    const unsigned wfrag0 = wave * 4096 + frag0, wfrag1 = wave * 4096 + frag1;   // this wave's rows 32 w ... 32 w + 31
+#define WAGG_RSRC(base, bytes) split_tile_rsrc(base, bytes)
+#define WAGG_DMA_X(i, xr, buf)                                                                    \
     do {                                                                                          \
         constexpr int i_ = (i);                                                                   \
-        if constexpr (i_ < 4) WAGG_DMA_W(wave + 8 * i_, tile, buf);                               \
-        else if constexpr (8 * (i_ - 4) + 7 < XPIECES) WAGG_DMA_X(wave + 8 * (i_ - 4), tile, buf); \
-        else { if (wave + 8 * (i_ - 4) < XPIECES) WAGG_DMA_X(wave + 8 * (i_ - 4), tile, buf); }   \
+        const int q_ = (wave + 8 * i_) % XPIECES;                                                 \
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(xr, (lptr_t)(lds + (buf) * XT4 + q_ * 1024), 16, lane16, q_ * 1024, 0, 0); \
     } while (0)
-#define WAGG_DMA_BLOCK(RB, tile, buf)                                                             \
+#define WAGG_DMA_XALL(tile, buf)                                                                  \
     do {                                                                                          \
-        if constexpr (DPB * (RB) + 0 < NP && 0 < DPB) WAGG_DMA_PIECE(DPB * (RB) + 0 < NP ? DPB * (RB) + 0 : 0, tile, buf); \
-        if constexpr (DPB * (RB) + 1 < NP && 1 < DPB) WAGG_DMA_PIECE(DPB * (RB) + 1 < NP ? DPB * (RB) + 1 : 0, tile, buf); \
-        if constexpr (DPB * (RB) + 2 < NP && 2 < DPB) WAGG_DMA_PIECE(DPB * (RB) + 2 < NP ? DPB * (RB) + 2 : 0, tile, buf); \
-        if constexpr (DPB * (RB) + 3 < NP && 3 < DPB) WAGG_DMA_PIECE(DPB * (RB) + 3 < NP ? DPB * (RB) + 3 : 0, tile, buf); \
-        if constexpr (DPB * (RB) + 4 < NP && 4 < DPB) WAGG_DMA_PIECE(DPB * (RB) + 4 < NP ? DPB * (RB) + 4 : 0, tile, buf); \
+        const auto xr_ = WAGG_RSRC(xslice + (int64_t)(tile) * XT4, XT4);                          \
+        WAGG_DMA_X(0, xr_, buf);                                                                  \
+        if constexpr (NXP > 1) WAGG_DMA_X(NXP > 1 ? 1 : 0, xr_, buf);                             \
+        if constexpr (NXP > 2) WAGG_DMA_X(NXP > 2 ? 2 : 0, xr_, buf);                             \
+        if constexpr (NXP > 3) WAGG_DMA_X(NXP > 3 ? 3 : 0, xr_, buf);                             \
+        if constexpr (NXP > 4) WAGG_DMA_X(NXP > 4 ? 4 : 0, xr_, buf);                             \
+        if constexpr (NXP > 5) WAGG_DMA_X(NXP > 5 ? 5 : 0, xr_, buf);                             \
+    } while (0)
+#define WAGG_LOAD_W(tile)                                                                         \
+    do {                                                                                          \
+        const auto wr_ = WAGG_RSRC(wslice + (int64_t)(tile) * D_WTB, D_WTB);                      \
+        b00 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(wr_, wfrag0, 0, 0));        \
+        b01 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(wr_, wfrag1, 0, 0));        \
+        b10 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(wr_, wfrag0 + 2048, 0, 0)); \
+        b11 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(wr_, wfrag1 + 2048, 0, 0)); \
     } while (0)
 
     f32x4 acc[MT][2];
 #pragma unroll
     for (int m = 0; m < MT; ++m) acc[m][0] = acc[m][1] = f32x4{0, 0, 0, 0};
 
+    f32x4 b00, b01, b10, b11;
     if (ntiles > 0) {
-        WAGG_DMA_PIECE(0, 0, 0); WAGG_DMA_PIECE(1, 0, 0); WAGG_DMA_PIECE(2, 0, 0); WAGG_DMA_PIECE(3, 0, 0);
-        WAGG_DMA_PIECE(4, 0, 0);
-        if constexpr (NP > 5) WAGG_DMA_PIECE(NP > 5 ? 5 : 0, 0, 0);
-        if constexpr (NP > 6) WAGG_DMA_PIECE(NP > 6 ? 6 : 0, 0, 0);
-        if constexpr (NP > 7) WAGG_DMA_PIECE(NP > 7 ? 7 : 0, 0, 0);
-        if constexpr (NP > 8) WAGG_DMA_PIECE(NP > 8 ? 8 : 0, 0, 0);
-        if constexpr (NP > 9) WAGG_DMA_PIECE(NP > 9 ? 9 : 0, 0, 0);
+        const int t1 = ntiles > 1 ? 1 : 0;
+        WAGG_LOAD_W(0);
+        WAGG_DMA_XALL(0, 0);
+        WAGG_DMA_XALL(t1, 1);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-
-    const int f = lr >> 1;
-    const int frag0 = (lr * 8 + (kq ^ f)) * 16;            // piece kq: W k = 4 kq + c, X high parts
-    const int frag1 = (lr * 8 + ((kq ^ f) ^ 4)) * 16;      // piece kq + 4: W k = 16 + 4 kq + c, X low parts
-    const int boff = XT4 + wave * (32 * 128);
 
 #define WAGG_MFMA16(RB, CB, A, B) acc[RB][CB] = __builtin_amdgcn_mfma_f32_16x16x32_f16(A, B, acc[RB][CB], 0, 0, 0)
 #define WAGG_READ_A(H, L, RB)                                                                     \
@@ -116,9 +150,19 @@ __global__ __launch_bounds__(D_THREADS, 2) void dense_split_kernel(
         H = *reinterpret_cast<const f16x8 *>(img + frag0 + (RB) * 2048);                          \
         L = *reinterpret_cast<const f16x8 *>(img + frag1 + (RB) * 2048);                          \
     } while (0)
-    // Row block RB: six MFMAs, cross terms first, xh.wh last (the largest term is added to the smallest partial sums
-    // last).  The next block's fragment reads go right behind the first MFMA; the next tile's DMA pieces go after the
-    // third (waves 0-3) or the sixth (waves 4-7), so that one wave of a SIMD always has MFMAs to issue.
+    // X piece i of tile t + 2 goes behind row block xdma_block(i): spread over the tile, none in the first two blocks
+    constexpr auto xdma_block = [](int i) { return MT <= 2 ? MT - 1 : 2 + i * (MT - 2) / NXP; };
+#define WAGG_DMA_AT(RB, i)                                                                        \
+    do {                                                                                          \
+        if constexpr (!(DBG & 1) && (i) < NXP && xdma_block(i) == (RB)) WAGG_DMA_X((i) < NXP ? (i) : 0, xfar, bfar); \
+    } while (0)
+#define WAGG_DMA_BLOCK(RB)                                                                        \
+    do {                                                                                          \
+        WAGG_DMA_AT(RB, 0); WAGG_DMA_AT(RB, 1); WAGG_DMA_AT(RB, 2);                               \
+        WAGG_DMA_AT(RB, 3); WAGG_DMA_AT(RB, 4); WAGG_DMA_AT(RB, 5);                               \
+    } while (0)
+    // Row block RB >= 2: six MFMAs, cross terms first, xh.wh last (the largest term is added to the smallest partial sums
+    // last); the next block's fragment reads go right behind the first MFMA, this block's X pieces behind the last
 #define WAGG_BLOCK_(RB, H, L, NH, NL)                                                             \
     do {                                                                                          \
         __builtin_amdgcn_sched_barrier(0);                                                        \
@@ -128,14 +172,11 @@ __global__ __launch_bounds__(D_THREADS, 2) void dense_split_kernel(
         __builtin_amdgcn_sched_barrier(0);                                                        \
         WAGG_MFMA16(RB, 1, H, wl1);                                                               \
         WAGG_MFMA16(RB, 0, L, wh0);                                                               \
-        __builtin_amdgcn_sched_barrier(0);                                                        \
-        if (early_dma) WAGG_DMA_BLOCK(RB, tnext, nbuf);                                           \
-        __builtin_amdgcn_sched_barrier(0);                                                        \
         WAGG_MFMA16(RB, 1, L, wh1);                                                               \
         WAGG_MFMA16(RB, 0, H, wh0);                                                               \
         WAGG_MFMA16(RB, 1, H, wh1);                                                               \
         __builtin_amdgcn_sched_barrier(0);                                                        \
-        if (!early_dma) WAGG_DMA_BLOCK(RB, tnext, nbuf);                                          \
+        WAGG_DMA_BLOCK(RB);                                                                       \
     } while (0)
 #define WAGG_BLOCK(RB)                                                                            \
     do {                                                                                          \
@@ -146,31 +187,58 @@ __global__ __launch_bounds__(D_THREADS, 2) void dense_split_kernel(
         }                                                                                         \
     } while (0)
 
-    const bool early_dma = wave < 4;
+    int bcur = 0;                                              // ring buffer of tile t
     for (int tile = 0; tile < ntiles; ++tile) {
-        const char *img = lds + (tile & 1) * BUF_BYTES;
-        const int nbuf = (tile & 1) ^ 1;
-        const int tnext = tile + 1 < ntiles ? tile + 1 : tile;     // last tile: harmless re-load
+        const char *img = lds + bcur * XT4;
+        const int bfar = bcur == 0 ? 2 : bcur - 1;                // buffer of tile t + 2 (read by tile t - 1)
+        const int tnext = tile + 1 < ntiles ? tile + 1 : ntiles - 1;   // last tiles: harmless re-loads inside the slice
+        const int tfar = tile + 2 < ntiles ? tile + 2 : ntiles - 1;
+        const auto xfar = WAGG_RSRC(xslice + (int64_t)tfar * XT4, XT4);
         f16x8 wh0, wl0, wh1, wl1, aAh, aAl, aBh, aBl;
-        {
-            const f32x4 b00 = *reinterpret_cast<const f32x4 *>(img + boff + frag0);
-            const f32x4 b01 = *reinterpret_cast<const f32x4 *>(img + boff + frag1);
-            const f32x4 b10 = *reinterpret_cast<const f32x4 *>(img + boff + 2048 + frag0);
-            const f32x4 b11 = *reinterpret_cast<const f32x4 *>(img + boff + 2048 + frag1);
-            WAGG_READ_A(aAh, aAl, 0);
-            split_w8(b00, b01, ew0, wh0, wl0);
-            split_w8(b10, b11, ew1, wh1, wl1);
+        // row blocks 0 and 1, column block 0, with column block 1's split between the MFMAs; then W of tile t + 1
+        WAGG_READ_A(aAh, aAl, 0);
+        split_w8(b00, b01, ew0, wh0, wl0);
+        if constexpr (MT > 1) WAGG_READ_A(aBh, aBl, MT > 1 ? 1 : 0);
+        __builtin_amdgcn_sched_barrier(0);
+        WAGG_MFMA16(0, 0, aAh, wl0);
+        WAGG_MFMA16(0, 0, aAl, wh0);
+        WAGG_MFMA16(0, 0, aAh, wh0);
+        if constexpr (MT > 1) {
+            WAGG_MFMA16(MT > 1 ? 1 : 0, 0, aBh, wl0);
+            WAGG_MFMA16(MT > 1 ? 1 : 0, 0, aBl, wh0);
+            WAGG_MFMA16(MT > 1 ? 1 : 0, 0, aBh, wh0);
         }
-        WAGG_BLOCK(0); WAGG_BLOCK(1); WAGG_BLOCK(2); WAGG_BLOCK(3); WAGG_BLOCK(4); WAGG_BLOCK(5);
+        split_w8(b10, b11, ew1, wh1, wl1);
+        __builtin_amdgcn_sched_barrier(0);
+        if constexpr (!(DBG & 1)) WAGG_LOAD_W(tnext);
+        __builtin_amdgcn_sched_barrier(0);
+        WAGG_MFMA16(0, 1, aAh, wl1);
+        WAGG_MFMA16(0, 1, aAl, wh1);
+        WAGG_MFMA16(0, 1, aAh, wh1);
+        __builtin_amdgcn_sched_barrier(0);
+        if constexpr (MT > 2) WAGG_READ_A(aAh, aAl, MT > 2 ? 2 : 0);
+        __builtin_amdgcn_sched_barrier(0);
+        if constexpr (MT > 1) {
+            WAGG_MFMA16(MT > 1 ? 1 : 0, 1, aBh, wl1);
+            WAGG_MFMA16(MT > 1 ? 1 : 0, 1, aBl, wh1);
+            WAGG_MFMA16(MT > 1 ? 1 : 0, 1, aBh, wh1);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        WAGG_DMA_BLOCK(0); WAGG_DMA_BLOCK(1);
+        WAGG_BLOCK(2); WAGG_BLOCK(3); WAGG_BLOCK(4); WAGG_BLOCK(5);
         WAGG_BLOCK(6); WAGG_BLOCK(7); WAGG_BLOCK(8); WAGG_BLOCK(9); WAGG_BLOCK(10); WAGG_BLOCK(11);
         WAGG_BLOCK(12); WAGG_BLOCK(13); WAGG_BLOCK(14); WAGG_BLOCK(15); WAGG_BLOCK(16); WAGG_BLOCK(17);
         WAGG_BLOCK(18); WAGG_BLOCK(19); WAGG_BLOCK(20); WAGG_BLOCK(21); WAGG_BLOCK(22);
         static_assert(MT <= 23, "row blocks are written out up to 22");
         __builtin_amdgcn_sched_barrier(0);
-        // this wave's DMA pieces of tile+1 have landed; every wave is done reading this buffer
-        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
+        if constexpr (!(DBG & 4)) {
+            __builtin_amdgcn_s_waitcnt(WAIT_TILE);
+            __builtin_amdgcn_s_barrier();
+        }
+        bcur = bcur == 2 ? 0 : bcur + 1;
     }
+    // the re-loads behind the last tile land before the wave ends
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 
     // C/D map of the f16 form: col = lane & 15, row = 4 (lane >> 4) + reg (as v_mfma_f32_16x16x4_f32)
     float *slab = slabs + ((((int64_t)mb * n_nt + nt) * S + ks) * (MT * 16)) * D_BN;
@@ -181,9 +249,11 @@ __global__ __launch_bounds__(D_THREADS, 2) void dense_split_kernel(
 #pragma unroll
             for (int r = 0; r < 4; ++r)
                 slab[(m * 16 + kq * 4 + r) * D_BN + wave * 32 + cb * 16 + lr] = acc[m][cb][r];
+#undef WAGG_RSRC
 #undef WAGG_DMA_X
-#undef WAGG_DMA_W
-#undef WAGG_DMA_PIECE
+#undef WAGG_DMA_XALL
+#undef WAGG_LOAD_W
+#undef WAGG_DMA_AT
 #undef WAGG_DMA_BLOCK
 #undef WAGG_MFMA16
 #undef WAGG_READ_A
