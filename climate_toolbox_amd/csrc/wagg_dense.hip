@@ -531,7 +531,7 @@ constexpr double SPMM_MAX_FILL = 0.10;
 struct FormRates { double full, tiled, entries_scale, dma; };
 // fp32: full 204.3 ms for 2,282 rows x 8,100 x 96 tiles on the fp32 pipe (142 TF), since the split form (f16 pipe, row maxima
 // and split pack included) 2.99x that: c2-dense 42.6 against 127.3 ms a step on one box, A/B -> 420 TF (re-derived for the
-// W-in-registers pipeline from the form guard's forced full-form times, 4.07-4.28 ms = 424-446 TF: kept); tile-sparse (a
+// W-in-registers pipeline from the form guard's forced full-form times, 424-446 TF, then 445-470 TF: kept); tile-sparse (a
 // workgroup walks an equal share of the stored tiles: dense_pieces_kernel) 144 TF on the stored tiles' flops (c5-block:
 // 8.39 ms), fp64 73 TF (16.58 ms); c5-uniform-f64 of bench.py for the fp64 entry-list scale
 constexpr FormRates FORM_RATES_F32 = {420e12, 144e12, 1.0, 10.1e12};
@@ -953,6 +953,8 @@ static int dense_apply_split(wagg_dense *d, const float *X_dev, int64_t Tn, int6
             case 1: kern = (const void *)dense_split_kernel<D_MT, 1>; break;
             case 4: kern = (const void *)dense_split_kernel<D_MT, 4>; break;
             case 5: kern = (const void *)dense_split_kernel<D_MT, 5>; break;
+            case 8: kern = (const void *)dense_split_kernel<D_MT, 8>; break;
+            case 9: kern = (const void *)dense_split_kernel<D_MT, 9>; break;
             default: break;
         }
     }

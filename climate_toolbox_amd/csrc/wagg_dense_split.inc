@@ -22,15 +22,32 @@ __host__ __device__ __forceinline__ int split_exp(float m) {
     return 15 - e;
 }
 
-// four fp32 W values of piece kq and four of piece kq + 4 -> scaled f16 high and low parts, in k order
+// four fp32 W values of piece kq and four of piece kq + 4 -> scaled f16 high and low parts, in k order, a pair of values
+// at a time: v = w 2^e, h = f16(v) (one v_cvt_pk_f16_f32 a pair), l = f16(v - (float)h).  v - (float)h is exact in fp32
+// (h is v rounded to eleven bits), and so is (float)h x -1, so one fused multiply-add that reads the f16 half and rounds its
+// fp32 result to f16 gives the bits of conversion back, subtraction and conversion: v_fma_mixlo_f16 / v_fma_mixhi_f16,
+// two instructions a pair where the plain form takes five (the whole split is 40 vector instructions a tile and wave where
+// the plain form compiled to 62).  The compiler folds the multiplier -1 into a subtraction again (or packs the pair into
+// v_pk_fma_f32), so the two are written out; the closing s_nop covers the matrix instruction that reads the result next.
+typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ void split_w8(f32x4 a, f32x4 b, int e, f16x8 &hi, f16x8 &lo) {
+    u32x4 H, L;
 #pragma unroll
-    for (int c = 0; c < 4; ++c) {
-        const float va = __builtin_amdgcn_ldexpf(a[c], e), vb = __builtin_amdgcn_ldexpf(b[c], e);
-        const _Float16 ha = (_Float16)va, hb = (_Float16)vb;
-        hi[c] = ha; hi[4 + c] = hb;
-        lo[c] = (_Float16)(va - (float)ha); lo[4 + c] = (_Float16)(vb - (float)hb);
+    for (int p = 0; p < 4; ++p) {
+        const float v0 = __builtin_amdgcn_ldexpf(p < 2 ? a[2 * p] : b[2 * p - 4], e);
+        const float v1 = __builtin_amdgcn_ldexpf(p < 2 ? a[2 * p + 1] : b[2 * p - 3], e);
+        const unsigned h = __builtin_bit_cast(unsigned, f16x2{(_Float16)v0, (_Float16)v1});
+        unsigned l;
+        asm("v_fma_mixlo_f16 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]\n\t"
+            "v_fma_mixhi_f16 %0, %1, -1.0, %3 op_sel:[1,0,0] op_sel_hi:[1,0,0]\n\t"
+            "s_nop 1"
+            : "=&v"(l) : "v"(h), "v"(v0), "v"(v1));
+        H[p] = h;
+        L[p] = l;
     }
+    hi = __builtin_bit_cast(f16x8, H);
+    lo = __builtin_bit_cast(f16x8, L);
 }
 
 // Pipeline (the fp32 kernel's double buffer left the f16 tile -- 3 x 16 cycles a row-block column -- about half a tile for
@@ -51,7 +68,8 @@ __device__ __forceinline__ void split_w8(f32x4 a, f32x4 b, int e, f16x8 &hi, f16
 // kernel's, bit for bit.
 //
 // DBG is a diagnostic knob (WAGG_SPLIT_DBG env, read by the -DWAGG_DIAG build only; tools/split_ablate.sh): bit0 = no W loads
-// and no X DMA in the k-loop, bit2 = no per-tile wait or barrier.  Results are wrong with either bit set.
+// and no X DMA in the k-loop, bit2 = no per-tile wait or barrier, bit3 = no split arithmetic (the raw register pairs go to
+// the MFMAs as they are: same loads, same waits).  Results are wrong with any bit set.
 
 // buffer descriptor of `bytes` bytes at a wave-uniform address (read back from lane 0, so that the compiler keeps the
 // descriptor in SGPRs instead of looping over the lanes' copies)
@@ -144,6 +162,12 @@ __global__ __launch_bounds__(D_THREADS, 2) void dense_split_kernel(
         __builtin_amdgcn_s_barrier();
     }
 
+    // DBG bit3: no split arithmetic, the raw register pairs go to the MFMAs as they are (same loads, same waits)
+#define WAGG_SPLIT(A, B, E, HI, LO)                                                               \
+    do {                                                                                          \
+        if constexpr (DBG & 8) { HI = __builtin_bit_cast(f16x8, A); LO = __builtin_bit_cast(f16x8, B); } \
+        else split_w8(A, B, E, HI, LO);                                                           \
+    } while (0)
 #define WAGG_MFMA16(RB, CB, A, B) acc[RB][CB] = __builtin_amdgcn_mfma_f32_16x16x32_f16(A, B, acc[RB][CB], 0, 0, 0)
 #define WAGG_READ_A(H, L, RB)                                                                     \
     do {                                                                                          \
@@ -197,7 +221,7 @@ __global__ __launch_bounds__(D_THREADS, 2) void dense_split_kernel(
         f16x8 wh0, wl0, wh1, wl1, aAh, aAl, aBh, aBl;
         // row blocks 0 and 1, column block 0, with column block 1's split between the MFMAs; then W of tile t + 1
         WAGG_READ_A(aAh, aAl, 0);
-        split_w8(b00, b01, ew0, wh0, wl0);
+        WAGG_SPLIT(b00, b01, ew0, wh0, wl0);
         if constexpr (MT > 1) WAGG_READ_A(aBh, aBl, MT > 1 ? 1 : 0);
         __builtin_amdgcn_sched_barrier(0);
         WAGG_MFMA16(0, 0, aAh, wl0);
@@ -208,7 +232,7 @@ __global__ __launch_bounds__(D_THREADS, 2) void dense_split_kernel(
             WAGG_MFMA16(MT > 1 ? 1 : 0, 0, aBl, wh0);
             WAGG_MFMA16(MT > 1 ? 1 : 0, 0, aBh, wh0);
         }
-        split_w8(b10, b11, ew1, wh1, wl1);
+        WAGG_SPLIT(b10, b11, ew1, wh1, wl1);
         __builtin_amdgcn_sched_barrier(0);
         if constexpr (!(DBG & 1)) WAGG_LOAD_W(tnext);
         __builtin_amdgcn_sched_barrier(0);
@@ -255,6 +279,7 @@ __global__ __launch_bounds__(D_THREADS, 2) void dense_split_kernel(
 #undef WAGG_LOAD_W
 #undef WAGG_DMA_AT
 #undef WAGG_DMA_BLOCK
+#undef WAGG_SPLIT
 #undef WAGG_MFMA16
 #undef WAGG_READ_A
 #undef WAGG_BLOCK_
