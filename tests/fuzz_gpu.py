@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Randomised differential run of every C-ABI compute entry point against the oracle (GPU box).
-usage: python tests/fuzz_gpu.py [n_cases] [seed]      -- prints one line per failing case, exit 1 on any"""
+usage: python tests/fuzz_gpu.py [n_cases] [seed]      -- prints one line per failing case, exit 1 on any
+FUZZ_LINES=1: lines_case (the lines-only host path); FUZZ_MANY=1: many_case (many-plans, wagg_plan_create_many)"""
 import os, sys, traceback
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -13,6 +14,7 @@ SEED = int(sys.argv[2]) if len(sys.argv) > 2 else 0
 
 
 N_LINES = 0
+N_FUSED = 0
 
 
 def rel_bad(got, ref, rtol, scale):
@@ -212,10 +214,112 @@ def lines_case(i, rng):
     return tag, fails
 
 
+def many_case(i, rng):
+    """FUZZ_MANY=1: many-plans (engine.ManyPlan) over compact tables: 1..4 weight columns with independent NaN / 0 entries,
+    0..3 derived levels (the block coordinates integer-divided, so they nest by construction), sometimes a null label shared
+    by all levels, NaN and sometimes +-inf data, padded / unaligned rows, either result layout.  Every plane against the
+    oracle over that weighting's raw column, the fine planes bit for bit the single plans over the columns the many-plan
+    uses; for unpadded (time, region) results one host flag set, bit for bit the device apply.  A table without the
+    whole-line chunking of the data type must refuse derived levels; the case goes on with none."""
+    from climate_toolbox_amd import _lib
+    from climate_toolbox_amd.engine import ManyPlan
+    dtype = np.float32 if rng.random() < 0.6 else np.float64
+    rtol = 1e-4 if dtype == np.float32 else 1e-6
+    T = int(rng.choice([1, 2, 3, 7, 16, 63, 64, 65, 100, 129, 200]))
+    sc = int(os.environ.get("FUZZ_SCALE", "1"))
+    nlat = int(rng.integers(2, 60 * sc))
+    nlon = 4 * int(rng.integers(1, 23 * sc)) if rng.random() < 0.85 else int(rng.integers(1, 90 * sc))   # (whole-line chunkings: rows of whole quads)
+    G = nlat * nlon
+    # the compact table of one_case: regions = blocks of the grid with holes, a few split cells
+    bh, bw = int(rng.integers(1, 9)), int(rng.integers(1, 17))
+    keep = np.flatnonzero(rng.random(G) < rng.uniform(0.3, 1.0))
+    if not len(keep):
+        keep = np.array([int(rng.integers(0, G))])
+    nbw = (nlon + bw - 1) // bw
+    reg = ((keep // nlon) // bh) * nbw + (keep % nlon) // bw
+    R = int(reg.max()) + 1 + int(rng.integers(0, 3))                                   # (sometimes a region nobody maps to)
+    extra = rng.choice(keep, min(len(keep), 40))
+    cell = np.concatenate([keep, extra]).astype(np.int32)
+    code = np.concatenate([reg, rng.integers(0, R, len(extra))]).astype(np.int32)
+    null = np.zeros(len(code), dtype=bool)
+    if rng.random() < 0.4:
+        null[rng.integers(0, len(code), 3)] = True
+    L = int(rng.integers(0, 4))
+    levels, f = [], 1
+    for _ in range(L):                                                                 # block (by, bx) -> (by // f, bx // f)
+        f *= int(rng.integers(2, 4))
+        nbc = (nbw + f - 1) // f
+        lc = ((code // nbw) // f) * nbc + (code % nbw) // f
+        levels.append((np.where(null, -1, lc).astype(np.int32), (((R - 1) // nbw) // f + 1) * nbc + int(rng.integers(0, 2))))
+    code[null] = -1
+    K = int(rng.integers(1, 5))
+    ws = []
+    for _ in range(K):
+        w = rng.uniform(0.05, 3.0, len(cell))
+        w[rng.random(len(cell)) < 0.05] = np.nan
+        w[rng.random(len(cell)) < 0.03] = 0.0
+        ws.append(w)
+    kept = ~np.isnan(np.stack(ws)).all(axis=0)
+    cols = [np.where(kept, np.where(np.isnan(w), 0.0, w), np.nan) for w in ws]         # what the many-plan makes of column k
+    X = (288.0 + 9.0 * rng.standard_normal((T, G))).astype(dtype)
+    if rng.random() < 0.6:
+        X[rng.integers(0, T, 5), cell[rng.integers(0, len(cell), 5)]] = np.nan
+    if rng.random() < 0.4:
+        X[rng.integers(0, T), cell[rng.integers(0, len(cell))]] = np.inf
+    if rng.random() < 0.3:
+        X[rng.integers(0, T), cell[rng.integers(0, len(cell))]] = -np.inf
+    out_layout = "TR" if rng.random() < 0.6 else "RT"
+    pad = int(rng.choice([0, 0, 1, 3, 4]))
+    hflags = int(rng.choice([0, _lib.HOST_PIN, _lib.HOST_WHOLE, _lib.HOST_PIN | _lib.HOST_WHOLE, _lib.HOST_LINES, _lib.HOST_PIN | _lib.HOST_LINES,
+                             _lib.HOST_PIN | _lib.HOST_LINES | _lib.HOST_LINES_WHOLE]))
+    tag = "many case %d: %s T=%d grid=%dx%d R=%d nseg=%d K=%d L=%d TG->%s pad=%d" % (i, dtype.__name__, T, nlat, nlon, R, len(cell), K, L, out_layout, pad)
+    if pad:
+        buf = torch.full((T, G + pad), float("nan"), dtype=torch.from_numpy(X).dtype, device="cuda")
+        c0 = 1 if pad in (1, 3) else 0                                                 # (pad 1, 3: rows that are not 16-byte aligned)
+        buf[:, c0:c0 + G] = torch.from_numpy(X).cuda()
+        Xd = buf[:, c0:c0 + G]
+    else:
+        Xd = torch.from_numpy(X).cuda()
+    fails = []
+    plan = ManyPlan(cell, code, ws, G, R, row_len=nlon, levels=levels)
+    fused = bool(plan.info["lines"] & (1 if dtype == np.float32 else 2))
+    if not fused and L:
+        try:
+            plan.apply(Xd, out_layout=out_layout)
+            fails.append("derived levels without the whole-line chunking were not refused")
+        except _lib.WaggError as e:
+            if e.code != -5: fails.append("derived levels refused with code %d" % e.code)
+        plan.close()
+        levels, L = [], 0
+        plan = ManyPlan(cell, code, ws, G, R, row_len=nlon)
+    tag += " [fused]" if fused else " [one by one]"
+    views = plan.apply(Xd, out_layout=out_layout)
+    got = [[v.cpu().numpy() if out_layout == "TR" else v.cpu().numpy().T for v in row] for row in views]
+    for l, (lc, Rl) in enumerate([(code, R)] + levels):
+        for k in range(K):
+            b = rel_bad(got[l][k], O.agg_coded(X, cell, lc, ws[k], Rl), rtol, 1.0)
+            if b: fails.append("plane (%d, %d): %s" % (l, k, b))
+    for k in range(K):
+        single = SparsePlan(cell, code, cols[k], G, R, row_len=nlon)
+        g1 = single.apply(Xd, out_layout=out_layout).cpu().numpy()
+        if not np.array_equal(g1 if out_layout == "TR" else g1.T, got[0][k], equal_nan=True): fails.append("fine plane %d differs from the single plan" % k)
+        if not np.array_equal(plan.den[0][k], single.den, equal_nan=True): fails.append("den of weighting %d differs from the single plan" % k)
+        single.close()
+    if pad == 0 and out_layout == "TR":
+        host = plan.apply_host(X, flags=hflags)
+        for l in range(L + 1):
+            for k in range(K):
+                if not np.array_equal(host[l][k], got[l][k], equal_nan=True): fails.append("apply_host(flags %d) plane (%d, %d) differs from the device apply" % (hflags, l, k))
+    plan.close()
+    return tag, fails
+
+
 def main():
     global one_case
     if os.environ.get("FUZZ_LINES"):
         one_case = lines_case
+    if os.environ.get("FUZZ_MANY"):
+        one_case = many_case
     rng = np.random.default_rng(SEED)
     bad = 0
     for i in range(N):
@@ -223,14 +327,17 @@ def main():
             tag, fails = one_case(i, rng)
         except Exception as e:                                                        # a crash is a failure too
             tag, fails = "case %d" % i, ["exception: %s" % traceback.format_exc().splitlines()[-1]]
-        global N_LINES
+        global N_LINES, N_FUSED
         N_LINES += "[lines]" in tag
+        N_FUSED += "[fused]" in tag
         if fails:
             bad += 1
             print(tag, "|", "; ".join(fails), flush=True)
         if i % 25 == 24:
             print("... %d cases, %d failing" % (i + 1, bad), flush=True)
     print("fuzz: %d cases, %d failing (%d of them took the lines-only host path)" % (N, bad, N_LINES))
+    if os.environ.get("FUZZ_MANY"):
+        print("fuzz: %d of the many-plan cases took the fused kernel" % N_FUSED)
     return 1 if bad else 0
 
 
