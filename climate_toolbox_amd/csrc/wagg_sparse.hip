@@ -1329,6 +1329,11 @@ static int launch_sparse(const wagg_plan *plan, const T *X, int64_t Ttot, int64_
     // aligned fast path: 16-byte aligned rows
     const bool vec = ((reinterpret_cast<uintptr_t>(X) & 15) == 0) && ((ldx * sizeof(T)) % 16 == 0) &&
                      (xpow != XF_EDD || (reinterpret_cast<uintptr_t>(X2) & 15) == 0);
+    // sparse_stream_kernel and sparse_gather_kernel fetch a quad as FOUR elements in one load: 32 bytes of a fp64 row, whose
+    // 16-byte alignment says nothing about G % 4.  With ldx == G and G % 4 == 2 the region-shaped chunking's last quad
+    // (cells G - 2, G - 1) would be read two elements past the end of the last row: such grids take the clamped arm.
+    // (fp32: aligned rows have ldx % 4 == 0, so a quad never leaves its row.  sparse_lcv_kernel loads 16-byte pieces.)
+    const bool vec_quad = vec && (sizeof(T) == 4 || plan->info.G % 4 == 0);
     // degree days (two fields): fp32 (time, gridcell) data in the loader/consumer kernel, everything else in the
     // chunk-walking kernel
     const bool edd = xpow == XF_EDD;
@@ -1376,7 +1381,7 @@ static int launch_sparse(const wagg_plan *plan, const T *X, int64_t Ttot, int64_
         const long long n_items = (long long)n_norm * n_tb;
         const long long nw = n_items < 2LL * ncu ? n_items : 2LL * ncu;
         const size_t shmem = SparseLds<T, TB>::total;
-        auto kern = vec ? sparse_stream_kernel<T, TB, true> : sparse_stream_kernel<T, TB, false>;
+        auto kern = vec_quad ? sparse_stream_kernel<T, TB, true> : sparse_stream_kernel<T, TB, false>;
         unsigned long long *stamps = nullptr;
         const bool do_stamp = diag_set("WAGG_SPARSE_STAMP");
 #ifdef WAGG_DIAG
@@ -1423,7 +1428,7 @@ static int launch_sparse(const wagg_plan *plan, const T *X, int64_t Ttot, int64_
             launch_timed(!main_done, kern, grid, block, shmem, stream, pv, X, Ttot, ldx,         \
                          (int64_t)plan->info.G, kout + (int64_t)pz * kpstride, kldo);            \
         } while (0)
-        if (layout == WAGG_LAYOUT_TG) { if (vec) WAGG_LAUNCH(WAGG_LAYOUT_TG, WAGG_OUT_RT, true); else WAGG_LAUNCH(WAGG_LAYOUT_TG, WAGG_OUT_RT, false); }
+        if (layout == WAGG_LAYOUT_TG) { if (vec_quad) WAGG_LAUNCH(WAGG_LAYOUT_TG, WAGG_OUT_RT, true); else WAGG_LAUNCH(WAGG_LAYOUT_TG, WAGG_OUT_RT, false); }
         else WAGG_LAUNCH(WAGG_LAYOUT_GT, WAGG_OUT_RT, false);
 #undef WAGG_LAUNCH
         WAGG_HIP(hipGetLastError());

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Randomised differential run of every C-ABI compute entry point against the oracle (GPU box).
 usage: python tests/fuzz_gpu.py [n_cases] [seed]      -- prints one line per failing case, exit 1 on any
-FUZZ_LINES=1: lines_case (the lines-only host path); FUZZ_MANY=1: many_case (many-plans, wagg_plan_create_many)"""
+FUZZ_LINES=1: lines_case (the lines-only host path); FUZZ_MANY=1: many_case (many-plans, wagg_plan_create_many);
+FUZZ_FLAGS=1: flags_case (the kernels behind the WAGG_PLAN_NO_* flags and plans without a row length)"""
 import os, sys, traceback
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -314,12 +315,111 @@ def many_case(i, rng):
     return tag, fails
 
 
+def flags_case(i, rng, run=True):
+    """FUZZ_FLAGS=1: single plans on the fallback routes of the table above lcv_pick (csrc/wagg_sparse.hip): row_len given or
+    not, flags 0 / NO_LC / NO_STREAM / NO_LINES and their pairs, over compact tables with (mostly) a giant region, sometimes
+    null labels, NaN / 0 weights; NaN and sometimes +-inf data, either layout of data and result, padded / unaligned rows; the
+    plain aggregation and one of: nothing more, one power, fused powers K = 1..5, 1..6 degree-day thresholds.  Every plane
+    against the oracle, the second plain apply bit for bit the first.  The tag names the route by that table -- [route A]: no
+    whole-line chunking, flags otherwise 0; [route C]: NO_LC; [route D]: NO_STREAM; [route F]: the default -- and [edd on
+    gather] where degree days run on a plan without the loader/consumer kernel.  run=False: the tag alone, from the same
+    random stream (no GPU)."""
+    from climate_toolbox_amd import _lib
+    dtype = np.float32 if rng.random() < 0.5 else np.float64
+    rtol = 1e-4 if dtype == np.float32 else 1e-6
+    T = int(rng.choice([1, 2, 3, 7, 16, 63, 64, 65, 100, 129, 130]))
+    sc = int(os.environ.get("FUZZ_SCALE", "1"))
+    nlat = int(rng.integers(4, 60 * sc))
+    nlon = 4 * int(rng.integers(2, 23 * sc)) if rng.random() < 0.7 else int(rng.integers(5, 90 * sc))
+    G = nlat * nlon
+    bh, bw = int(rng.integers(1, 9)), int(rng.integers(1, 17))
+    keep = np.flatnonzero(rng.random(G) < rng.uniform(0.3, 1.0))
+    if not len(keep):
+        keep = np.array([int(rng.integers(0, G))])
+    nbw = (nlon + bw - 1) // bw
+    reg = ((keep // nlon) // bh) * nbw + (keep % nlon) // bw
+    R = int(reg.max()) + 1 + int(rng.integers(0, 3))                                   # (sometimes a region nobody maps to)
+    extra = rng.choice(keep, min(len(keep), 40))
+    cell = np.concatenate([keep, extra]).astype(np.int32)
+    code = np.concatenate([reg, rng.integers(0, R, len(extra))]).astype(np.int32)
+    if rng.random() < 0.4:
+        code[rng.integers(0, len(code), 3)] = -1
+    giant = rng.random() < 0.6 and G > 400
+    if giant:                                                                         # a run of cells plus scattered ones, as a region of its own
+        n = int(rng.integers(260, min(G, 1500)))
+        start = int(rng.integers(0, G - n // 2))
+        cell = np.concatenate([cell, np.arange(start, start + n // 2), rng.choice(G, n - n // 2, replace=False)]).astype(np.int32)
+        code = np.concatenate([code, np.full(n, R)]).astype(np.int32)
+        R += 1
+    w = rng.uniform(0.05, 3.0, len(cell))
+    w[rng.random(len(cell)) < 0.05] = np.nan
+    w[rng.random(len(cell)) < 0.03] = 0.0
+    X = (288.0 + 9.0 * rng.standard_normal((T, G))).astype(dtype)
+    if rng.random() < 0.6:
+        X[rng.integers(0, T, 5), cell[rng.integers(0, len(cell), 5)]] = np.nan
+    if rng.random() < 0.4:
+        X[rng.integers(0, T), cell[rng.integers(0, len(cell))]] = np.inf
+    if rng.random() < 0.3:
+        X[rng.integers(0, T), cell[rng.integers(0, len(cell))]] = -np.inf
+    layout = "TG" if rng.random() < 0.6 else "GT"
+    out_layout = "TR" if rng.random() < 0.6 else "RT"
+    pad = int(rng.choice([0, 0, 1, 3, 4]))
+    row_len = nlon if rng.random() < 0.5 else 0
+    LC, ST, LN = _lib.PLAN_NO_LC, _lib.PLAN_NO_STREAM, _lib.PLAN_NO_LINES
+    flags = int(rng.choice([0, 0, LC, ST, LN, LC | ST, LC | LN, ST | LN]))
+    kind = ["none", "power", "fused", "edd"][int(rng.choice(4, p=[0.2, 0.15, 0.25, 0.4]))]
+    n = int(rng.integers(1, 5)) if kind == "power" else int(rng.integers(1, 6)) if kind == "fused" else int(rng.integers(1, 7))
+    half = rng.uniform(0, 8, X.shape).astype(dtype)
+    thr = [float(e) for e in rng.uniform(5, 35, 6)[:n]]
+    route = "D" if flags & ST else "C" if flags & LC else "A" if (row_len == 0 or flags & LN) else "F"
+    tag = "flags case %d: %s T=%d grid=%dx%d R=%d nseg=%d row_len=%d flags=%d %s->%s pad=%d %s(%d)%s [route %s]%s" % (
+        i, dtype.__name__, T, nlat, nlon, R, len(cell), row_len, flags, layout, out_layout, pad, kind, n, " giant" if giant else "",
+        route, " [edd on gather]" if kind == "edd" and route != "F" else "")
+    if not run:
+        return tag, None
+
+    def dev(a):                                                                       # NaN in the pad; pad 1, 3: rows not 16-byte aligned
+        a = torch.from_numpy(np.ascontiguousarray(a if layout == "TG" else a.T)).cuda()
+        if not pad:
+            return a
+        buf = torch.full((a.shape[0], a.shape[1] + pad), float("nan"), dtype=a.dtype, device="cuda")
+        c0 = 1 if pad in (1, 3) else 0
+        buf[:, c0:c0 + a.shape[1]] = a
+        return buf[:, c0:c0 + a.shape[1]]
+
+    def tr(a):
+        return a if out_layout == "TR" else np.swapaxes(a, -1, -2)
+    fails = []
+    plan = SparsePlan(cell, code, w, G, R, row_len=row_len, flags=flags)
+    Xd = dev(X)
+    got = plan.apply(Xd, layout=layout, out_layout=out_layout).cpu().numpy()
+    b = rel_bad(tr(got), O.agg_coded(X, cell, code, w, R), rtol, 1.0)
+    if b: fails.append("apply: " + b)
+    if not np.array_equal(plan.apply(Xd, layout=layout, out_layout=out_layout).cpu().numpy(), got, equal_nan=True): fails.append("the second apply differs")
+    if kind in ("power", "fused"):
+        p0, K = (n, 1) if kind == "power" else (1, n)
+        gp = tr(plan.apply_poly(Xd, -273.15, K, layout=layout, out_layout=out_layout, pow_first=p0).cpu().numpy())
+        for k in range(K):
+            b = rel_bad(gp[k], O.agg_coded(O.tas_poly_values(X, p0 + k), cell, code, w, R), rtol, 10.0 ** (p0 + k))
+            if b: fails.append("poly p=%d: %s" % (p0 + k, b))
+    elif kind == "edd":
+        lo, hi = X - half, X + half
+        ge = tr(plan.apply_edd(dev(lo), dev(hi), thr, offset=-273.15, layout=layout, out_layout=out_layout).cpu().numpy())
+        for k, e in enumerate(thr):
+            b = rel_bad(ge[k], O.agg_coded(O.snyder_edd_values(lo + dtype(-273.15), hi + dtype(-273.15), e), cell, code, w, R), rtol, 0.05)
+            if b: fails.append("edd e=%.2f: %s" % (e, b))
+    plan.close()
+    return tag, fails
+
+
 def main():
     global one_case
     if os.environ.get("FUZZ_LINES"):
         one_case = lines_case
     if os.environ.get("FUZZ_MANY"):
         one_case = many_case
+    if os.environ.get("FUZZ_FLAGS"):
+        one_case = flags_case
     rng = np.random.default_rng(SEED)
     bad = 0
     for i in range(N):
