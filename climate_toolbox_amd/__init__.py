@@ -14,6 +14,7 @@ from .aggregations import (  # noqa: F401
     _aggregate_reindexed_data_to_regions,
 )
 from .many import weighted_aggregate_grid_to_regions_many  # noqa: F401  (several weightings / levels, one pass)
+from .periods import weighted_aggregate_grid_to_regions_periods  # noqa: F401  (annual / monthly / labelled totals on the device)
 from .standardize import (  # noqa: F401  (coordinate standardisation folded into the plan)
     standardize_climate_data,
     convert_lons_split,

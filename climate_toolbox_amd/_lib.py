@@ -46,6 +46,7 @@ EXPORTS = (
     "wagg_apply", "wagg_struct_size", "wagg_struct_ordinals", "wagg_plan_get_info_sized", "wagg_dense_get_info_sized",
     "wagg_host_stats_read_sized",
     "wagg_plan_create_many", "wagg_plan_many_info", "wagg_plan_get_den_many",
+    "wagg_period_reduce_f32", "wagg_period_reduce_f64", "wagg_period_reduce_work_bytes",
 )
 STRUCT_PLAN_INFO, STRUCT_DENSE_INFO, STRUCT_HOST_STATS, STRUCT_APPLY_DESC = 0, 1, 2, 3
 PLAN_SEGMENT, PLAN_DENSE = 0, 1
@@ -54,6 +55,7 @@ XF_NONE, XF_POLY, XF_EDD = 0, 1, 2
 # wagg_apply_desc.flags with a dense-family plan: fp32 full form through the fp32 MFMA kernel instead of the split form
 APPLY_EXACT_F32 = 0x10000
 T_F32, T_F64 = 7, 8
+PERIOD_KEEP_NAN, PERIOD_ROWS_CHECKED = 1, 2      # WAGG_PERIOD_*
 
 
 class HostStats(C.Structure):
@@ -260,9 +262,14 @@ def load():
     L.wagg_shard_group_info.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     for name in ("wagg_apply_sharded_f32", "wagg_apply_sharded_f64", "wagg_dense_apply_sharded_f32", "wagg_dense_apply_sharded_f64"):
         getattr(L, name).argtypes = [vp, C.POINTER(vp), C.POINTER(vp), i64p, C.c_int64, vp, C.c_int64, C.c_int]
+    for name in ("wagg_period_reduce_f32", "wagg_period_reduce_f64"):
+        getattr(L, name).argtypes = [vp, vp, C.c_int64, C.c_int64, C.c_int64, vp, vp, C.c_int32, C.c_int64, C.c_int, C.c_double, C.c_int,
+                                     C.c_int, f64p, C.c_int, C.c_int, vp, C.c_int64, C.c_int64, vp, vp, C.c_int64, vp]
+    L.wagg_period_reduce_work_bytes.argtypes = [C.c_int64, C.c_int32, C.c_int64, C.c_int]
+    L.wagg_period_reduce_work_bytes.restype = C.c_int64
     for name in EXPORTS:
         fn = getattr(L, name)
-        if name not in ("wagg_last_error", "wagg_scratch_bytes"):
+        if name not in ("wagg_last_error", "wagg_scratch_bytes", "wagg_period_reduce_work_bytes"):
             fn.restype = C.c_int
     _lib = L
     return L

@@ -735,6 +735,80 @@ def combine_planes(stack, coefs, stream=None):
     return out
 
 
+def period_lists(row_begin, rows, T, device=None):
+    """Host row lists (CSR: ``row_begin`` of P + 1 offsets into ``rows``) checked against ``T`` rows and uploaded as the two
+    int32 CUDA tensors :func:`period_reduce` takes; ValueError for offsets that do not ascend or a row outside [0, T)."""
+    import torch
+    rb = np.ascontiguousarray(row_begin, dtype=np.int64)
+    rw = np.ascontiguousarray(rows, dtype=np.int64)
+    if rb.ndim != 1 or rw.ndim != 1 or len(rb) < 1 or rb[0] < 0 or rb[-1] > len(rw) or (np.diff(rb) < 0).any():
+        raise ValueError("row_begin must hold P + 1 ascending offsets into rows")
+    if len(rw) and (rw.min() < 0 or rw.max() >= int(T)):
+        raise ValueError("a period lists a row outside [0, %d)" % int(T))
+    dev = "cuda" if device is None else device
+    return torch.from_numpy(rb.astype(np.int32)).to(dev), torch.from_numpy(rw.astype(np.int32)).to(dev)
+
+
+def period_reduce(X, row_begin, rows, X2=None, poly=None, edd=None, keep_nan=False, checked=False, out=None, status=None, stream=None):
+    """Period totals of the rows of a (T, n) CUDA tensor (``wagg_period_reduce_*``): ``out[k, p, j] = sum_t f_k(X[t, j])`` over
+    the rows ``t`` of period ``p`` in list order, fp64 accumulation.  ``row_begin`` / ``rows``: the CSR row lists -- host
+    integers (checked here, uploaded) or the int32 CUDA tensors of :func:`period_lists` (``checked=True``: the call is then
+    asynchronous; otherwise the library checks them on the device first, which blocks).  ``poly=(offset, pow_first, n_pow)``:
+    planes ``(x + offset) ** q``; ``edd=(offset, thresholds)`` with ``X2`` = tasmax: Snyder degree days per threshold; neither:
+    one plane of plain sums.  ``keep_nan``: NaN propagates (sums of aggregated results) instead of counting 0 (S6).
+    Returns ``(out, status)``: the (planes, P, n) tensor and the one-word int32 CUDA tensor ``status`` (zeroed here unless
+    handed in), bit 0 of which the kernel sets when a transformed value was +-inf -- reading it waits for the kernel."""
+    import torch
+    X = _check_X(X, "TG")
+    T, n = int(X.shape[0]), int(X.shape[1])
+    if not (isinstance(row_begin, torch.Tensor) and isinstance(rows, torch.Tensor)):
+        row_begin, rows = period_lists(row_begin, rows, T, device=X.device)
+        checked = True
+    for a in (row_begin, rows):
+        if not (a.is_cuda and a.dtype == torch.int32 and a.dim() == 1 and a.is_contiguous()):
+            raise TypeError("row_begin and rows must be contiguous int32 CUDA tensors (or host integers)")
+    P = int(row_begin.numel()) - 1
+    if P < 0:
+        raise ValueError("row_begin must hold P + 1 offsets")
+    transform, offset, pow_first, n_pow, thr, planes = _lib.XF_NONE, 0.0, 1, 1, None, 1
+    if poly is not None and edd is not None:
+        raise ValueError("one transform per call")
+    if poly is not None:
+        transform, (offset, pow_first, n_pow) = _lib.XF_POLY, poly
+        planes = int(n_pow)
+    elif edd is not None:
+        transform, offset = _lib.XF_EDD, edd[0]
+        thr = np.ascontiguousarray(np.atleast_1d(edd[1]), dtype=np.float64)
+        planes = len(thr)
+        X2 = _check_X(X2, "TG")
+        if X2.shape != X.shape or X2.dtype != X.dtype or _ld(X2) != _ld(X):
+            raise ValueError("tasmin and tasmax must have the same shape, dtype and row stride")
+    if not 1 <= planes <= 4:
+        raise ValueError("1..4 planes per call, got %d" % planes)
+    shape = (planes, P, n)
+    if out is None:
+        out = torch.empty(shape, dtype=X.dtype, device=X.device)
+    elif tuple(out.shape) != shape or out.dtype != X.dtype or not out.is_contiguous():
+        raise ValueError("out must be a contiguous %s %s tensor" % (shape, X.dtype))
+    if status is None:
+        status = torch.zeros(1, dtype=torch.int32, device=X.device)
+    L = _lib.load()
+    wb = int(L.wagg_period_reduce_work_bytes(n, P, int(rows.numel()), planes))
+    work = torch.empty(wb // 8, dtype=torch.float64, device=X.device) if wb else None
+    fn = L.wagg_period_reduce_f32 if X.dtype == torch.float32 else L.wagg_period_reduce_f64
+    flags = (_lib.PERIOD_KEEP_NAN if keep_nan else 0) | (_lib.PERIOD_ROWS_CHECKED if checked else 0)
+    _lib.check(fn(C.c_void_p(X.data_ptr()), C.c_void_p(X2.data_ptr()) if edd is not None else None, T, n, _ld(X),
+                  C.c_void_p(row_begin.data_ptr()), C.c_void_p(rows.data_ptr()), P, int(rows.numel()), transform, float(offset),
+                  int(pow_first), int(n_pow), None if thr is None else _np_ptr(thr, C.c_double), 0 if thr is None else len(thr), flags,
+                  C.c_void_p(out.data_ptr()), max(1, n), max(1, P * n), C.c_void_p(status.data_ptr()),
+                  None if work is None else C.c_void_p(work.data_ptr()), wb, _stream_handle(stream)), "wagg_period_reduce")
+    if stream is not None:                           # scratch and lists go back to torch's allocator on return: keep them alive
+        for t in (work, row_begin, rows):            # until the kernels on the caller's stream are through with them
+            if t is not None:
+                t.record_stream(stream)
+    return out, status
+
+
 def take_axis(t, axis, index, stream=None):
     """``t`` with only the positions ``index`` (host integers) kept / re-ordered along ``axis`` (``wagg_take_axis``):
     the leap-day drop and the lon re-ordering of a device-resident field, without a torch kernel."""

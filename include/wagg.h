@@ -654,6 +654,46 @@ int wagg_plan_create_many(const int32_t *cell_idx, const int32_t *region_code, c
 int wagg_plan_many_info(const wagg_plan *plan, int *n_weights, int *n_levels, int32_t *level_R, int64_t *out_cols);
 int wagg_plan_get_den_many(const wagg_plan *plan, int weighting, int level, double *den_host /* R_level values */);
 
+/* ---- period totals: sums over the rows of a (T, n) device matrix, per period (0.6.0) ------------------------------------
+ * out[k][p][j] = sum over the rows t of period p, IN LIST ORDER, of f_k(X[t, j])  -- the degree-day measures as the
+ * reference defines them (EDD_P = sum of EDD_d over the days of P, transformations.py:17-19), annual or monthly totals of
+ * any aggregate.  The sum is linear, so it may run in front of an apply (on the field: X = the (T, G) field, n = G, f = the
+ * transform) or behind it (X = the (T, R) result, n = R, no transform, WAGG_PERIOD_KEEP_NAN).
+ *   X_dev, X2_dev   row-major (T, n), leading dimension ldx >= n; X2_dev (tasmax) only with WAGG_XF_EDD
+ *   row_begin_dev   P + 1 ascending int32 offsets into rows_dev (n_rows entries): period p owns rows_dev[row_begin[p] ..
+ *   rows_dev        row_begin[p + 1]).  Rows in any order; a row may be listed in no period (a dropped 29 February) or in
+ *                   several; an empty period totals 0
+ *   transform       WAGG_XF_NONE (one plane); WAGG_XF_POLY: (x + offset)^q, q = pow_first .. pow_first + n_pow - 1, n_pow <= 4,
+ *                   q <= 16; WAGG_XF_EDD: snyder_edd(x + offset, x2 + offset, thresholds[k]) (host array), n_thr <= 4 -- the
+ *                   device functions of the fused applies, evaluated in the element type
+ *   out_dev         plane k at out_dev + k * out_pstride, row p at + p * ldo (ldo >= n, out_pstride >= P * ldo)
+ *   status_dev      one device int32, OR-ed with 1 when a transformed value was +-inf (an inf in X, a power that overflows);
+ *                   the caller zeroes it.  Sums of +inf and -inf over DIFFERENT days of a cell differ between the two
+ *                   orders (NaN in front of an apply, per-day handling behind it): a caller who needs the daily semantics
+ *                   redoes such a call behind the apply
+ *   work_dev        optional scratch of work_bytes bytes: when n * P is too small to fill the device a period's list is cut
+ *                   into consecutive parts whose fp64 partial sums land here and are added in part order by a second launch
+ *                   (wagg_period_reduce_work_bytes says how much that takes; NULL / less: fewer parts or one)
+ *   flags           WAGG_PERIOD_KEEP_NAN: NaN propagates (for (T, R) results: a region without weight stays NaN); without
+ *                   it a NaN f_k counts 0 (S6: the NaN product leaves the numerator, its weight stays in the denominator).
+ *                   WAGG_PERIOD_ROWS_CHECKED: the caller vouches for the lists; without it they are checked on the device
+ *                   first (row_begin ascending within [0, n_rows], every row in [0, T), else WAGG_EINVAL), which BLOCKS on
+ *                   `stream`.  With it the call is asynchronous; a row index outside [0, T) is skipped, never read.
+ * fp32 and fp64 data both accumulate in fp64 and are rounded once; list order, no atomics on a sum: bit-reproducible.   */
+#define WAGG_PERIOD_KEEP_NAN 1
+#define WAGG_PERIOD_ROWS_CHECKED 2
+int wagg_period_reduce_f32(const float *X_dev, const float *X2_dev, int64_t T, int64_t n, int64_t ldx,
+                           const int32_t *row_begin_dev, const int32_t *rows_dev, int32_t P, int64_t n_rows, int transform,
+                           double offset, int pow_first, int n_pow, const double *thresholds, int n_thr, int flags,
+                           float *out_dev, int64_t ldo, int64_t out_pstride, int32_t *status_dev, void *work_dev,
+                           int64_t work_bytes, void *stream);
+int wagg_period_reduce_f64(const double *X_dev, const double *X2_dev, int64_t T, int64_t n, int64_t ldx,
+                           const int32_t *row_begin_dev, const int32_t *rows_dev, int32_t P, int64_t n_rows, int transform,
+                           double offset, int pow_first, int n_pow, const double *thresholds, int n_thr, int flags,
+                           double *out_dev, int64_t ldo, int64_t out_pstride, int32_t *status_dev, void *work_dev,
+                           int64_t work_bytes, void *stream);
+int64_t wagg_period_reduce_work_bytes(int64_t n, int32_t P, int64_t n_rows, int planes);
+
 #ifdef __cplusplus
 }
 #endif
