@@ -1,7 +1,7 @@
 """MI355X-native weighted grid->region aggregation engine: a drop-in for the aggregation path of
 ClimateImpactLab/climate_toolbox (``climate_toolbox.aggregations``).  See DESIGN.md."""
 
-__version__ = "0.1.0"
+__version__ = "0.7.0"
 
 from .aggregations import (  # noqa: F401
     weighted_aggregate_grid_to_regions,
@@ -15,6 +15,14 @@ from .aggregations import (  # noqa: F401
 )
 from .many import weighted_aggregate_grid_to_regions_many  # noqa: F401  (several weightings / levels, one pass)
 from .periods import weighted_aggregate_grid_to_regions_periods  # noqa: F401  (annual / monthly / labelled totals on the device)
+from .seasons import (  # noqa: F401  (the reference's growing-season mask as per-cell day windows, summed on the device)
+    season_boundaries,
+    season_windows,
+    get_daily_growing_season_mask,
+    SeasonMask,
+    SeasonWindows,
+    day_of_year,
+)
 from .standardize import (  # noqa: F401  (coordinate standardisation folded into the plan)
     standardize_climate_data,
     convert_lons_split,

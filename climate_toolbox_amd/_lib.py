@@ -47,6 +47,7 @@ EXPORTS = (
     "wagg_host_stats_read_sized",
     "wagg_plan_create_many", "wagg_plan_many_info", "wagg_plan_get_den_many",
     "wagg_period_reduce_f32", "wagg_period_reduce_f64", "wagg_period_reduce_work_bytes",
+    "wagg_season_reduce_f32", "wagg_season_reduce_f64", "wagg_season_reduce_work_bytes", "wagg_season_mask",
 )
 STRUCT_PLAN_INFO, STRUCT_DENSE_INFO, STRUCT_HOST_STATS, STRUCT_APPLY_DESC = 0, 1, 2, 3
 PLAN_SEGMENT, PLAN_DENSE = 0, 1
@@ -56,6 +57,7 @@ XF_NONE, XF_POLY, XF_EDD = 0, 1, 2
 APPLY_EXACT_F32 = 0x10000
 T_F32, T_F64 = 7, 8
 PERIOD_KEEP_NAN, PERIOD_ROWS_CHECKED = 1, 2      # WAGG_PERIOD_*
+SEASON_INVERT, SEASON_NULL = 1 << 20, 1 << 21    # WAGG_SEASON_*: the packed day-of-year window (bits 0-9 a, 10-19 b)
 
 
 class HostStats(C.Structure):
@@ -267,9 +269,15 @@ def load():
                                      C.c_int, f64p, C.c_int, C.c_int, vp, C.c_int64, C.c_int64, vp, vp, C.c_int64, vp]
     L.wagg_period_reduce_work_bytes.argtypes = [C.c_int64, C.c_int32, C.c_int64, C.c_int]
     L.wagg_period_reduce_work_bytes.restype = C.c_int64
+    for name in ("wagg_season_reduce_f32", "wagg_season_reduce_f64"):
+        getattr(L, name).argtypes = [vp, vp, C.c_int64, C.c_int64, C.c_int64, vp, vp, C.c_int32, C.c_int64, vp, vp, C.c_int, C.c_double,
+                                     C.c_int, C.c_int, f64p, C.c_int, C.c_int, vp, C.c_int64, C.c_int64, vp, vp, C.c_int64, vp]
+    L.wagg_season_reduce_work_bytes.argtypes = [C.c_int64, C.c_int32, C.c_int64, C.c_int]
+    L.wagg_season_reduce_work_bytes.restype = C.c_int64
+    L.wagg_season_mask.argtypes = [vp, C.c_int64, vp, C.c_int64, vp, vp]
     for name in EXPORTS:
         fn = getattr(L, name)
-        if name not in ("wagg_last_error", "wagg_scratch_bytes", "wagg_period_reduce_work_bytes"):
+        if name not in ("wagg_last_error", "wagg_scratch_bytes", "wagg_period_reduce_work_bytes", "wagg_season_reduce_work_bytes"):
             fn.restype = C.c_int
     _lib = L
     return L

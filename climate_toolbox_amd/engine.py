@@ -809,6 +809,103 @@ def period_reduce(X, row_begin, rows, X2=None, poly=None, edd=None, keep_nan=Fal
     return out, status
 
 
+def _season_vector(a, length, what, device):
+    """``a`` (host integers or an int32 CUDA tensor) as the contiguous int32 CUDA tensor of ``length`` entries the season calls take"""
+    import torch
+    if not isinstance(a, torch.Tensor):
+        h = np.ascontiguousarray(a)
+        if h.ndim != 1 or h.dtype.kind not in "iu":
+            raise TypeError("%s must be a 1-D integer array or an int32 CUDA tensor" % what)
+        if len(h) and (h.min() < np.iinfo(np.int32).min or h.max() > np.iinfo(np.int32).max):
+            raise ValueError("%s must fit int32" % what)
+        a = torch.from_numpy(h.astype(np.int32)).to(device)
+    if not (a.is_cuda and a.dtype == torch.int32 and a.dim() == 1 and a.is_contiguous()):
+        raise TypeError("%s must be a contiguous int32 CUDA tensor (or host integers)" % what)
+    if int(a.numel()) != int(length):
+        raise ValueError("%s must hold %d entries, got %d" % (what, int(length), int(a.numel())))
+    return a
+
+
+def season_reduce(X, row_begin, rows, doy, windows, X2=None, poly=None, edd=None, checked=False, out=None, status=None, stream=None):
+    """Growing-season totals of the rows of a (T, n) CUDA tensor (``wagg_season_reduce_*``): :func:`period_reduce` with one more
+    predicate -- ``out[k, p, j]`` sums ``f_k(X[t, j])`` over the rows ``t`` of period ``p`` on which cell ``j`` is in season.
+    ``doy``: the day of year of each of the T rows; ``windows``: one packed window per cell (``_lib.SEASON_*``: bits 0-9 first
+    day, 10-19 last day, bit 20 invert, bit 21 null; :func:`climate_toolbox_amd.seasons.season_windows` builds them) -- host
+    integers or int32 CUDA tensors.  Everything else as for :func:`period_reduce`, without ``keep_nan``: NaN in season counts 0
+    (S6), a value out of season is never looked at.  Returns ``(out, status)``; bit 0 of ``status``: an in-season transformed
+    value was +-inf."""
+    import torch
+    X = _check_X(X, "TG")
+    T, n = int(X.shape[0]), int(X.shape[1])
+    if not (isinstance(row_begin, torch.Tensor) and isinstance(rows, torch.Tensor)):
+        row_begin, rows = period_lists(row_begin, rows, T, device=X.device)
+        checked = True
+    for a in (row_begin, rows):
+        if not (a.is_cuda and a.dtype == torch.int32 and a.dim() == 1 and a.is_contiguous()):
+            raise TypeError("row_begin and rows must be contiguous int32 CUDA tensors (or host integers)")
+    doy = _season_vector(doy, T, "doy", X.device)
+    windows = _season_vector(windows, n, "windows", X.device)
+    P = int(row_begin.numel()) - 1
+    if P < 0:
+        raise ValueError("row_begin must hold P + 1 offsets")
+    transform, offset, pow_first, n_pow, thr, planes = _lib.XF_NONE, 0.0, 1, 1, None, 1
+    if poly is not None and edd is not None:
+        raise ValueError("one transform per call")
+    if poly is not None:
+        transform, (offset, pow_first, n_pow) = _lib.XF_POLY, poly
+        planes = int(n_pow)
+    elif edd is not None:
+        transform, offset = _lib.XF_EDD, edd[0]
+        thr = np.ascontiguousarray(np.atleast_1d(edd[1]), dtype=np.float64)
+        planes = len(thr)
+        X2 = _check_X(X2, "TG")
+        if X2.shape != X.shape or X2.dtype != X.dtype or _ld(X2) != _ld(X):
+            raise ValueError("tasmin and tasmax must have the same shape, dtype and row stride")
+    if not 1 <= planes <= 4:
+        raise ValueError("1..4 planes per call, got %d" % planes)
+    shape = (planes, P, n)
+    if out is None:
+        out = torch.empty(shape, dtype=X.dtype, device=X.device)
+    elif tuple(out.shape) != shape or out.dtype != X.dtype or not out.is_contiguous():
+        raise ValueError("out must be a contiguous %s %s tensor" % (shape, X.dtype))
+    if status is None:
+        status = torch.zeros(1, dtype=torch.int32, device=X.device)
+    L = _lib.load()
+    wb = int(L.wagg_season_reduce_work_bytes(n, P, int(rows.numel()), planes))
+    work = torch.empty(wb // 8, dtype=torch.float64, device=X.device) if wb else None
+    fn = L.wagg_season_reduce_f32 if X.dtype == torch.float32 else L.wagg_season_reduce_f64
+    _lib.check(fn(C.c_void_p(X.data_ptr()), C.c_void_p(X2.data_ptr()) if edd is not None else None, T, n, _ld(X),
+                  C.c_void_p(row_begin.data_ptr()), C.c_void_p(rows.data_ptr()), P, int(rows.numel()), C.c_void_p(doy.data_ptr()),
+                  C.c_void_p(windows.data_ptr()), transform, float(offset), int(pow_first), int(n_pow),
+                  None if thr is None else _np_ptr(thr, C.c_double), 0 if thr is None else len(thr),
+                  _lib.PERIOD_ROWS_CHECKED if checked else 0, C.c_void_p(out.data_ptr()), max(1, n), max(1, P * n),
+                  C.c_void_p(status.data_ptr()), None if work is None else C.c_void_p(work.data_ptr()), wb, _stream_handle(stream)),
+               "wagg_season_reduce")
+    if stream is not None:                           # (as in period_reduce: keep what torch's allocator would take back alive)
+        for t in (work, row_begin, rows, doy, windows):
+            if t is not None:
+                t.record_stream(stream)
+    return out, status
+
+
+def season_mask(doy, windows, stream=None):
+    """The growing-season mask itself (``wagg_season_mask``): a float64 (n, T) CUDA tensor, 1 where cell ``j`` is in season on
+    the day of year ``doy[t]``, 0 where it is not, NaN for a null window.  ``doy`` / ``windows`` as for :func:`season_reduce`."""
+    torch = require_gpu()
+    dev = next((a.device for a in (doy, windows) if isinstance(a, torch.Tensor)), "cuda")
+    doy = _season_vector(doy, len(doy), "doy", dev)
+    windows = _season_vector(windows, len(windows), "windows", dev)
+    if doy.device != windows.device:
+        raise ValueError("doy and windows must live on one device")
+    out = torch.empty((int(windows.numel()), int(doy.numel())), dtype=torch.float64, device=doy.device)
+    _lib.check(_lib.load().wagg_season_mask(C.c_void_p(doy.data_ptr()), int(doy.numel()), C.c_void_p(windows.data_ptr()),
+                                            int(windows.numel()), C.c_void_p(out.data_ptr()), _stream_handle(stream)), "wagg_season_mask")
+    if stream is not None:
+        doy.record_stream(stream)
+        windows.record_stream(stream)
+    return out
+
+
 def take_axis(t, axis, index, stream=None):
     """``t`` with only the positions ``index`` (host integers) kept / re-ordered along ``axis`` (``wagg_take_axis``):
     the leap-day drop and the lon re-ordering of a device-resident field, without a torch kernel."""

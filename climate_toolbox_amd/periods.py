@@ -119,6 +119,36 @@ def _sum_time_axis(arr, axis, lists, P, keep_dev):
     return np.moveaxis(_to_host(out), 0, axis)
 
 
+def _contract(plan, field, P, R, edd, powers, rdims, agglev, keep_dev):
+    """The (planes, P, G) period sums of a field through the leased ``plan``: the list of (P, R) results (in ``rdims`` order;
+    device tensors when ``keep_dev``), or None when a dense-family plan met +-inf."""
+    K = field.shape[0]
+    flat = field.reshape(K * P, field.shape[2])
+    out = plan.apply(flat) if isinstance(plan, DensePlan) else plan.apply(flat, layout="TG", out_layout="TR")
+    if isinstance(plan, DensePlan) and plan.saw_inf():
+        return None
+    stack = out.reshape(K, P, R)
+    if edd is not None:
+        coefs = [c for c, _ in edd[2]]
+        outs = [stack[0] if coefs == [1.0] else _engine.combine_planes(stack, coefs)]
+    elif powers is not None:
+        lo = int(min(powers))
+        outs = [stack[int(p) - lo] for p in powers]
+    else:
+        outs = [stack[0]]
+    if rdims.index("time") > rdims.index(agglev):
+        outs = [o.transpose(0, 1) for o in outs]
+    res = [o if keep_dev else _to_host(o.contiguous()) for o in outs]
+    if isinstance(plan, SparsePlan):
+        if not keep_dev:
+            plan.status()
+        else:
+            pending = getattr(_agg._TLS, "unchecked_plans", None)
+            if pending is not None and not any(p is plan for p in pending):
+                pending.append(plan)
+    return res
+
+
 def _reduce_first(ds, variable, aggwt, agglev, weights, backup_aggwt, lists, P, powers, offset, force):
     """The reduce-first route; None when this call cannot (or, unless forced, should not) take it, or met +-inf."""
     if not (isinstance(ds, _agg.ReindexedDataset) and variable in ds._src_values):
@@ -173,31 +203,11 @@ def _reduce_first(ds, variable, aggwt, agglev, weights, backup_aggwt, lists, P, 
             field, status = _engine.period_reduce(Xd, rb, rw, checked=True)
         if int(status.item()) & 1:
             return None                              # +-inf somewhere: the daily path decides what it means (S6)
-        K = field.shape[0]
-        flat = field.reshape(K * P, G)
-        out = plan.apply(flat) if isinstance(plan, DensePlan) else plan.apply(flat, layout="TG", out_layout="TR")
-        if isinstance(plan, DensePlan) and plan.saw_inf():
+        res = _contract(plan, field, P, len(uniq), edd, powers, _result_dims(dims, agglev), agglev,
+                        _agg._device_results_wanted() and _is_device_tensor(values) and not ds._was_xarray)
+        if res is None:
             return None                              # (finite days whose total overflows fp32)
-        stack = out.reshape(K, P, len(uniq))
-        if edd is not None:
-            coefs = [c for c, _ in edd[2]]
-            outs = [stack[0] if coefs == [1.0] else _engine.combine_planes(stack, coefs)]
-        elif powers is not None:
-            outs = [stack[int(p) - lo] for p in powers]
-        else:
-            outs = [stack[0]]
         rdims = _result_dims(dims, agglev)
-        if rdims.index("time") > rdims.index(agglev):
-            outs = [o.transpose(0, 1) for o in outs]
-        keep_dev = _agg._device_results_wanted() and _is_device_tensor(values) and not ds._was_xarray
-        res = [o if keep_dev else _to_host(o.contiguous()) for o in outs]
-        if isinstance(plan, SparsePlan):
-            if not keep_dev:
-                plan.status()
-            else:
-                pending = getattr(_agg._TLS, "unchecked_plans", None)
-                if pending is not None and not any(p is plan for p in pending):
-                    pending.append(plan)
     except _engine.WaggError:
         _drop_plan(plan)
         raise
@@ -209,11 +219,15 @@ def _reduce_first(ds, variable, aggwt, agglev, weights, backup_aggwt, lists, P, 
     return (res[0] if single or edd is not None else res), rdims, coords, ds._was_xarray
 
 
-def _aggregate_periods(ds, variables, aggwt, agglev, weights, backup_aggwt, period, time_values, powers=None, offset=0.0, route=None):
+def _aggregate_periods(ds, variables, aggwt, agglev, weights, backup_aggwt, period, time_values, powers=None, offset=0.0, route=None,
+                       season=None, grid=None):
     """Body of the period calls.  ``ds``: a reindexed dataset; ``variables``: the name to aggregate (``powers`` None) or the
-    result names, one per power of variable "tas".  Returns the Dataset with ``time`` replaced by ``period``."""
+    result names, one per power of variable "tas".  ``season`` (with ``grid`` = the dataset's own lat / lon labels): only
+    in-season days count (seasons.py).  Returns the Dataset with ``time`` replaced by ``period``."""
     if route not in (None, "reduce_first", "aggregate_first"):
         raise ValueError("_route must be None, 'reduce_first' or 'aggregate_first'")
+    if season is not None and route is not None:
+        raise ValueError("_route cannot be combined with season=: season totals always sum the field first")
     labels, row_begin, rows = period_rows(time_values, period)
     P = len(labels)
     variable = variables if powers is None else "tas"
@@ -226,7 +240,11 @@ def _aggregate_periods(ds, variables, aggwt, agglev, weights, backup_aggwt, peri
         return cache[key]
 
     got = None
-    if route != "aggregate_first":
+    if season is not None:
+        from . import seasons
+        got = seasons._season_totals(ds, variable, aggwt, agglev, weights, backup_aggwt, lists, P, powers, offset, season, grid,
+                                     time_values)
+    elif route != "aggregate_first":
         got = _reduce_first(ds, variable, aggwt, agglev, weights, backup_aggwt, lists, P, powers, offset, route == "reduce_first")
         if got is None and route == "reduce_first" and not _reduce_first_possible(ds, variable, powers):
             raise ValueError("reduce-first needs a (time, gridcell) field whose only other dimension is time")
@@ -264,7 +282,7 @@ def _flatten_for_device_layout(dims):
 
 
 def weighted_aggregate_grid_to_regions_periods(ds, variable, aggwt, agglev, weights, period="year", backup_aggwt="areawt",
-                                               _route=None):
+                                               _route=None, season=None):
     """``weighted_aggregate_grid_to_regions`` followed by the sum over each period's time steps, all on the device.
 
     ds, variable, aggwt, agglev, weights   as for :func:`weighted_aggregate_grid_to_regions` (``weights``: the segment table,
@@ -275,6 +293,15 @@ def weighted_aggregate_grid_to_regions_periods(ds, variable, aggwt, agglev, weig
               datetime64 time 29 February is summed like any day (``tas_poly`` has removed it from its own variables).
               Anything else raises ValueError (:func:`period_rows`).
     backup_aggwt   the weights column that stands in wherever ``aggwt`` is not > 0
+    season    None, or a growing-season mask: what :func:`climate_toolbox_amd.seasons.get_daily_growing_season_mask` or
+              :func:`~climate_toolbox_amd.seasons.season_windows` returned.  Only the days on which a cell is in season count
+              for it -- the total of ``mask * field`` aggregated daily, with a day out of season counting 0 like a NaN term
+              (its weight stays in the denominator).  The mask's grid is joined to the dataset's ``lat`` / ``lon`` by exact
+              label equality (KeyError for a dataset cell the mask lacks); the days are those of the dataset's own ``time``.
+              One route whatever the plan: the field is summed per period first (``wagg_season_reduce_*``), P rows are
+              contracted.  A (lat, lon, time) field is transposed on the device; a host-resident field is uploaded WHOLE --
+              this route does not use the quads-only host pipeline of the daily call.  A further non-time dimension, an
+              in-season +-inf (there is no daily masked route to fall back to) or ``_route=`` with it raise ValueError.
 
     Returns the single call's Dataset with ``time`` replaced by a dimension ``period`` carrying the labels; region labels,
     other coordinates and the variable name are unchanged.  Lazy variables (``tas_poly``, ``convert_kelvin_to_celsius``,
@@ -286,6 +313,8 @@ def weighted_aggregate_grid_to_regions_periods(ds, variable, aggwt, agglev, weig
 
     Dense-family plans on device-resident (time, gridcell) data sum the field first and contract P rows; everything else
     aggregates daily and sums the (T x R) result on the device (``REDUCE_FIRST_FAMILIES``; the module docstring)."""
+    if season is not None and _route is not None:
+        raise ValueError("_route cannot be combined with season=: season totals always sum the field first")
     if weights is None:
         weights = _agg.prepare_spatial_weights_data()         # TypeError, like the reference
     elif isinstance(weights, str):
@@ -293,5 +322,7 @@ def weighted_aggregate_grid_to_regions_periods(ds, variable, aggwt, agglev, weig
     if "time" not in ds.coords:
         raise ValueError("the dataset has no 'time' coordinate to form periods from")
     time_values = np.asarray(ds.coords["time"].values)
+    grid = None if season is None else (np.asarray(ds.coords["lat"].values), np.asarray(ds.coords["lon"].values))
     re = _agg._reindex_spatial_data_to_regions(ds, weights)
-    return _aggregate_periods(re, variable, aggwt, agglev, weights, backup_aggwt, period, time_values, route=_route)
+    return _aggregate_periods(re, variable, aggwt, agglev, weights, backup_aggwt, period, time_values, route=_route, season=season,
+                              grid=grid)

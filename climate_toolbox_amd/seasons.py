@@ -1,0 +1,256 @@
+"""Growing-season totals: the reference's per-cell growing-season mask (``climate_toolbox/utils/utils.py:83-153``) as one packed
+day-of-year window per grid cell, applied on the device while the field is summed over each period.
+
+Reference (read as text): climate_toolbox/utils/utils.py
+  season_boundaries(growing_days)                               :83-110
+  get_daily_growing_season_mask(lat, lon, time, growing_days)   :113-153
+
+Its users multiply the daily degree days by the (lat, lon, time) mask, aggregate to regions and sum over the year.  The daily
+masked result is linear in the field, and weights and denominators do not depend on time, so
+
+  sum_{t in p} out_masked[t, r] = sum_i w_i * S[p, cell_i] / den_r,
+  S[p, c] = sum over the days t of period p on which cell c is in season of f(x[t, c])
+
+with a NaN term counting 0 and its weight staying in the denominator (S6); a day out of season counts 0 in the same way.  ``S``
+is the reduce-first period sum of periods.py with one more predicate per cell (``wagg_season_reduce_*``,
+csrc/wagg_season.hip); the plan then contracts P rows.  The label work -- the boundaries, the windows, the join of the mask's
+grid to the dataset's -- runs here on the host, like _labels.py.
+
+The window of a cell, with ``a = ceil(min_day)`` and ``b = floor(max_day)`` (utils.py:143-149):
+  z1 (planting day) is NaN           never in season; the mask value is NaN                        (null window)
+  z2 >= z1                           in season on day d iff a <= d <= b
+  otherwise (also z2 NaN, z1 given)  in season iff NOT (a <= d <= b): the season wraps the year end and the two boundary days
+                                     themselves are out (``1 - mask``); with z2 NaN no day satisfies ``d <= NaN``: all year
+packed as include/wagg.h lays it out: bits 0-9 ``a``, 10-19 ``b`` (both clamped to 0..1023), bit 20 invert, bit 21 null; an
+interval that is empty is stored as ``a = 1, b = 0``.
+"""
+from __future__ import annotations
+
+from collections import namedtuple
+
+import numpy as np
+
+from . import aggregations as _agg, engine as _engine, minixr
+from ._labels import _exact_index
+from ._layout import _flatten_for_device, _is_device_tensor, _result_dims, _spatial_layout, _to_device
+from ._lib import SEASON_INVERT, SEASON_NULL
+from ._plans import _drop_plan, _plan_for
+from ._prepared import PreparedWeights
+
+__all__ = ["season_boundaries", "season_windows", "get_daily_growing_season_mask", "SeasonMask", "SeasonWindows", "day_of_year"]
+
+# ``windows``: int32 (latitude, longitude) packed windows; ``latitude`` / ``longitude``: the growing-days grid's labels, the
+# longitudes shifted by -180 and ascending
+SeasonWindows = namedtuple("SeasonWindows", ["windows", "latitude", "longitude"])
+
+
+def _planes(growing_days):
+    """(z1, z2, latitude, longitude): planting and harvest day as (latitude, longitude) float64 arrays, the longitudes shifted
+    by -180 and sorted (utils.py:86-89; the caller's dataset is left as it is)."""
+    if isinstance(growing_days, str):
+        from .output import read_netcdf
+        growing_days = read_netcdf(growing_days)
+    var = growing_days["variable"]
+    dims = tuple(var.dims)
+    if sorted(dims) != ["latitude", "longitude", "z"]:
+        raise ValueError("growing_days needs variable(z, latitude, longitude), got dims %r" % (dims,))
+    v = np.transpose(np.asarray(var.values, dtype=np.float64), [dims.index(d) for d in ("z", "latitude", "longitude")])
+    if "z" in growing_days.coords:
+        z = np.asarray(growing_days.coords["z"].values)
+        i1, i2 = np.flatnonzero(z == 1), np.flatnonzero(z == 2)
+        if len(i1) != 1 or len(i2) != 1:
+            raise KeyError("growing_days needs z = 1 (planting day) and z = 2 (harvest day)")
+        z1, z2 = v[i1[0]], v[i2[0]]
+    else:
+        if v.shape[0] != 2:
+            raise ValueError("growing_days needs two z planes: planting day and harvest day")
+        z1, z2 = v[0], v[1]
+    lat = np.asarray(growing_days.coords["latitude"].values)
+    lon = np.asarray(growing_days.coords["longitude"].values) - 180
+    order = np.argsort(lon, kind="stable")
+    return z1[:, order], z2[:, order], lat, lon[order]
+
+
+def season_boundaries(growing_days):
+    """Drop-in for utils.py:83-110: ``(min_day, max_day)``, the planting / harvest pair of every cell sorted elementwise (NaN
+    last, as ``np.sort`` puts it), on the growing-days grid with its longitudes shifted by -180 and sorted.  ``growing_days``:
+    a Dataset with ``variable(z, latitude, longitude)`` (z = 1 planting day, z = 2 harvest day) or the path of its file.
+    Unlike the reference this does not write the shifted longitudes back into the caller's dataset."""
+    z1, z2, lat, lon = _planes(growing_days)
+    both = np.sort(np.stack([z1, z2], axis=2), axis=2)
+    coords = {"latitude": lat, "longitude": lon}
+    return tuple(minixr.DataArray(both[:, :, k], ("latitude", "longitude"), coords=dict(coords, sort=name), name=name)
+                 for k, name in enumerate(("min", "max")))
+
+
+def season_windows(growing_days):
+    """One packed int32 window per cell of the growing-days grid (the module docstring has the rule and the packing) as a
+    :class:`SeasonWindows` ``(windows, latitude, longitude)``: what ``season=`` of the period calls takes."""
+    z1, z2, lat, lon = _planes(growing_days)
+    both = np.sort(np.stack([z1, z2], axis=2), axis=2)
+    with np.errstate(invalid="ignore"):
+        lo, hi = np.ceil(both[:, :, 0]), np.floor(both[:, :, 1])
+        null = np.isnan(z1)
+        invert = ~(z2 >= z1) & ~null                                   # (a NaN harvest day compares false: the complement)
+        empty = ~(lo <= hi) | (hi < 0) | (lo > 1023)                   # (NaN on either side: no day is inside)
+    a = np.where(empty, 1, np.clip(np.nan_to_num(lo, nan=1.0), 0, 1023)).astype(np.int32)
+    b = np.where(empty, 0, np.clip(np.nan_to_num(hi, nan=0.0), 0, 1023)).astype(np.int32)
+    win = a | (b << 10) | np.where(invert, SEASON_INVERT, 0).astype(np.int32) | np.where(null, SEASON_NULL, 0).astype(np.int32)
+    return SeasonWindows(win.astype(np.int32), lat, lon)
+
+
+def day_of_year(time_values):
+    """The day of year of every time step: the calendar day (1..366) of datetime64 values, ``v % 1000`` of the YYYYDDD
+    integers ``tas_poly`` writes (365-day calendar).  Any other dtype raises ValueError."""
+    t = np.asarray(time_values)
+    if t.dtype.kind == "M":
+        d = t.astype("datetime64[D]")
+        return ((d - d.astype("datetime64[Y]").astype("datetime64[D]")).astype(np.int64) + 1).astype(np.int32)
+    if t.dtype.kind in "iu":
+        return (t.astype(np.int64) % 1000).astype(np.int32)
+    raise ValueError("the day of year needs datetime64 or YYYYDDD integer time values, got dtype %s" % t.dtype)
+
+
+class SeasonMask:
+    """What :func:`get_daily_growing_season_mask` returns: the (lat, lon, time) growing-season mask, lazily -- the windows of
+    the growing-days grid and the day of year of every time step.  ``.values`` materialises float64 0 / 1 / NaN on the device
+    (``wagg_season_mask``); handed to a period call as ``season=`` nothing is materialised at all."""
+
+    dims = ("lat", "lon", "time")
+
+    def __init__(self, windows, time_values):
+        self.windows = windows
+        self.doy = day_of_year(time_values)
+        self.coords = {"lat": minixr.DataArray(windows.latitude, ("lat",)), "lon": minixr.DataArray(windows.longitude, ("lon",)),
+                       "time": minixr.DataArray(np.asarray(time_values), ("time",))}
+
+    @property
+    def shape(self):
+        return tuple(self.windows.windows.shape) + (len(self.doy),)
+
+    @property
+    def values(self):
+        _engine.require_gpu()
+        out = _engine.season_mask(self.doy, self.windows.windows.reshape(-1))
+        return out.cpu().numpy().reshape(self.shape)
+
+    def __array__(self, dtype=None, copy=None):
+        v = self.values
+        return v.astype(dtype) if dtype is not None else v
+
+
+def get_daily_growing_season_mask(lat, lon, time, growing_days):
+    """Drop-in for utils.py:113-153: the mask of the days inside each cell's calendar growing season, dims (lat, lon, time), as
+    a lazy :class:`SeasonMask`.  ``growing_days``: the path of the growing-days file (or the Dataset itself).  As in the
+    reference ``lat`` and ``lon`` select nothing -- the result lives on the growing-days grid, its longitudes shifted by -180
+    and sorted; ``time`` (a coordinate or an array: datetime64, or YYYYDDD integers) gives the day of year."""
+    return SeasonMask(season_windows(growing_days), np.asarray(getattr(time, "values", time)))
+
+
+# ----------------------------------------------------------------------------------------------
+# season= of the period calls
+# ----------------------------------------------------------------------------------------------
+def _as_windows(season):
+    if isinstance(season, SeasonMask):
+        return season.windows
+    if isinstance(season, SeasonWindows):
+        return season
+    raise TypeError("season must be a SeasonMask (get_daily_growing_season_mask) or the result of season_windows")
+
+
+def _stored_windows(season, lat, lon, dims, shape, lon_perm):
+    """The windows of the dataset's cells in the field's STORED cell order (the order ``_cell_index`` numbers cells in): the
+    mask's grid joined to the dataset's ``lat`` / ``lon`` labels by exact equality (KeyError for a cell the mask lacks), then
+    laid out like the buffer -- (lat, lon) or (lon, lat), column ``lon_perm[j]`` of the buffer holding longitude label j."""
+    sw = _as_windows(season)
+    ilat = _exact_index(sw.latitude, np.asarray(lat), "season latitude")
+    ilon = _exact_index(sw.longitude, np.asarray(lon), "season longitude")
+    if (len(lat), len(lon)) != (shape["lat"], shape["lon"]):
+        raise ValueError("the dataset's lat / lon coordinates do not match its field")
+    win = np.asarray(sw.windows, dtype=np.int32)[np.ix_(ilat, ilon)]
+    stored = np.empty_like(win)
+    stored[:, np.arange(len(lon)) if lon_perm is None else np.asarray(lon_perm)] = win
+    ia, io, *_ = _spatial_layout(dims)
+    return np.ascontiguousarray(stored if ia < io else stored.T).reshape(-1)
+
+
+def _season_totals(ds, variable, aggwt, agglev, weights, backup_aggwt, lists, P, powers, offset, season, grid, time_values):
+    """The one route of a ``season=`` call: sum first (``wagg_season_reduce_*``), then contract P rows on whatever plan serves
+    the table.  Returns what ``periods._reduce_first`` returns; raises where that one would fall back -- there is no daily masked
+    route to fall back to."""
+    from . import periods as _periods
+    if not (isinstance(ds, _agg.ReindexedDataset) and variable in ds._src_values):
+        raise ValueError("season= needs a gridded variable with 'lat' and 'lon' dimensions, got %r" % (variable,))
+    if P == 0:
+        raise ValueError("season= needs at least one period")
+    values, dims = ds._src_values[variable], ds._src_dims[variable]
+    *_, others = _spatial_layout(dims)
+    if [dims[i] for i in others] != ["time"]:
+        raise ValueError("season= needs a field whose only dimension besides lat / lon is time, got dims %r" % (dims,))
+    xform, edd = ds._xforms.get(variable), ds._edds.get(variable)
+    if (powers is not None or edd is not None) and xform is not None:
+        raise ValueError("variable %r already carries a lazy transform" % (variable,))
+    single = powers is None
+    if powers is None and xform is not None:
+        offset, powers = xform[0], [xform[1]]
+    if powers is not None and (max(powers) - min(powers) >= 4 or max(powers) > 16):
+        raise ValueError("season= takes powers within 1..16 that span at most four consecutive ones, got %r" % (powers,))
+    if edd is not None and len(edd[2]) > 4:
+        raise ValueError("season= takes degree-day combinations of at most four thresholds")
+    prepared = weights if isinstance(weights, PreparedWeights) else None
+    if prepared is not None:
+        prepared.check(aggwt, agglev, backup_aggwt)
+        w_eff, uniq, codes = prepared.w_eff, prepared.uniq.copy(), prepared.codes
+    else:
+        w_eff = _agg._backup_fill(weights[aggwt].values, weights[backup_aggwt].values)
+        uniq, codes = _agg._factorize_labels(np.asarray(weights[agglev].values))
+    cell_idx, G = ds._cell_index(variable)
+    if len(cell_idx) != len(w_eff):
+        raise ValueError("weights has %d rows but the dataset was reindexed with %d" % (len(w_eff), len(cell_idx)))
+    shape = dict(zip(dims, tuple(values.shape)))
+    ia, io, *_ = _spatial_layout(dims)
+    win = _stored_windows(season, grid[0], grid[1], dims, shape, ds._lon_perms.get(variable))
+    doy = day_of_year(time_values)
+    if len(doy) != shape["time"]:
+        raise ValueError("the dataset's time coordinate has %d steps, the field %d" % (len(doy), shape["time"]))
+    _engine.require_gpu()
+
+    def time_by_cell(buf):
+        """the field as a (time, gridcell) device tensor: uploaded whole if it is host-resident, transposed on the device if
+        it is stored (gridcell, time)"""
+        X2, layout, _, _ = _flatten_for_device(buf, dims)
+        Xd = _to_device(X2)
+        return Xd if layout == "TG" else _engine.relayout(Xd, [1, 0])
+
+    Xd = time_by_cell(values)
+    plan = _plan_for(cell_idx, codes, w_eff, G, len(uniq), shape["lon"] if ia < io else shape["lat"],
+                     is_f32=str(Xd.dtype).endswith("float32"), layout="TG", prepared=prepared)
+    try:
+        rb, rw = lists(Xd.device)
+        if edd is not None:
+            Hd = time_by_cell(edd[0])
+            if Hd.shape != Xd.shape or Hd.dtype != Xd.dtype:
+                raise ValueError("tasmin and tasmax must have the same shape and dtype")
+            field, status = _engine.season_reduce(Xd, rb, rw, doy, win, X2=Hd, edd=(edd[1], [e for _, e in edd[2]]), checked=True)
+        elif powers is not None:
+            lo, hi = int(min(powers)), int(max(powers))
+            field, status = _engine.season_reduce(Xd, rb, rw, doy, win, poly=(offset, lo, hi - lo + 1), checked=True)
+        else:
+            field, status = _engine.season_reduce(Xd, rb, rw, doy, win, checked=True)
+        if int(status.item()) & 1:
+            raise ValueError("season=: an in-season value of %r is +-inf (in the data, or a power that overflows); season totals "
+                             "have no daily route that could give it the daily treatment" % (variable,))
+        rdims = _result_dims(dims, agglev)
+        res = _periods._contract(plan, field, P, len(uniq), edd, powers, rdims, agglev,
+                                 _agg._device_results_wanted() and _is_device_tensor(values) and not ds._was_xarray)
+        if res is None:
+            raise ValueError("season=: the season totals of %r overflow the element type (the dense-family plan met +-inf)" % (variable,))
+    except _engine.WaggError:
+        _drop_plan(plan)
+        raise
+    finally:
+        plan._lease.release()
+    carried = ds.coords
+    coords = {d: np.asarray(carried[d].values) for d in rdims if d != agglev and d in carried and tuple(carried[d].dims) == (d,)}
+    coords[agglev] = uniq
+    return (res[0] if single or edd is not None else res), rdims, coords, ds._was_xarray

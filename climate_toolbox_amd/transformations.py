@@ -135,13 +135,20 @@ def tas_poly(ds, power, varname):
     return ds1
 
 
-def tas_poly_aggregate(ds, powers, aggwt, agglev, weights, varnames=None, backup_aggwt="areawt", period=None, _route=None):
+def tas_poly_aggregate(ds, powers, aggwt, agglev, weights, varnames=None, backup_aggwt="areawt", period=None, _route=None,
+                       season=None):
     """``tas_poly`` for several powers followed by ``weighted_aggregate_grid_to_regions`` of each --
     as ONE pass over the temperature field (powers 1..4 of fp32 (time, lat, lon) data share a single
     read of the grid from HBM).  ``varnames`` defaults to ``tas-poly-<p>``.  Returns one Dataset
     with a variable per power, dims/coords as the reference's aggregation gives them.  ``period`` ("year", "month" or
     a label per remaining day; None: daily results as ever): every power summed over each period's days on the device, ``time``
-    replaced by ``period`` (:func:`climate_toolbox_amd.periods.weighted_aggregate_grid_to_regions_periods`)."""
+    replaced by ``period`` (:func:`climate_toolbox_amd.periods.weighted_aggregate_grid_to_regions_periods`).  ``season`` (a
+    growing-season mask, seasons.py; needs ``period``): only a cell's in-season days count, the days being those of the
+    365-day calendar left after the leap-day drop."""
+    if season is not None and period is None:
+        raise ValueError("season= needs period=: a growing-season total is a sum over days")
+    if season is not None and _route is not None:
+        raise ValueError("_route cannot be combined with season=: season totals always sum the field first")
     powers = [int(p) for p in powers]
     if not powers or min(powers) < 1 or len(set(powers)) != len(powers):
         raise ValueError("powers must be distinct positive integers, got %r" % (powers,))
@@ -155,11 +162,12 @@ def tas_poly_aggregate(ds, powers, aggwt, agglev, weights, varnames=None, backup
     day = _day_index(ds)
     ds = minixr.Dataset({"tas": ds["tas"]}, coords={k: (minixr.DataArray(day, ("time",)) if k == "time" else c)
                                                   for k, c in ds.coords.items()})
+    grid = None if season is None else (np.asarray(ds.coords["lat"].values), np.asarray(ds.coords["lon"].values))
     re = _agg._reindex_spatial_data_to_regions(ds, weights)
     if period is not None:
         from . import periods
         return periods._aggregate_periods(re, varnames, aggwt, agglev, weights, backup_aggwt, period, day, powers=powers,
-                                          offset=-KELVIN, route=_route)
+                                          offset=-KELVIN, route=_route, season=season, grid=grid)
     res, rdims, coords, was_xr = _agg._aggregate_core(re, "tas", aggwt, agglev, weights, backup_aggwt,
                                                       powers=powers, offset=-KELVIN)
     return _agg._as_dataset(dict(zip(varnames, res)), rdims, coords, was_xr)

@@ -694,6 +694,35 @@ int wagg_period_reduce_f64(const double *X_dev, const double *X2_dev, int64_t T,
                            int64_t work_bytes, void *stream);
 int64_t wagg_period_reduce_work_bytes(int64_t n, int32_t P, int64_t n_rows, int planes);
 
+/* ---- growing-season totals: the period sum with a day-of-year window per cell (0.7.0) ---------------------------------------
+ * out[k][p][j] = sum over the rows t of period p, IN LIST ORDER, on which cell j is in season, of f_k(X[t, j]) -- the
+ * reference's growing-season mask (utils.py:83-153) times the daily field, summed over time in front of an apply.  The
+ * arguments are those of wagg_period_reduce_* plus
+ *   doy_dev   T int32: the day of year of every row of X (1..366); a value outside 0..1023 is in no season
+ *   win_dev   n int32: one packed window per cell.  Bits 0-9: a (first day), bits 10-19: b (last day), bit 20
+ *             (WAGG_SEASON_INVERT): the season is the complement of [a, b] (it wraps the year end; a and b themselves are then
+ *             out of season), bit 21 (WAGG_SEASON_NULL): never in season (no planting day; the mask value is NaN).  Cell j is in
+ *             season on day d iff not null and (a <= d <= b) != invert.  An empty interval is stored as a = 1, b = 0.
+ * A value out of season is selected away, never multiplied: NaN or +-inf there reaches neither a sum nor status_dev, and a
+ * piece of a row none of whose cells is in season is not read.  NaN in season counts 0 (S6); there is no keep-NaN form
+ * (flags: WAGG_PERIOD_ROWS_CHECKED only).  status_dev bit 0: an IN-SEASON transformed value was +-inf.  With every window
+ * open all year (a = 0, b = 1023) the result is bit for bit that of wagg_period_reduce_*.
+ * wagg_season_mask writes the mask itself: out_dev[j * T + t] = NaN (null window), 1 or 0 -- (n, T) row-major, fp64.          */
+#define WAGG_SEASON_INVERT (1 << 20)
+#define WAGG_SEASON_NULL (1 << 21)
+int wagg_season_reduce_f32(const float *X_dev, const float *X2_dev, int64_t T, int64_t n, int64_t ldx,
+                           const int32_t *row_begin_dev, const int32_t *rows_dev, int32_t P, int64_t n_rows,
+                           const int32_t *doy_dev, const int32_t *win_dev, int transform, double offset, int pow_first, int n_pow,
+                           const double *thresholds, int n_thr, int flags, float *out_dev, int64_t ldo, int64_t out_pstride,
+                           int32_t *status_dev, void *work_dev, int64_t work_bytes, void *stream);
+int wagg_season_reduce_f64(const double *X_dev, const double *X2_dev, int64_t T, int64_t n, int64_t ldx,
+                           const int32_t *row_begin_dev, const int32_t *rows_dev, int32_t P, int64_t n_rows,
+                           const int32_t *doy_dev, const int32_t *win_dev, int transform, double offset, int pow_first, int n_pow,
+                           const double *thresholds, int n_thr, int flags, double *out_dev, int64_t ldo, int64_t out_pstride,
+                           int32_t *status_dev, void *work_dev, int64_t work_bytes, void *stream);
+int64_t wagg_season_reduce_work_bytes(int64_t n, int32_t P, int64_t n_rows, int planes);
+int wagg_season_mask(const int32_t *doy_dev, int64_t T, const int32_t *win_dev, int64_t n, double *out_dev /* [n][T] */, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
