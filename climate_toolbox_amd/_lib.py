@@ -48,6 +48,7 @@ EXPORTS = (
     "wagg_plan_create_many", "wagg_plan_many_info", "wagg_plan_get_den_many",
     "wagg_period_reduce_f32", "wagg_period_reduce_f64", "wagg_period_reduce_work_bytes",
     "wagg_season_reduce_f32", "wagg_season_reduce_f64", "wagg_season_reduce_work_bytes", "wagg_season_mask",
+    "wagg_edd_ladder_reduce_f32", "wagg_edd_ladder_reduce_f64", "wagg_edd_ladder_work_bytes",
 )
 STRUCT_PLAN_INFO, STRUCT_DENSE_INFO, STRUCT_HOST_STATS, STRUCT_APPLY_DESC = 0, 1, 2, 3
 PLAN_SEGMENT, PLAN_DENSE = 0, 1
@@ -58,6 +59,7 @@ APPLY_EXACT_F32 = 0x10000
 T_F32, T_F64 = 7, 8
 PERIOD_KEEP_NAN, PERIOD_ROWS_CHECKED = 1, 2      # WAGG_PERIOD_*
 SEASON_INVERT, SEASON_NULL = 1 << 20, 1 << 21    # WAGG_SEASON_*: the packed day-of-year window (bits 0-9 a, 10-19 b)
+EDD_LADDER_MAX, EDD_LADDER_GROUP = 64, 8         # WAGG_EDD_LADDER_*: thresholds a call takes / the kernel's group size
 
 
 class HostStats(C.Structure):
@@ -275,9 +277,15 @@ def load():
     L.wagg_season_reduce_work_bytes.argtypes = [C.c_int64, C.c_int32, C.c_int64, C.c_int]
     L.wagg_season_reduce_work_bytes.restype = C.c_int64
     L.wagg_season_mask.argtypes = [vp, C.c_int64, vp, C.c_int64, vp, vp]
+    for name in ("wagg_edd_ladder_reduce_f32", "wagg_edd_ladder_reduce_f64"):
+        getattr(L, name).argtypes = [vp, vp, C.c_int64, C.c_int64, C.c_int64, vp, vp, C.c_int32, C.c_int64, vp, vp, C.c_double, f64p,
+                                     C.c_int, C.c_int, vp, C.c_int64, C.c_int64, vp, vp, C.c_int64, vp]
+    L.wagg_edd_ladder_work_bytes.argtypes = [C.c_int64, C.c_int32, C.c_int64, C.c_int]
+    L.wagg_edd_ladder_work_bytes.restype = C.c_int64
     for name in EXPORTS:
         fn = getattr(L, name)
-        if name not in ("wagg_last_error", "wagg_scratch_bytes", "wagg_period_reduce_work_bytes", "wagg_season_reduce_work_bytes"):
+        if name not in ("wagg_last_error", "wagg_scratch_bytes", "wagg_period_reduce_work_bytes", "wagg_season_reduce_work_bytes",
+                        "wagg_edd_ladder_work_bytes"):
             fn.restype = C.c_int
     _lib = L
     return L

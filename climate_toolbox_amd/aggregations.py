@@ -174,11 +174,11 @@ def _reindex_spatial_data_to_regions(ds, df):
     return out
 
 
-def _aggregate_core(ds, variable, aggwt, agglev, weights, backup_aggwt, powers=None, offset=0.0):
+def _aggregate_core(ds, variable, aggwt, agglev, weights, backup_aggwt, powers=None, offset=0.0, edd_planes=False):
     """Shared body of the aggregation.  ``powers=None``: aggregate ``variable`` as it is (with its
     own lazy transform, if it carries one).  ``powers=[p, ...]``: aggregate ``(x + offset) ** p``
-    for every p in ONE pass over the data.  Returns (list of result arrays, result
-    dims, coords, was_xarray)."""
+    for every p in ONE pass over the data.  ``edd_planes``: a degree-day variable's thresholds come back one
+    result each (a list) instead of combined.  Returns (list of result arrays, result dims, coords, was_xarray)."""
     prepared = weights if isinstance(weights, PreparedWeights) else None
     if prepared is not None:
         prepared.check(aggwt, agglev, backup_aggwt)
@@ -280,7 +280,7 @@ def _aggregate_core(ds, variable, aggwt, agglev, weights, backup_aggwt, powers=N
             rdims, coords = result_coords()
             return (res[0] if single else res), rdims, coords, was_xr
         if ((not _is_device_tensor(X2)) and layout == "TG" and edd is not None and isinstance(plan, SparsePlan)
-                and len(edd[2]) == 1 and edd[2][0][0] == 1.0 and len(_host_devices()) < 2):
+                and len(edd[2]) == 1 and edd[2][0][0] == 1.0 and len(_host_devices()) < 2 and not edd_planes):
             # Host-resident tasmin / tasmax, one set of degree days (snyder_edd, transformations.py:7-93, then the aggregation):
             # both fields through the row-block pipeline together (wagg_apply_edd_host_*), lines only.  (A combination of
             # several degree-day planes -- snyder_gdd -- is summed on the device: the upload-then-kernels way below.)
@@ -313,8 +313,8 @@ def _aggregate_core(ds, variable, aggwt, agglev, weights, backup_aggwt, powers=N
                         plan.apply_edd(Xd, Hd, e, offset=edd[1], out=stack[k])
                 else:
                     stack = plan.apply_edd(Xd, Hd, thr, offset=edd[1], layout=layout, out_layout=out_layout)
-                if len(coefs) == 1 and coefs[0] == 1.0:
-                    return [stack[0]]
+                if edd_planes or (len(coefs) == 1 and coefs[0] == 1.0):
+                    return list(stack) if edd_planes else [stack[0]]
                 return [_engine.combine_planes(stack, coefs)]     # wagg_combine_planes_*: sum_k coef_k * EDD_k (gdd, :138-140)
             if powers is None:
                 return [plan.apply(Xd) if isinstance(plan, DensePlan) else plan.apply(Xd, layout=layout, out_layout=out_layout)]
@@ -348,7 +348,7 @@ def _aggregate_core(ds, variable, aggwt, agglev, weights, backup_aggwt, powers=N
                 if pending is not None and not any(p is plan for p in pending):
                     pending.append(plan)
         rdims, coords = result_coords()
-        return (res[0] if single or edd is not None else res), rdims, coords, was_xr
+        return (res if edd_planes else res[0] if single or edd is not None else res), rdims, coords, was_xr
 
     plan = _plan_for(cell_idx, codes, w_eff, G, len(uniq), row_len, is_f32=is_f32, layout=layout, prepared=prepared)
     try:

@@ -1,0 +1,352 @@
+// Degree-day ladders (wagg_edd_ladder_reduce_*): out[k][p][j] = sum over the rows t of period p, in list order, on which cell j
+// is in season, of snyder_edd1(X[t, j] + off, X2[t, j] + off, thr[k]) for up to WAGG_EDD_LADDER_MAX thresholds in ONE launch --
+// the reference's agricultural product (validate_edd_snyder_agriculture, transformations.py:150-157: every refTemp of a
+// ladder, per region and growing season).  wagg_season_reduce_* / wagg_period_reduce_* take four thresholds a call; a 41-step
+// ladder costs eleven calls there, each one more pass over tasmin and tasmax.
+//
+// Shape: that of season_reduce_kernel<.., SR_EDD, ..> -- a lane owns one 16-byte piece of a row (VEC = 1 for rows that are not
+// 16-byte aligned) and walks its period's row list with EL_UNROLL loads in flight; fp64 accumulation rounded once; a NaN term
+// counts 0 (S6); an in-season +-inf sets bit 0 of the status word; a value out of season is selected away and a piece none of
+// whose cells is in season is not read; short grids cut the lists into parts (season_split's rule, copied below) that a second
+// launch adds in part order; no atomics on a sum.  With doy_dev = win_dev = NULL every listed row counts (the period sum).
+// A lane cannot hold 64 x VEC fp64 sums, so the thresholds are cut into groups of EL_G and the group is one more grid dimension
+// beside column block x period x part; every group reads its tasmin / tasmax pieces again (L2 serves what HBM served once).
+//
+// New against the four-plane kernels: snyder_edd1<float> evaluates the band expression for every value and then selects.  Here
+// a wave first asks, per threshold and row, whether ANY lane has e inside the range of its in-season cells, least tasmin to
+// greatest tasmax (one ballot; no cell with tasmin < e < tasmax escapes that); if none has, the
+// band expression is skipped and each lane takes M - e or 0 -- the value snyder_edd1 would have selected, bit for bit, so plane
+// k equals the plane wagg_season_reduce_* (or, without a season, wagg_period_reduce_* with WAGG_XF_EDD) gives for the same
+// threshold when each call gets the workspace its own *_work_bytes reports.  On a 0..40 C ladder most thresholds lie outside a
+// cell's diurnal range on a given day.  fp64 calls snyder_edd1<double>, the libm form the season kernel calls.
+//
+// EL_G = 8 thresholds a group, EL_UNROLL = 2 rows in flight.  hipcc -O3 --offload-arch=gfx950, -Rpass-analysis=kernel-resource-usage
+// (VGPRs / scratch bytes / waves per SIMD; the season kernels, the no-season ones take 2-7 registers fewer; DST does not matter):
+//   fp32 VEC = 4   122 / 0 / 4        fp32 VEC = 1   56 / 0 / 8        fp64 VEC = 2   119 / 0 / 4        fp64 VEC = 1   91 / 0 / 5
+// No AGPRs, no LDS.  EL_UNROLL = 4 (the four-plane kernels' depth) took fp32 VEC = 4 to 136 registers = 3 waves, and holding it
+// to 128 by attribute spilled 24 bytes; EL_G = 16 cannot stay under 128 at any depth (64 registers of sums alone).  From a
+// handful of thresholds on the kernel is bound by arithmetic, not by its loads -- reasoning, not measurement.
+#include "wagg_common.h"
+
+namespace wagg {
+
+constexpr int EL_G = WAGG_EDD_LADDER_GROUP;
+constexpr int EL_UNROLL = 2;
+constexpr int EL_BLOCK = 256;
+constexpr int EL_TARGET_BLOCKS = 1024;      // (= SR_TARGET_BLOCKS .. SR_MIN_ROWS_PER_PART of wagg_season.hip: the same parts)
+constexpr int EL_MAX_SPLIT = 64;
+constexpr int EL_MIN_ROWS_PER_PART = 8;
+constexpr int32_t EL_WIN_NULL = 1 << 21, EL_WIN_INVERT = 1 << 20;
+
+template <typename T> struct LadderXf {
+    T off;
+    int n_thr;
+    T thr[WAGG_EDD_LADDER_MAX];
+};
+
+struct LadderShape {
+    int64_t T, n, ldx, n_rows;
+    int32_t P, n_colblk, split, n_grp;
+};
+
+// is day-of-year d inside the packed window w?  (wagg_season.hip::in_season)
+__device__ __forceinline__ bool ladder_in_season(int32_t d, int32_t w) {
+    const int32_t a = w & 1023, b = (w >> 10) & 1023;
+    const bool inside = d >= a && d <= b;
+    return (w & EL_WIN_NULL) == 0 && (uint32_t)d <= 1023u && inside != ((w & EL_WIN_INVERT) != 0);
+}
+
+// the cells [col, col + VEC) of one row; a piece that would reach past n is read cell by cell (cells past n read 0)
+template <typename T, int VEC>
+__device__ __forceinline__ void ladder_load_piece(const T *__restrict__ row, int64_t col, int64_t n, T (&v)[VEC]) {
+    if constexpr (VEC == 1) {
+        v[0] = row[col];
+    } else {
+        typedef T vec_t __attribute__((ext_vector_type(VEC)));
+        if (col + VEC <= n) {
+            const vec_t x = *reinterpret_cast<const vec_t *>(row + col);
+#pragma unroll
+            for (int c = 0; c < VEC; ++c) v[c] = x[c];
+        } else {
+#pragma unroll
+            for (int c = 0; c < VEC; ++c) v[c] = col + c < n ? row[col + c] : T(0);
+        }
+    }
+}
+
+// what snyder_edd1<T> selects when NOT tmin < e < tmax, in snyder_edd1<T>'s own arithmetic (wagg_common.h): M - e where
+// tasmin is not below the threshold (NaN for a NaN tasmin), else 0.  The four-plane kernels form M = sum * 0.5 and M - e in two
+// instructions (M serves four thresholds there); contraction is switched off so that this does too.  (A fused sum * 0.5 - e
+// would give the same bits for every sum that is not subnormal: a product with 0.5 is exact.)
+template <typename T> __device__ __forceinline__ T snyder_edd1_outside(T tmin, T tmax, T e) {
+#pragma clang fp contract(off)
+    if constexpr (sizeof(T) == 4) {
+        const T d = 0.5f * (tmax + tmin) - e;
+        return !(tmin < e) ? d : T(0);
+    } else {
+        const T M = (tmax + tmin) / T(2);
+        return !(tmin < e) ? M - e : T(0);
+    }
+}
+
+// VEC = 4 / 2 (16-byte pieces; needs 16-byte aligned rows) or 1 (any alignment).  Grid: n_colblk x P x split x n_grp blocks,
+// flat.  SEASON = false: doy / win are not read, every valid listed row counts.  DST = T: the finished sums go to `out`;
+// DST = double: partial sums of part `s` go to `out` = the workspace [s][plane][p][j] (ldo = n, pstride = P * n), finished by
+// ladder_finish_kernel.
+template <typename T, int VEC, bool SEASON, typename DST>
+__global__ void __launch_bounds__(EL_BLOCK)
+edd_ladder_kernel(const T *__restrict__ X, const T *__restrict__ X2, LadderShape sh, const int32_t *__restrict__ row_begin,
+                  const int32_t *__restrict__ rows, const int32_t *__restrict__ doy, const int32_t *__restrict__ win, LadderXf<T> xf,
+                  DST *__restrict__ out, int64_t ldo, int64_t pstride, int32_t *__restrict__ status) {
+    const int64_t blk = blockIdx.x;
+    const int32_t cb = (int32_t)(blk % sh.n_colblk);
+    const int64_t ps = blk / sh.n_colblk;
+    const int32_t p = (int32_t)(ps % sh.P);
+    const int64_t sg = ps / sh.P;
+    const int32_t s = (int32_t)(sg % sh.split), k0 = (int32_t)(sg / sh.split) * EL_G;
+    const int kg = xf.n_thr - k0 < EL_G ? xf.n_thr - k0 : EL_G;      // thresholds of this group (>= 1 by the grid's extent)
+    const int64_t col = ((int64_t)cb * EL_BLOCK + threadIdx.x) * VEC;
+    // rows [b, e) of this block: part s of period p's list (a malformed row_begin is confined to the list's extent)
+    int64_t b = row_begin[p], e = row_begin[p + 1];
+    b = b < 0 ? 0 : (b > sh.n_rows ? sh.n_rows : b);
+    e = e < b ? b : (e > sh.n_rows ? sh.n_rows : e);
+    if (sh.split > 1) {
+        const int64_t part = (e - b + sh.split - 1) / sh.split;
+        b = b + part * s < e ? b + part * s : e;
+        e = b + part < e ? b + part : e;
+    }
+    T thr[EL_G];                                                     // (wave-uniform: scalar registers)
+#pragma unroll
+    for (int k = 0; k < EL_G; ++k) thr[k] = k < kg ? xf.thr[k0 + k] : T(0);
+    double acc[EL_G][VEC];
+#pragma unroll
+    for (int k = 0; k < EL_G; ++k)
+#pragma unroll
+        for (int c = 0; c < VEC; ++c) acc[k][c] = 0.0;
+    bool saw_inf = false;
+    if (col < sh.n) {
+        int32_t w[VEC];                                              // the lane's windows, read once (cells past n: null)
+#pragma unroll
+        for (int c = 0; c < VEC; ++c) {
+            if constexpr (SEASON) w[c] = col + c < sh.n ? win[col + c] : EL_WIN_NULL;
+            else w[c] = 0;
+        }
+        for (int64_t i = b; i < e; i += EL_UNROLL) {
+            T x[EL_UNROLL][VEC], x2[EL_UNROLL][VEC];
+            bool in[EL_UNROLL][VEC];
+#pragma unroll
+            for (int u = 0; u < EL_UNROLL; ++u) {
+                const int64_t t = i + u < e ? (int64_t)rows[i + u] : -1;
+                const bool ok = t >= 0 && t < sh.T;                  // (wave-uniform; a row index outside the field is never read)
+                int32_t d = -1;
+                if constexpr (SEASON) d = ok ? doy[t] : -1;          // (wave-uniform too: one scalar per row)
+                bool any = false;
+#pragma unroll
+                for (int c = 0; c < VEC; ++c) {
+                    if constexpr (SEASON) in[u][c] = ladder_in_season(d, w[c]);
+                    else in[u][c] = ok && col + c < sh.n;
+                    any |= in[u][c];
+                    x[u][c] = x2[u][c] = T(0);
+                }
+                if (any) {                                           // no cell of this piece in season: no load
+                    ladder_load_piece<T, VEC>(X + t * sh.ldx, col, sh.n, x[u]);
+                    ladder_load_piece<T, VEC>(X2 + t * sh.ldx, col, sh.n, x2[u]);
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < EL_UNROLL; ++u) {
+                T lo[VEC], hi[VEC];
+                // the lane's in-season cells as one range [least tasmin, greatest tasmax]: a cell whose sinusoid crosses e puts
+                // e inside it, so testing the range never misses a cell (it may ask for the band expression where no single
+                // cell needs it: the values are the same) and costs two compares a threshold instead of two a cell.  NaN
+                // compares false: it neither widens the range nor is it in any band.
+                T lane_lo = __builtin_huge_val(), lane_hi = -__builtin_huge_val();
+#pragma unroll
+                for (int c = 0; c < VEC; ++c) {
+                    lo[c] = x[u][c] + xf.off;
+                    hi[c] = x2[u][c] + xf.off;
+                    if (in[u][c] && lo[c] < lane_lo) lane_lo = lo[c];
+                    if (in[u][c] && hi[c] > lane_hi) lane_hi = hi[c];
+                }
+#pragma unroll
+                for (int k = 0; k < EL_G; ++k) {
+                    if (k >= kg) continue;
+                    const bool band = lane_lo < thr[k] && lane_hi > thr[k];      // may an in-season cell's sinusoid cross thr[k]?
+                    T f[VEC];
+                    if (__ballot(band) != 0ull) {                    // (wave-uniform branch)
+#pragma unroll
+                        for (int c = 0; c < VEC; ++c) f[c] = snyder_edd1<T>(lo[c], hi[c], thr[k]);
+                    } else {                                         // no lane of the wave needs the band expression
+#pragma unroll
+                        for (int c = 0; c < VEC; ++c) f[c] = snyder_edd1_outside<T>(lo[c], hi[c], thr[k]);
+                    }
+#pragma unroll
+                    for (int c = 0; c < VEC; ++c) {
+                        T v = in[u][c] ? f[c] : T(0);                // selected, not multiplied: nothing out of season gets further
+                        saw_inf |= __builtin_isinf(v);
+                        if (v != v) v = T(0);                        // S6: a NaN term counts 0
+                        acc[k][c] += (double)v;
+                    }
+                }
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < EL_G; ++k) {
+            if (k >= kg) continue;
+            DST *o = out + (int64_t)s * xf.n_thr * pstride + (int64_t)(k0 + k) * pstride + (int64_t)p * ldo + col;
+#pragma unroll
+            for (int c = 0; c < VEC; ++c)
+                if (col + c < sh.n) o[c] = (DST)acc[k][c];
+        }
+    }
+    if (__ballot(saw_inf) != 0ull && (threadIdx.x & 63) == 0) atomicOr(status, 1);
+}
+
+// out[k][p][j] = (T) sum_s work[s][k][p][j], s ascending  (season_finish_kernel's order)
+template <typename T>
+__global__ void ladder_finish_kernel(const double *__restrict__ work, int split, int planes, int64_t P, int64_t n, T *__restrict__ out,
+                                     int64_t ldo, int64_t pstride) {
+    const int64_t per = P * n, total = (int64_t)planes * per;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
+        double a = work[i];
+        for (int s = 1; s < split; ++s) a += work[(int64_t)s * total + i];
+        const int64_t k = i / per, r = i % per;
+        out[k * pstride + (r / n) * ldo + r % n] = (T)a;
+    }
+}
+
+// flag |= 1 unless row_begin ascends from >= 0 to <= n_rows and every listed row lies in [0, T)
+__global__ void ladder_check_kernel(const int32_t *__restrict__ row_begin, int64_t P, const int32_t *__restrict__ rows, int64_t n_rows,
+                                    int64_t T, int *__restrict__ flag) {
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    bool bad = false;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < P; i += stride)
+        bad |= row_begin[i] < 0 || row_begin[i] > row_begin[i + 1] || row_begin[i + 1] > n_rows;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_rows; i += stride)
+        bad |= rows[i] < 0 || rows[i] >= T;
+    if (__ballot(bad) != 0ull && (threadIdx.x & 63) == 0) atomicOr(flag, 1);
+}
+
+// how many consecutive parts a period's row list is cut into: season_split / period_split, to the letter -- the parts decide
+// the order of the fp64 additions, and the planes are to equal those kernels' bit for bit.  The threshold groups do not enter:
+// they multiply the blocks, but a ladder split differently from the four-plane call would add in another order.
+static int ladder_split(int64_t n, int64_t P, int64_t n_rows, int vec) {
+    const int64_t n_colblk = (n + (int64_t)EL_BLOCK * vec - 1) / ((int64_t)EL_BLOCK * vec);
+    const int64_t blocks = n_colblk * P;
+    if (blocks <= 0 || blocks >= EL_TARGET_BLOCKS) return 1;
+    int64_t want = (EL_TARGET_BLOCKS + blocks - 1) / blocks;
+    const int64_t by_rows = n_rows / P / EL_MIN_ROWS_PER_PART;
+    if (want > by_rows) want = by_rows;
+    if (want > EL_MAX_SPLIT) want = EL_MAX_SPLIT;
+    return want < 2 ? 1 : (int)want;
+}
+
+template <typename T, int VEC>
+static void launch_ladder(const T *X, const T *X2, const LadderShape &sh, const int32_t *row_begin, const int32_t *rows, const int32_t *doy,
+                          const int32_t *win, const LadderXf<T> &xf, T *out, int64_t ldo, int64_t pstride, double *work, int32_t *status,
+                          hipStream_t st) {
+    const dim3 grid((unsigned)((int64_t)sh.n_colblk * sh.P * sh.split * sh.n_grp)), block(EL_BLOCK);
+    const bool season = doy != nullptr;
+#define WAGG_EL_LAUNCH(SEASON)                                                                                                       \
+    do {                                                                                                                             \
+        if (sh.split > 1)                                                                                                            \
+            hipLaunchKernelGGL((edd_ladder_kernel<T, VEC, SEASON, double>), grid, block, 0, st, X, X2, sh, row_begin, rows, doy, win, xf, \
+                               work, sh.n, (int64_t)sh.P * sh.n, status);                                                            \
+        else                                                                                                                         \
+            hipLaunchKernelGGL((edd_ladder_kernel<T, VEC, SEASON, T>), grid, block, 0, st, X, X2, sh, row_begin, rows, doy, win, xf, out, \
+                               ldo, pstride, status);                                                                                \
+    } while (0)
+    if (season) WAGG_EL_LAUNCH(true);
+    else WAGG_EL_LAUNCH(false);
+#undef WAGG_EL_LAUNCH
+}
+
+template <typename T>
+static int ladder_reduce(const T *X, const T *X2, int64_t Ttot, int64_t n, int64_t ldx, const int32_t *row_begin, const int32_t *rows,
+                         int32_t P, int64_t n_rows, const int32_t *doy, const int32_t *win, double offset, const double *thresholds,
+                         int n_thr, int flags, T *out, int64_t ldo, int64_t pstride, int32_t *status, void *work, int64_t work_bytes,
+                         void *stream) {
+    clear_error();
+    WAGG_REQUIRE(Ttot >= 0 && n >= 0 && P >= 0 && n_rows >= 0, "negative size (T=%lld, n=%lld, P=%d, n_rows=%lld)", (long long)Ttot,
+                 (long long)n, (int)P, (long long)n_rows);
+    WAGG_REQUIRE(Ttot <= 0x7fffffff && n_rows <= 0x7fffffff, "row indices are int32: T and n_rows must stay below 2^31");
+    WAGG_REQUIRE((flags & ~WAGG_PERIOD_ROWS_CHECKED) == 0, "unknown flags 0x%x (a degree-day ladder has no keep-NaN form)", flags);
+    WAGG_REQUIRE(n_thr >= 1 && n_thr <= WAGG_EDD_LADDER_MAX, "n_thr must be 1..%d, got %d", WAGG_EDD_LADDER_MAX, n_thr);
+    WAGG_REQUIRE(thresholds != nullptr, "thresholds is NULL");
+    WAGG_REQUIRE((doy == nullptr) == (win == nullptr), "doy_dev and win_dev go together: both given, or both NULL (no season)");
+    WAGG_REQUIRE(ldx >= n && ldo >= n, "ldx / ldo smaller than n (ldx=%lld, ldo=%lld, n=%lld)", (long long)ldx, (long long)ldo, (long long)n);
+    WAGG_REQUIRE(n_thr == 1 || pstride >= (int64_t)P * ldo, "out_pstride smaller than P * ldo");
+    WAGG_REQUIRE(work_bytes >= 0 && (reinterpret_cast<uintptr_t>(work) & 7) == 0, "work_dev must be 8-byte aligned, work_bytes >= 0");
+    WAGG_REQUIRE(status != nullptr && row_begin != nullptr, "NULL pointer (status_dev / row_begin)");
+    WAGG_REQUIRE(n_rows == 0 || rows != nullptr, "NULL pointer (rows)");
+    if (P == 0 || n == 0) return WAGG_OK;
+    WAGG_REQUIRE(out != nullptr, "NULL pointer (out_dev)");
+    WAGG_REQUIRE(n_rows == 0 || Ttot == 0 || (X != nullptr && X2 != nullptr), "NULL pointer (tasmin_dev / tasmax_dev)");
+    hipStream_t st = (hipStream_t)stream;
+    if (!(flags & WAGG_PERIOD_ROWS_CHECKED)) {                   // one blocking look at the lists, as wagg_period_reduce_* takes it
+        DevBuf<int> flag;
+        int bad = 0;
+        WAGG_HIP(flag.alloc(1));
+        WAGG_HIP(hipMemsetAsync(flag.p, 0, sizeof(int), st));
+        hipLaunchKernelGGL(ladder_check_kernel, dim3(256), dim3(256), 0, st, row_begin, (int64_t)P, rows, n_rows, Ttot, flag.p);
+        WAGG_HIP(hipGetLastError());
+        WAGG_HIP(staged_d2h(&bad, flag.p, sizeof(int), st));
+        WAGG_REQUIRE(bad == 0, "row lists: row_begin must ascend within [0, n_rows] and every row index lie in [0, T)");
+    }
+    constexpr int V = 16 / (int)sizeof(T);
+    const bool wide = ldx % V == 0 && (reinterpret_cast<uintptr_t>(X) & 15) == 0 && (reinterpret_cast<uintptr_t>(X2) & 15) == 0;
+    const int vec = wide ? V : 1;
+    LadderShape sh;
+    sh.T = Ttot; sh.n = n; sh.ldx = ldx; sh.n_rows = n_rows; sh.P = P;
+    sh.n_colblk = (int32_t)((n + (int64_t)EL_BLOCK * vec - 1) / ((int64_t)EL_BLOCK * vec));
+    sh.n_grp = (n_thr + EL_G - 1) / EL_G;
+    int split = ladder_split(n, P, n_rows, vec);
+    const int64_t per_part = 8 * (int64_t)n_thr * P * n;
+    if (split > 1 && (work == nullptr || work_bytes / per_part < 2)) split = 1;
+    if (split > 1 && work_bytes / per_part < split) split = (int)(work_bytes / per_part);
+    sh.split = split;
+    WAGG_REQUIRE((int64_t)sh.n_colblk * P * split * sh.n_grp < (int64_t)0x7fffffff, "too many pieces x periods x groups for one launch");
+    LadderXf<T> xf;
+    xf.off = (T)offset; xf.n_thr = n_thr;
+    for (int k = 0; k < WAGG_EDD_LADDER_MAX; ++k) xf.thr[k] = (T)(k < n_thr ? thresholds[k] : 0.0);
+    double *w = static_cast<double *>(work);
+    if (wide) launch_ladder<T, V>(X, X2, sh, row_begin, rows, doy, win, xf, out, ldo, pstride, w, status, st);
+    else launch_ladder<T, 1>(X, X2, sh, row_begin, rows, doy, win, xf, out, ldo, pstride, w, status, st);
+    WAGG_HIP(hipGetLastError());
+    if (split > 1) {
+        const int64_t total = (int64_t)n_thr * P * n;
+        const int64_t nb = (total + 255) / 256;
+        hipLaunchKernelGGL((ladder_finish_kernel<T>), dim3((unsigned)(nb < 2048 ? nb : 2048)), dim3(256), 0, st, w, split, n_thr, (int64_t)P, n,
+                           out, ldo, pstride);
+        WAGG_HIP(hipGetLastError());
+    }
+    return WAGG_OK;
+}
+
+}  // namespace wagg
+
+extern "C" int64_t wagg_edd_ladder_work_bytes(int64_t n, int32_t P, int64_t n_rows, int n_thr) {
+    if (n <= 0 || P <= 0 || n_rows <= 0 || n_thr <= 0) return 0;
+    int s = wagg::ladder_split(n, P, n_rows, 1);                 // (the scalar path has more column blocks: never below the wide one)
+    const int s4 = wagg::ladder_split(n, P, n_rows, 4);
+    if (s4 > s) s = s4;
+    return s > 1 ? 8 * (int64_t)s * n_thr * P * n : 0;
+}
+
+extern "C" int wagg_edd_ladder_reduce_f32(const float *tasmin_dev, const float *tasmax_dev, int64_t T, int64_t n, int64_t ldx,
+                                          const int32_t *row_begin_dev, const int32_t *rows_dev, int32_t P, int64_t n_rows,
+                                          const int32_t *doy_dev, const int32_t *win_dev, double offset, const double *thresholds,
+                                          int n_thr, int flags, float *out_dev, int64_t ldo, int64_t out_pstride, int32_t *status_dev,
+                                          void *work_dev, int64_t work_bytes, void *stream) {
+    return wagg::ladder_reduce<float>(tasmin_dev, tasmax_dev, T, n, ldx, row_begin_dev, rows_dev, P, n_rows, doy_dev, win_dev, offset,
+                                      thresholds, n_thr, flags, out_dev, ldo, out_pstride, status_dev, work_dev, work_bytes, stream);
+}
+extern "C" int wagg_edd_ladder_reduce_f64(const double *tasmin_dev, const double *tasmax_dev, int64_t T, int64_t n, int64_t ldx,
+                                          const int32_t *row_begin_dev, const int32_t *rows_dev, int32_t P, int64_t n_rows,
+                                          const int32_t *doy_dev, const int32_t *win_dev, double offset, const double *thresholds,
+                                          int n_thr, int flags, double *out_dev, int64_t ldo, int64_t out_pstride, int32_t *status_dev,
+                                          void *work_dev, int64_t work_bytes, void *stream) {
+    return wagg::ladder_reduce<double>(tasmin_dev, tasmax_dev, T, n, ldx, row_begin_dev, rows_dev, P, n_rows, doy_dev, win_dev, offset,
+                                       thresholds, n_thr, flags, out_dev, ldo, out_pstride, status_dev, work_dev, work_bytes, stream);
+}

@@ -888,6 +888,63 @@ def season_reduce(X, row_begin, rows, doy, windows, X2=None, poly=None, edd=None
     return out, status
 
 
+def edd_ladder_reduce(tasmin, tasmax, row_begin, rows, offset, thresholds, doy=None, windows=None, checked=False, out=None, status=None,
+                      stream=None):
+    """Snyder degree days at every threshold of a ladder, summed per period, in ONE launch (``wagg_edd_ladder_reduce_*``):
+    ``out[k, p, j]`` sums ``snyder_edd(tasmin[t, j] + offset, tasmax[t, j] + offset, thresholds[k])`` over the rows ``t`` of
+    period ``p`` on which cell ``j`` is in season -- :func:`season_reduce` with ``edd=`` without its cap of four thresholds
+    (1 .. ``_lib.EDD_LADDER_MAX``; the kernel takes them ``EDD_LADDER_GROUP`` at a time).  ``tasmin`` / ``tasmax``: (T, n) CUDA
+    tensors of one dtype and row stride; ``row_begin`` / ``rows`` / ``doy`` / ``windows`` / ``checked`` as for
+    :func:`season_reduce`; ``doy`` and ``windows`` both None: no season, every listed row counts (:func:`period_reduce`).  Plane
+    ``k`` is bit for bit the plane those two give for ``thresholds[k]``.  Returns ``(out, status)``: the (n_thr, P, n) tensor and
+    the status word (bit 0: an in-season value was +-inf)."""
+    import torch
+    X = _check_X(tasmin, "TG")
+    X2 = _check_X(tasmax, "TG")
+    if X2.shape != X.shape or X2.dtype != X.dtype or _ld(X2) != _ld(X) or X2.device != X.device:
+        raise ValueError("tasmin and tasmax must have the same shape, dtype, row stride and device")
+    T, n = int(X.shape[0]), int(X.shape[1])
+    thr = np.ascontiguousarray(np.atleast_1d(thresholds), dtype=np.float64)
+    if thr.ndim != 1 or not 1 <= len(thr) <= _lib.EDD_LADDER_MAX:
+        raise ValueError("1..%d thresholds per call, got %s" % (_lib.EDD_LADDER_MAX, thr.shape))
+    if (doy is None) != (windows is None):
+        raise ValueError("doy and windows go together: both given, or both None (no season)")
+    if not (isinstance(row_begin, torch.Tensor) and isinstance(rows, torch.Tensor)):
+        row_begin, rows = period_lists(row_begin, rows, T, device=X.device)
+        checked = True
+    for a in (row_begin, rows):
+        if not (a.is_cuda and a.dtype == torch.int32 and a.dim() == 1 and a.is_contiguous()):
+            raise TypeError("row_begin and rows must be contiguous int32 CUDA tensors (or host integers)")
+    if doy is not None:
+        doy = _season_vector(doy, T, "doy", X.device)
+        windows = _season_vector(windows, n, "windows", X.device)
+    P = int(row_begin.numel()) - 1
+    if P < 0:
+        raise ValueError("row_begin must hold P + 1 offsets")
+    shape = (len(thr), P, n)
+    if out is None:
+        out = torch.empty(shape, dtype=X.dtype, device=X.device)
+    elif tuple(out.shape) != shape or out.dtype != X.dtype or not out.is_contiguous():
+        raise ValueError("out must be a contiguous %s %s tensor" % (shape, X.dtype))
+    if status is None:
+        status = torch.zeros(1, dtype=torch.int32, device=X.device)
+    L = _lib.load()
+    wb = int(L.wagg_edd_ladder_work_bytes(n, P, int(rows.numel()), len(thr)))
+    work = torch.empty(wb // 8, dtype=torch.float64, device=X.device) if wb else None
+    fn = L.wagg_edd_ladder_reduce_f32 if X.dtype == torch.float32 else L.wagg_edd_ladder_reduce_f64
+    _lib.check(fn(C.c_void_p(X.data_ptr()), C.c_void_p(X2.data_ptr()), T, n, _ld(X), C.c_void_p(row_begin.data_ptr()),
+                  C.c_void_p(rows.data_ptr()), P, int(rows.numel()), None if doy is None else C.c_void_p(doy.data_ptr()),
+                  None if windows is None else C.c_void_p(windows.data_ptr()), float(offset), _np_ptr(thr, C.c_double), len(thr),
+                  _lib.PERIOD_ROWS_CHECKED if checked else 0, C.c_void_p(out.data_ptr()), max(1, n), max(1, P * n),
+                  C.c_void_p(status.data_ptr()), None if work is None else C.c_void_p(work.data_ptr()), wb, _stream_handle(stream)),
+               "wagg_edd_ladder_reduce")
+    if stream is not None:                           # (as in period_reduce: keep what torch's allocator would take back alive)
+        for t in (work, row_begin, rows, doy, windows):
+            if t is not None:
+                t.record_stream(stream)
+    return out, status
+
+
 def season_mask(doy, windows, stream=None):
     """The growing-season mask itself (``wagg_season_mask``): a float64 (n, T) CUDA tensor, 1 where cell ``j`` is in season on
     the day of year ``doy[t]``, 0 where it is not, NaN for a null window.  ``doy`` / ``windows`` as for :func:`season_reduce`."""

@@ -58,6 +58,9 @@ class DataArray:
     def __len__(self):
         return self.shape[0]
 
+    def __iter__(self):
+        return iter(self.values)
+
     def isnull(self):
         v = self.values
         if v.dtype.kind == "f":

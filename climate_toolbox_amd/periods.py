@@ -119,16 +119,19 @@ def _sum_time_axis(arr, axis, lists, P, keep_dev):
     return np.moveaxis(_to_host(out), 0, axis)
 
 
-def _contract(plan, field, P, R, edd, powers, rdims, agglev, keep_dev):
+def _contract(plan, field, P, R, edd, powers, rdims, agglev, keep_dev, planes=False):
     """The (planes, P, G) period sums of a field through the leased ``plan``: the list of (P, R) results (in ``rdims`` order;
-    device tensors when ``keep_dev``), or None when a dense-family plan met +-inf."""
+    device tensors when ``keep_dev``), or None when a dense-family plan met +-inf.  ``planes``: every plane is a result of its
+    own, in order (a degree-day ladder) -- nothing is combined or picked."""
     K = field.shape[0]
     flat = field.reshape(K * P, field.shape[2])
     out = plan.apply(flat) if isinstance(plan, DensePlan) else plan.apply(flat, layout="TG", out_layout="TR")
     if isinstance(plan, DensePlan) and plan.saw_inf():
         return None
     stack = out.reshape(K, P, R)
-    if edd is not None:
+    if planes:
+        outs = list(stack)
+    elif edd is not None:
         coefs = [c for c, _ in edd[2]]
         outs = [stack[0] if coefs == [1.0] else _engine.combine_planes(stack, coefs)]
     elif powers is not None:

@@ -33,7 +33,7 @@ import numpy as np
 from . import aggregations as _agg, engine as _engine, minixr
 from ._labels import _exact_index
 from ._layout import _flatten_for_device, _is_device_tensor, _result_dims, _spatial_layout, _to_device
-from ._lib import SEASON_INVERT, SEASON_NULL
+from ._lib import EDD_LADDER_MAX as _EDD_LADDER_MAX, SEASON_INVERT, SEASON_NULL
 from ._plans import _drop_plan, _plan_for
 from ._prepared import PreparedWeights
 
@@ -174,29 +174,22 @@ def _stored_windows(season, lat, lon, dims, shape, lon_perm):
     return np.ascontiguousarray(stored if ia < io else stored.T).reshape(-1)
 
 
-def _season_totals(ds, variable, aggwt, agglev, weights, backup_aggwt, lists, P, powers, offset, season, grid, time_values):
-    """The one route of a ``season=`` call: sum first (``wagg_season_reduce_*``), then contract P rows on whatever plan serves
-    the table.  Returns what ``periods._reduce_first`` returns; raises where that one would fall back -- there is no daily masked
-    route to fall back to."""
-    from . import periods as _periods
+def _gridded_field(ds, variable, P, what):
+    """``(values, dims)`` of the (time x lat x lon) field that a sum-first call of ``what`` takes; ValueError for anything else"""
     if not (isinstance(ds, _agg.ReindexedDataset) and variable in ds._src_values):
-        raise ValueError("season= needs a gridded variable with 'lat' and 'lon' dimensions, got %r" % (variable,))
+        raise ValueError("%s needs a gridded variable with 'lat' and 'lon' dimensions, got %r" % (what, variable))
     if P == 0:
-        raise ValueError("season= needs at least one period")
+        raise ValueError("%s needs at least one period" % what)
     values, dims = ds._src_values[variable], ds._src_dims[variable]
     *_, others = _spatial_layout(dims)
     if [dims[i] for i in others] != ["time"]:
-        raise ValueError("season= needs a field whose only dimension besides lat / lon is time, got dims %r" % (dims,))
-    xform, edd = ds._xforms.get(variable), ds._edds.get(variable)
-    if (powers is not None or edd is not None) and xform is not None:
-        raise ValueError("variable %r already carries a lazy transform" % (variable,))
-    single = powers is None
-    if powers is None and xform is not None:
-        offset, powers = xform[0], [xform[1]]
-    if powers is not None and (max(powers) - min(powers) >= 4 or max(powers) > 16):
-        raise ValueError("season= takes powers within 1..16 that span at most four consecutive ones, got %r" % (powers,))
-    if edd is not None and len(edd[2]) > 4:
-        raise ValueError("season= takes degree-day combinations of at most four thresholds")
+        raise ValueError("%s needs a field whose only dimension besides lat / lon is time, got dims %r" % (what, dims))
+    return values, dims
+
+
+def _segment_table(ds, variable, aggwt, agglev, weights, backup_aggwt):
+    """``(prepared, w_eff, uniq, codes, cell_idx, G)``: the effective weight and region code of every table row, the sorted
+    region labels, and the cell every row reads"""
     prepared = weights if isinstance(weights, PreparedWeights) else None
     if prepared is not None:
         prepared.check(aggwt, agglev, backup_aggwt)
@@ -207,28 +200,61 @@ def _season_totals(ds, variable, aggwt, agglev, weights, backup_aggwt, lists, P,
     cell_idx, G = ds._cell_index(variable)
     if len(cell_idx) != len(w_eff):
         raise ValueError("weights has %d rows but the dataset was reindexed with %d" % (len(w_eff), len(cell_idx)))
-    shape = dict(zip(dims, tuple(values.shape)))
-    ia, io, *_ = _spatial_layout(dims)
+    return prepared, w_eff, uniq, codes, cell_idx, G
+
+
+def _stored_season(ds, variable, season, grid, dims, shape, time_values):
+    """``(doy, windows)`` of a ``season=`` call, the windows in the field's stored cell order"""
     win = _stored_windows(season, grid[0], grid[1], dims, shape, ds._lon_perms.get(variable))
     doy = day_of_year(time_values)
     if len(doy) != shape["time"]:
         raise ValueError("the dataset's time coordinate has %d steps, the field %d" % (len(doy), shape["time"]))
+    return doy, win
+
+
+def _time_by_cell(buf, dims):
+    """the field as a (time, gridcell) device tensor: uploaded whole if it is host-resident, transposed on the device if it is
+    stored (gridcell, time)"""
+    X2, layout, _, _ = _flatten_for_device(buf, dims)
+    Xd = _to_device(X2)
+    return Xd if layout == "TG" else _engine.relayout(Xd, [1, 0])
+
+
+def _result_coords(ds, rdims, agglev, uniq):
+    carried = ds.coords
+    coords = {d: np.asarray(carried[d].values) for d in rdims if d != agglev and d in carried and tuple(carried[d].dims) == (d,)}
+    coords[agglev] = uniq
+    return coords
+
+
+def _season_totals(ds, variable, aggwt, agglev, weights, backup_aggwt, lists, P, powers, offset, season, grid, time_values):
+    """The one route of a ``season=`` call: sum first (``wagg_season_reduce_*``), then contract P rows on whatever plan serves
+    the table.  Returns what ``periods._reduce_first`` returns; raises where that one would fall back -- there is no daily masked
+    route to fall back to."""
+    from . import periods as _periods
+    values, dims = _gridded_field(ds, variable, P, "season=")
+    xform, edd = ds._xforms.get(variable), ds._edds.get(variable)
+    if (powers is not None or edd is not None) and xform is not None:
+        raise ValueError("variable %r already carries a lazy transform" % (variable,))
+    single = powers is None
+    if powers is None and xform is not None:
+        offset, powers = xform[0], [xform[1]]
+    if powers is not None and (max(powers) - min(powers) >= 4 or max(powers) > 16):
+        raise ValueError("season= takes powers within 1..16 that span at most four consecutive ones, got %r" % (powers,))
+    if edd is not None and len(edd[2]) > 4:
+        raise ValueError("season= takes degree-day combinations of at most four thresholds")
+    prepared, w_eff, uniq, codes, cell_idx, G = _segment_table(ds, variable, aggwt, agglev, weights, backup_aggwt)
+    shape = dict(zip(dims, tuple(values.shape)))
+    ia, io, *_ = _spatial_layout(dims)
+    doy, win = _stored_season(ds, variable, season, grid, dims, shape, time_values)
     _engine.require_gpu()
-
-    def time_by_cell(buf):
-        """the field as a (time, gridcell) device tensor: uploaded whole if it is host-resident, transposed on the device if
-        it is stored (gridcell, time)"""
-        X2, layout, _, _ = _flatten_for_device(buf, dims)
-        Xd = _to_device(X2)
-        return Xd if layout == "TG" else _engine.relayout(Xd, [1, 0])
-
-    Xd = time_by_cell(values)
+    Xd = _time_by_cell(values, dims)
     plan = _plan_for(cell_idx, codes, w_eff, G, len(uniq), shape["lon"] if ia < io else shape["lat"],
                      is_f32=str(Xd.dtype).endswith("float32"), layout="TG", prepared=prepared)
     try:
         rb, rw = lists(Xd.device)
         if edd is not None:
-            Hd = time_by_cell(edd[0])
+            Hd = _time_by_cell(edd[0], dims)
             if Hd.shape != Xd.shape or Hd.dtype != Xd.dtype:
                 raise ValueError("tasmin and tasmax must have the same shape and dtype")
             field, status = _engine.season_reduce(Xd, rb, rw, doy, win, X2=Hd, edd=(edd[1], [e for _, e in edd[2]]), checked=True)
@@ -250,7 +276,50 @@ def _season_totals(ds, variable, aggwt, agglev, weights, backup_aggwt, lists, P,
         raise
     finally:
         plan._lease.release()
-    carried = ds.coords
-    coords = {d: np.asarray(carried[d].values) for d in rdims if d != agglev and d in carried and tuple(carried[d].dims) == (d,)}
-    coords[agglev] = uniq
-    return (res[0] if single or edd is not None else res), rdims, coords, ds._was_xarray
+    return (res[0] if single or edd is not None else res), rdims, _result_coords(ds, rdims, agglev, uniq), ds._was_xarray
+
+
+def _ladder_totals(ds, variable, aggwt, agglev, weights, backup_aggwt, lists, P, ladder, season, grid, time_values):
+    """Period totals of the degree days of ``variable`` (a degree-day variable; its own terms are ignored) at EVERY threshold of
+    ``ladder``: summed first (``wagg_edd_ladder_reduce_*``, up to 64 thresholds a launch), then one apply per launch contracts
+    its n_thr * P rows on whatever plan serves the table.  ``season`` None: every day counts.  Returns ``(stack, rdims, coords,
+    was_xarray)`` like :func:`_season_totals`, ``stack`` being the (n_thr, P | R, R | P) results in the ladder's order."""
+    from . import periods as _periods
+    values, dims = _gridded_field(ds, variable, P, "a degree-day ladder")
+    edd = ds._edds.get(variable)
+    if edd is None or ds._xforms.get(variable) is not None:
+        raise ValueError("a degree-day ladder needs a degree-day variable, got %r" % (variable,))
+    prepared, w_eff, uniq, codes, cell_idx, G = _segment_table(ds, variable, aggwt, agglev, weights, backup_aggwt)
+    shape = dict(zip(dims, tuple(values.shape)))
+    ia, io, *_ = _spatial_layout(dims)
+    doy, win = (None, None) if season is None else _stored_season(ds, variable, season, grid, dims, shape, time_values)
+    _engine.require_gpu()
+    Xd = _time_by_cell(values, dims)
+    plan = _plan_for(cell_idx, codes, w_eff, G, len(uniq), shape["lon"] if ia < io else shape["lat"],
+                     is_f32=str(Xd.dtype).endswith("float32"), layout="TG", prepared=prepared)
+    try:
+        rb, rw = lists(Xd.device)
+        Hd = _time_by_cell(edd[0], dims)
+        if Hd.shape != Xd.shape or Hd.dtype != Xd.dtype:
+            raise ValueError("tasmin and tasmax must have the same shape and dtype")
+        rdims = _result_dims(dims, agglev)
+        keep_dev = _agg._device_results_wanted() and _is_device_tensor(values) and not ds._was_xarray
+        res = []
+        for k0 in range(0, len(ladder), _EDD_LADDER_MAX):
+            thr = [float(e) for e in ladder[k0:k0 + _EDD_LADDER_MAX]]
+            field, status = _engine.edd_ladder_reduce(Xd, Hd, rb, rw, edd[1], thr, doy=doy, windows=win, checked=True)
+            if int(status.item()) & 1:
+                raise ValueError("degree-day ladder: a counted value of %r is +-inf; period totals of a ladder have no daily "
+                                 "route that could give it the daily treatment" % (variable,))
+            got = _periods._contract(plan, field, P, len(uniq), None, None, rdims, agglev, keep_dev, planes=True)
+            if got is None:
+                raise ValueError("degree-day ladder: the totals of %r overflow the element type (the dense-family plan met "
+                                 "+-inf)" % (variable,))
+            res.extend(got)
+    except _engine.WaggError:
+        _drop_plan(plan)
+        raise
+    finally:
+        plan._lease.release()
+    stack = _engine.require_gpu().stack(res) if keep_dev else np.stack(res)
+    return stack, rdims, _result_coords(ds, rdims, agglev, uniq), ds._was_xarray

@@ -723,6 +723,37 @@ int wagg_season_reduce_f64(const double *X_dev, const double *X2_dev, int64_t T,
 int64_t wagg_season_reduce_work_bytes(int64_t n, int32_t P, int64_t n_rows, int planes);
 int wagg_season_mask(const int32_t *doy_dev, int64_t T, const int32_t *win_dev, int64_t n, double *out_dev /* [n][T] */, void *stream);
 
+/* ---- degree-day ladders: Snyder degree days at every reference temperature in one pass (0.8.0) -----------------------------
+ * out[k][p][j] = sum over the rows t of period p, IN LIST ORDER, on which cell j is in season, of
+ * snyder_edd(tasmin[t, j] + offset, tasmax[t, j] + offset, thresholds[k]),  k = 0 .. n_thr - 1,  1 <= n_thr <= WAGG_EDD_LADDER_MAX
+ * -- wagg_season_reduce_* with WAGG_XF_EDD without its cap of four thresholds: one launch, the thresholds taken in groups of
+ * WAGG_EDD_LADDER_GROUP.  Arguments as there (tasmin_dev / tasmax_dev: row-major (T, n), one leading dimension ldx), except
+ *   doy_dev, win_dev   both NULL: no season, every listed row counts (wagg_period_reduce_* with WAGG_XF_EDD); one of them NULL
+ *                      alone is WAGG_EINVAL
+ *   thresholds         n_thr host doubles, converted to the element type
+ *   flags              WAGG_PERIOD_ROWS_CHECKED only (no keep-NaN form: a NaN term counts 0, S6)
+ *   out_dev            plane k at out_dev + k * out_pstride, row p at + p * ldo (out_pstride >= P * ldo when n_thr > 1)
+ *   work_dev           wagg_edd_ladder_work_bytes(n, P, n_rows, n_thr) bytes: n_thr / planes times what
+ *                      wagg_season_reduce_work_bytes reports for `planes` (equal to it up to four thresholds)
+ * status_dev bit 0: an in-season value was +-inf; a value out of season is never looked at.  Per threshold and row a wave
+ * evaluates the band expression only if a lane's in-season cells span the threshold (least tasmin < threshold < greatest
+ * tasmax: no cell whose sinusoid crosses it escapes that); the value is the one the four-plane kernels select.  BIT-EQUALITY: when every call gets the workspace its own *_work_bytes reports, plane k is
+ * bit for bit the plane wagg_season_reduce_* gives for thresholds[k] (in whichever group of up to four it is called there),
+ * and with doy_dev = win_dev = NULL the plane wagg_period_reduce_* gives.                                                     */
+#define WAGG_EDD_LADDER_MAX 64
+#define WAGG_EDD_LADDER_GROUP 8
+int wagg_edd_ladder_reduce_f32(const float *tasmin_dev, const float *tasmax_dev, int64_t T, int64_t n, int64_t ldx,
+                               const int32_t *row_begin_dev, const int32_t *rows_dev, int32_t P, int64_t n_rows,
+                               const int32_t *doy_dev, const int32_t *win_dev, double offset, const double *thresholds, int n_thr,
+                               int flags, float *out_dev, int64_t ldo, int64_t out_pstride, int32_t *status_dev, void *work_dev,
+                               int64_t work_bytes, void *stream);
+int wagg_edd_ladder_reduce_f64(const double *tasmin_dev, const double *tasmax_dev, int64_t T, int64_t n, int64_t ldx,
+                               const int32_t *row_begin_dev, const int32_t *rows_dev, int32_t P, int64_t n_rows,
+                               const int32_t *doy_dev, const int32_t *win_dev, double offset, const double *thresholds, int n_thr,
+                               int flags, double *out_dev, int64_t ldo, int64_t out_pstride, int32_t *status_dev, void *work_dev,
+                               int64_t work_bytes, void *stream);
+int64_t wagg_edd_ladder_work_bytes(int64_t n, int32_t P, int64_t n_rows, int n_thr);
+
 #ifdef __cplusplus
 }
 #endif
