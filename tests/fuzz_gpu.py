@@ -2,7 +2,8 @@
 """Randomised differential run of every C-ABI compute entry point against the oracle (GPU box).
 usage: python tests/fuzz_gpu.py [n_cases] [seed]      -- prints one line per failing case, exit 1 on any
 FUZZ_LINES=1: lines_case (the lines-only host path); FUZZ_MANY=1: many_case (many-plans, wagg_plan_create_many);
-FUZZ_FLAGS=1: flags_case (the kernels behind the WAGG_PLAN_NO_* flags and plans without a row length)"""
+FUZZ_FLAGS=1: flags_case (the kernels behind the WAGG_PLAN_NO_* flags and plans without a row length);
+FUZZ_FORMS=1: forms_case (dense-family plans with a forced form: full, tile-sparse, entry lists)"""
 import os, sys, traceback
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -412,6 +413,99 @@ def flags_case(i, rng, run=True):
     return tag, fails
 
 
+def forms_case(i, rng, run=True):
+    """FUZZ_FORMS=1: dense-family plans with a forced form (DensePlan.from_segments / from_csr, form="full" / "tiles" /
+    "entries"; the fp32 full form split or exact) over scattered tables with duplicate rows, negative weights, sometimes null
+    labels and NaN weights; zero-mean fields 10^u N(0, 1), u uniform in [-2, 2] per row, contiguous, one element into a wider
+    buffer or with a padded pitch; NaN or +-inf data.  Against the oracle within rtol sum |x| |w| / |den| per (t, r) (what
+    the rounding of a sum is proportional to; the split form: 4e-6 of it plus its 2^-36 floors), the second apply bit for bit
+    the first; with +-inf the MFMA forms are compared in the rows without it and must raise the note once.  A pair with a
+    negative weight is never repeated: the oracle multiplies row by row, a plan adds the rows of a pair first (S5), and +-inf
+    data times weights of both signs of one pair is NaN in the one and +-inf in the other.  The tag names the form -- [form full] / [form tiles] / [form entries].  run=False: the tag alone, from the same random stream."""
+    dtype = np.float32 if rng.random() < 0.5 else np.float64
+    rtol = 1e-4 if dtype == np.float32 else 1e-6
+    form = ["full", "tiles", "entries"][int(rng.integers(0, 3))]
+    exact = bool(rng.random() < 0.5)
+    T = int(rng.choice([1, 2, 16, 17, 63, 64, 65, 97, 127, 128, 129, 257, 369]))
+    G = int(rng.choice([1, 31, 32, 33, 127, 128, 129, 255, 256, 257, 384, 385, 640, 1000]))
+    R = int(rng.choice([1, 2, 15, 16, 17, 47, 48, 49, 255, 256, 257, 688, 689, 700]))
+    fill = float(rng.choice([0.02, 0.1, 0.4]))
+    m = rng.random((G, R)) < fill
+    if G > 64 and rng.random() < 0.7:
+        m[32:64] = False                                                             # empty tiles for the tile-sparse form
+    m[int(rng.integers(0, G)), int(rng.integers(0, R))] = True
+    cell, code = (a.astype(np.int32) for a in np.nonzero(m))
+    w = rng.uniform(0.1, 1.0, len(cell))
+    neg = rng.random(len(cell)) < 0.02
+    w[neg] *= -1.0
+    dup = rng.integers(0, len(cell), len(cell) // 7)
+    dup = dup[~neg[dup]]                                                             # (see above: negative weights stay single rows)
+    cell, code, w = np.concatenate([cell, cell[dup]]), np.concatenate([code, code[dup]]), np.concatenate([w, rng.uniform(0.1, 1.0, len(dup))])
+    perm = rng.permutation(len(cell))
+    cell, code, w = cell[perm], code[perm], w[perm]
+    if rng.random() < 0.5:
+        code[rng.random(len(code)) < 0.02] = -1
+        w[rng.random(len(w)) < 0.02] = np.nan
+    X = (10.0 ** rng.uniform(-2, 2, (T, 1)) * rng.standard_normal((T, G))).astype(dtype)
+    special = ["none", "nan", "inf"][int(rng.choice(3, p=[0.4, 0.35, 0.25]))]
+    if special == "nan":
+        X[rng.random(X.shape) < 0.01] = np.nan
+        X[int(rng.integers(0, T))] = np.nan
+    elif special == "inf":
+        X[int(rng.integers(0, T)), int(rng.integers(0, G))] = np.inf
+        X[int(rng.integers(0, T)), int(rng.integers(0, G))] = -np.inf
+    view = ["contiguous", "unaligned", "pitched"][int(rng.integers(0, 3))]
+    csr = bool(rng.random() < 0.3)
+    variant = ("exact" if exact else "split") if form == "full" and dtype == np.float32 else ""
+    tag = "forms case %d: %s T=%d G=%d R=%d nseg=%d fill=%.2f %s %s %s%s [form %s]%s" % (
+        i, dtype.__name__, T, G, R, len(cell), fill, view, special, "csr" if csr else "coo", " " + variant if variant else "", form,
+        " [split]" if variant == "split" else "")
+    if not run:
+        return tag, None
+    fails = []
+    if csr:
+        order = np.argsort(cell, kind="stable")
+        rowptr = np.concatenate([[0], np.cumsum(np.bincount(cell, minlength=G))]).astype(np.int64)
+        plan = DensePlan.from_csr(rowptr, code[order], w[order], G, R, dtype=dtype, form=form)
+    else:
+        plan = DensePlan.from_segments(cell, code, w, G, R, dtype=dtype, form=form)
+    if plan.info["form"] != {"full": 0, "tiles": 1, "entries": 2}[form]:
+        fails.append("form %d" % plan.info["form"])
+    Xd = torch.from_numpy(X).cuda()
+    if view != "contiguous":
+        c0 = 1 if view == "unaligned" else 0
+        wide = torch.full((T, (G + 8) // 4 * 4), float("nan"), dtype=Xd.dtype, device="cuda")
+        wide[:, c0:c0 + G] = Xd
+        Xd = wide[:, c0:c0 + G]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        ref = O.agg_coded(X, cell, code, w, R)
+    keep = (code >= 0) & ~np.isnan(w)
+    W = np.zeros((G, R))
+    np.add.at(W, (cell[keep], code[keep]), w[keep])
+    ax, aw = np.abs(np.where(np.isfinite(X), X, 0.0).astype(np.float64)), np.abs(W)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        if variant == "split":
+            tol = (4e-6 * (ax @ aw) + 2.0 ** -36 * ax.max(1, keepdims=True) * aw.sum(0)[None, :] +
+                   2.0 ** -36 * aw.max(0)[None, :] * ax.sum(1, keepdims=True)) / np.abs(W.sum(0))[None, :]
+        else:
+            tol = rtol * (ax @ aw) / np.abs(W.sum(0))[None, :]
+    got = plan.apply(Xd, exact=exact).cpu().numpy()
+    if not np.array_equal(plan.apply(Xd, exact=exact).cpu().numpy(), got, equal_nan=True): fails.append("the second apply differs")
+    rows = np.ones(T, dtype=bool)
+    if special == "inf" and form != "entries":
+        rows = np.isfinite(X).all(1)
+        if not plan.saw_inf(): fails.append("+-inf was not noted")
+    if plan.saw_inf(): fails.append("a note of +-inf that nothing explains")
+    g, r, tl = got[rows].astype(np.float64), ref[rows], tol[rows]
+    fin = np.isfinite(r)
+    if not np.array_equal(np.isnan(g), np.isnan(r)): fails.append("NaN pattern differs at %d places" % (np.isnan(g) != np.isnan(r)).sum())
+    elif not np.array_equal(g[~fin & ~np.isnan(r)], r[~fin & ~np.isnan(r)]): fails.append("inf values differ")
+    elif not (np.abs(g[fin] - r[fin]) <= tl[fin] + 1e-300).all():
+        fails.append("max err/tol %.3g" % (np.abs(g[fin] - r[fin]) / np.maximum(tl[fin], 1e-300)).max())
+    plan.close()
+    return tag, fails
+
+
 def main():
     global one_case
     if os.environ.get("FUZZ_LINES"):
@@ -420,6 +514,8 @@ def main():
         one_case = many_case
     if os.environ.get("FUZZ_FLAGS"):
         one_case = flags_case
+    if os.environ.get("FUZZ_FORMS"):
+        one_case = forms_case
     rng = np.random.default_rng(SEED)
     bad = 0
     for i in range(N):
