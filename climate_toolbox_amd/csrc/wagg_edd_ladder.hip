@@ -4,11 +4,9 @@
 // ladder, per region and growing season).  wagg_season_reduce_* / wagg_period_reduce_* take four thresholds a call; a 41-step
 // ladder costs eleven calls there, each one more pass over tasmin and tasmax.
 //
-// Shape: that of season_reduce_kernel<.., SR_EDD, ..> -- a lane owns one 16-byte piece of a row (VEC = 1 for rows that are not
-// 16-byte aligned) and walks its period's row list with EL_UNROLL loads in flight; fp64 accumulation rounded once; a NaN term
-// counts 0 (S6); an in-season +-inf sets bit 0 of the status word; a value out of season is selected away and a piece none of
-// whose cells is in season is not read; short grids cut the lists into parts (season_split's rule, copied below) that a second
-// launch adds in part order; no atomics on a sum.  With doy_dev = win_dev = NULL every listed row counts (the period sum).
+// The shape is the row-list family's (wagg_rowlist.h) and the season handling is season_reduce_kernel's: a NaN term counts 0
+// (S6); an in-season +-inf sets bit 0 of the status word; a value out of season is selected away and a piece none of whose
+// cells is in season is not read.  With doy_dev = win_dev = NULL every listed row counts (the period sum).
 // A lane cannot hold 64 x VEC fp64 sums, so the thresholds are cut into groups of EL_G and the group is one more grid dimension
 // beside column block x period x part; every group reads its tasmin / tasmax pieces again (L2 serves what HBM served once).
 //
@@ -26,53 +24,18 @@
 // No AGPRs, no LDS.  EL_UNROLL = 4 (the four-plane kernels' depth) took fp32 VEC = 4 to 136 registers = 3 waves, and holding it
 // to 128 by attribute spilled 24 bytes; EL_G = 16 cannot stay under 128 at any depth (64 registers of sums alone).  From a
 // handful of thresholds on the kernel is bound by arithmetic, not by its loads -- reasoning, not measurement.
-#include "wagg_common.h"
+#include "wagg_rowlist.h"
 
 namespace wagg {
 
 constexpr int EL_G = WAGG_EDD_LADDER_GROUP;
 constexpr int EL_UNROLL = 2;
-constexpr int EL_BLOCK = 256;
-constexpr int EL_TARGET_BLOCKS = 1024;      // (= SR_TARGET_BLOCKS .. SR_MIN_ROWS_PER_PART of wagg_season.hip: the same parts)
-constexpr int EL_MAX_SPLIT = 64;
-constexpr int EL_MIN_ROWS_PER_PART = 8;
-constexpr int32_t EL_WIN_NULL = 1 << 21, EL_WIN_INVERT = 1 << 20;
 
 template <typename T> struct LadderXf {
     T off;
     int n_thr;
     T thr[WAGG_EDD_LADDER_MAX];
 };
-
-struct LadderShape {
-    int64_t T, n, ldx, n_rows;
-    int32_t P, n_colblk, split, n_grp;
-};
-
-// is day-of-year d inside the packed window w?  (wagg_season.hip::in_season)
-__device__ __forceinline__ bool ladder_in_season(int32_t d, int32_t w) {
-    const int32_t a = w & 1023, b = (w >> 10) & 1023;
-    const bool inside = d >= a && d <= b;
-    return (w & EL_WIN_NULL) == 0 && (uint32_t)d <= 1023u && inside != ((w & EL_WIN_INVERT) != 0);
-}
-
-// the cells [col, col + VEC) of one row; a piece that would reach past n is read cell by cell (cells past n read 0)
-template <typename T, int VEC>
-__device__ __forceinline__ void ladder_load_piece(const T *__restrict__ row, int64_t col, int64_t n, T (&v)[VEC]) {
-    if constexpr (VEC == 1) {
-        v[0] = row[col];
-    } else {
-        typedef T vec_t __attribute__((ext_vector_type(VEC)));
-        if (col + VEC <= n) {
-            const vec_t x = *reinterpret_cast<const vec_t *>(row + col);
-#pragma unroll
-            for (int c = 0; c < VEC; ++c) v[c] = x[c];
-        } else {
-#pragma unroll
-            for (int c = 0; c < VEC; ++c) v[c] = col + c < n ? row[col + c] : T(0);
-        }
-    }
-}
 
 // what snyder_edd1<T> selects when NOT tmin < e < tmax, in snyder_edd1<T>'s own arithmetic (wagg_common.h): M - e where
 // tasmin is not below the threshold (NaN for a NaN tasmin), else 0.  The four-plane kernels form M = sum * 0.5 and M - e in two
@@ -89,32 +52,18 @@ template <typename T> __device__ __forceinline__ T snyder_edd1_outside(T tmin, T
     }
 }
 
-// VEC = 4 / 2 (16-byte pieces; needs 16-byte aligned rows) or 1 (any alignment).  Grid: n_colblk x P x split x n_grp blocks,
-// flat.  SEASON = false: doy / win are not read, every valid listed row counts.  DST = T: the finished sums go to `out`;
-// DST = double: partial sums of part `s` go to `out` = the workspace [s][plane][p][j] (ldo = n, pstride = P * n), finished by
-// ladder_finish_kernel.
+// SEASON = false: doy / win are not read, every valid listed row counts.  DST = T: the finished sums go to `out`; DST = double:
+// partial sums of part `s` go to `out` = the workspace (ldo = n, pstride = P * n), finished by rowlist_finish.
 template <typename T, int VEC, bool SEASON, typename DST>
-__global__ void __launch_bounds__(EL_BLOCK)
-edd_ladder_kernel(const T *__restrict__ X, const T *__restrict__ X2, LadderShape sh, const int32_t *__restrict__ row_begin,
+__global__ void __launch_bounds__(RL_BLOCK)
+edd_ladder_kernel(const T *__restrict__ X, const T *__restrict__ X2, RowlistShape sh, const int32_t *__restrict__ row_begin,
                   const int32_t *__restrict__ rows, const int32_t *__restrict__ doy, const int32_t *__restrict__ win, LadderXf<T> xf,
                   DST *__restrict__ out, int64_t ldo, int64_t pstride, int32_t *__restrict__ status) {
-    const int64_t blk = blockIdx.x;
-    const int32_t cb = (int32_t)(blk % sh.n_colblk);
-    const int64_t ps = blk / sh.n_colblk;
-    const int32_t p = (int32_t)(ps % sh.P);
-    const int64_t sg = ps / sh.P;
+    WAGG_ROWLIST_BLOCK(sh, cb, p, sg);
     const int32_t s = (int32_t)(sg % sh.split), k0 = (int32_t)(sg / sh.split) * EL_G;
     const int kg = xf.n_thr - k0 < EL_G ? xf.n_thr - k0 : EL_G;      // thresholds of this group (>= 1 by the grid's extent)
-    const int64_t col = ((int64_t)cb * EL_BLOCK + threadIdx.x) * VEC;
-    // rows [b, e) of this block: part s of period p's list (a malformed row_begin is confined to the list's extent)
-    int64_t b = row_begin[p], e = row_begin[p + 1];
-    b = b < 0 ? 0 : (b > sh.n_rows ? sh.n_rows : b);
-    e = e < b ? b : (e > sh.n_rows ? sh.n_rows : e);
-    if (sh.split > 1) {
-        const int64_t part = (e - b + sh.split - 1) / sh.split;
-        b = b + part * s < e ? b + part * s : e;
-        e = b + part < e ? b + part : e;
-    }
+    const int64_t col = ((int64_t)cb * RL_BLOCK + threadIdx.x) * VEC;
+    WAGG_ROWLIST_ROWS(sh, row_begin, p, s, b, e);
     T thr[EL_G];                                                     // (wave-uniform: scalar registers)
 #pragma unroll
     for (int k = 0; k < EL_G; ++k) thr[k] = k < kg ? xf.thr[k0 + k] : T(0);
@@ -128,7 +77,7 @@ edd_ladder_kernel(const T *__restrict__ X, const T *__restrict__ X2, LadderShape
         int32_t w[VEC];                                              // the lane's windows, read once (cells past n: null)
 #pragma unroll
         for (int c = 0; c < VEC; ++c) {
-            if constexpr (SEASON) w[c] = col + c < sh.n ? win[col + c] : EL_WIN_NULL;
+            if constexpr (SEASON) w[c] = col + c < sh.n ? win[col + c] : RL_WIN_NULL;
             else w[c] = 0;
         }
         for (int64_t i = b; i < e; i += EL_UNROLL) {
@@ -143,14 +92,14 @@ edd_ladder_kernel(const T *__restrict__ X, const T *__restrict__ X2, LadderShape
                 bool any = false;
 #pragma unroll
                 for (int c = 0; c < VEC; ++c) {
-                    if constexpr (SEASON) in[u][c] = ladder_in_season(d, w[c]);
+                    if constexpr (SEASON) in[u][c] = in_season(d, w[c]);
                     else in[u][c] = ok && col + c < sh.n;
                     any |= in[u][c];
                     x[u][c] = x2[u][c] = T(0);
                 }
                 if (any) {                                           // no cell of this piece in season: no load
-                    ladder_load_piece<T, VEC>(X + t * sh.ldx, col, sh.n, x[u]);
-                    ladder_load_piece<T, VEC>(X2 + t * sh.ldx, col, sh.n, x2[u]);
+                    load_piece<T, VEC>(X + t * sh.ldx, col, sh.n, x[u]);
+                    load_piece<T, VEC>(X2 + t * sh.ldx, col, sh.n, x2[u]);
                 }
             }
 #pragma unroll
@@ -202,51 +151,11 @@ edd_ladder_kernel(const T *__restrict__ X, const T *__restrict__ X2, LadderShape
     if (__ballot(saw_inf) != 0ull && (threadIdx.x & 63) == 0) atomicOr(status, 1);
 }
 
-// out[k][p][j] = (T) sum_s work[s][k][p][j], s ascending  (season_finish_kernel's order)
-template <typename T>
-__global__ void ladder_finish_kernel(const double *__restrict__ work, int split, int planes, int64_t P, int64_t n, T *__restrict__ out,
-                                     int64_t ldo, int64_t pstride) {
-    const int64_t per = P * n, total = (int64_t)planes * per;
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
-        double a = work[i];
-        for (int s = 1; s < split; ++s) a += work[(int64_t)s * total + i];
-        const int64_t k = i / per, r = i % per;
-        out[k * pstride + (r / n) * ldo + r % n] = (T)a;
-    }
-}
-
-// flag |= 1 unless row_begin ascends from >= 0 to <= n_rows and every listed row lies in [0, T)
-__global__ void ladder_check_kernel(const int32_t *__restrict__ row_begin, int64_t P, const int32_t *__restrict__ rows, int64_t n_rows,
-                                    int64_t T, int *__restrict__ flag) {
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    bool bad = false;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < P; i += stride)
-        bad |= row_begin[i] < 0 || row_begin[i] > row_begin[i + 1] || row_begin[i + 1] > n_rows;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_rows; i += stride)
-        bad |= rows[i] < 0 || rows[i] >= T;
-    if (__ballot(bad) != 0ull && (threadIdx.x & 63) == 0) atomicOr(flag, 1);
-}
-
-// how many consecutive parts a period's row list is cut into: season_split / period_split, to the letter -- the parts decide
-// the order of the fp64 additions, and the planes are to equal those kernels' bit for bit.  The threshold groups do not enter:
-// they multiply the blocks, but a ladder split differently from the four-plane call would add in another order.
-static int ladder_split(int64_t n, int64_t P, int64_t n_rows, int vec) {
-    const int64_t n_colblk = (n + (int64_t)EL_BLOCK * vec - 1) / ((int64_t)EL_BLOCK * vec);
-    const int64_t blocks = n_colblk * P;
-    if (blocks <= 0 || blocks >= EL_TARGET_BLOCKS) return 1;
-    int64_t want = (EL_TARGET_BLOCKS + blocks - 1) / blocks;
-    const int64_t by_rows = n_rows / P / EL_MIN_ROWS_PER_PART;
-    if (want > by_rows) want = by_rows;
-    if (want > EL_MAX_SPLIT) want = EL_MAX_SPLIT;
-    return want < 2 ? 1 : (int)want;
-}
-
 template <typename T, int VEC>
-static void launch_ladder(const T *X, const T *X2, const LadderShape &sh, const int32_t *row_begin, const int32_t *rows, const int32_t *doy,
+static void launch_ladder(const T *X, const T *X2, const RowlistShape &sh, const int32_t *row_begin, const int32_t *rows, const int32_t *doy,
                           const int32_t *win, const LadderXf<T> &xf, T *out, int64_t ldo, int64_t pstride, double *work, int32_t *status,
                           hipStream_t st) {
-    const dim3 grid((unsigned)((int64_t)sh.n_colblk * sh.P * sh.split * sh.n_grp)), block(EL_BLOCK);
+    const dim3 grid((unsigned)((int64_t)sh.n_colblk * sh.P * sh.split * sh.aux)), block(RL_BLOCK);
     const bool season = doy != nullptr;
 #define WAGG_EL_LAUNCH(SEASON)                                                                                                       \
     do {                                                                                                                             \
@@ -268,70 +177,37 @@ static int ladder_reduce(const T *X, const T *X2, int64_t Ttot, int64_t n, int64
                          int n_thr, int flags, T *out, int64_t ldo, int64_t pstride, int32_t *status, void *work, int64_t work_bytes,
                          void *stream) {
     clear_error();
-    WAGG_REQUIRE(Ttot >= 0 && n >= 0 && P >= 0 && n_rows >= 0, "negative size (T=%lld, n=%lld, P=%d, n_rows=%lld)", (long long)Ttot,
-                 (long long)n, (int)P, (long long)n_rows);
-    WAGG_REQUIRE(Ttot <= 0x7fffffff && n_rows <= 0x7fffffff, "row indices are int32: T and n_rows must stay below 2^31");
+    WAGG_TRY(rowlist_require_sizes(Ttot, n, P, n_rows));
     WAGG_REQUIRE((flags & ~WAGG_PERIOD_ROWS_CHECKED) == 0, "unknown flags 0x%x (a degree-day ladder has no keep-NaN form)", flags);
     WAGG_REQUIRE(n_thr >= 1 && n_thr <= WAGG_EDD_LADDER_MAX, "n_thr must be 1..%d, got %d", WAGG_EDD_LADDER_MAX, n_thr);
     WAGG_REQUIRE(thresholds != nullptr, "thresholds is NULL");
     WAGG_REQUIRE((doy == nullptr) == (win == nullptr), "doy_dev and win_dev go together: both given, or both NULL (no season)");
-    WAGG_REQUIRE(ldx >= n && ldo >= n, "ldx / ldo smaller than n (ldx=%lld, ldo=%lld, n=%lld)", (long long)ldx, (long long)ldo, (long long)n);
-    WAGG_REQUIRE(n_thr == 1 || pstride >= (int64_t)P * ldo, "out_pstride smaller than P * ldo");
-    WAGG_REQUIRE(work_bytes >= 0 && (reinterpret_cast<uintptr_t>(work) & 7) == 0, "work_dev must be 8-byte aligned, work_bytes >= 0");
-    WAGG_REQUIRE(status != nullptr && row_begin != nullptr, "NULL pointer (status_dev / row_begin)");
-    WAGG_REQUIRE(n_rows == 0 || rows != nullptr, "NULL pointer (rows)");
+    WAGG_TRY(rowlist_require_layout(n, ldx, ldo, P, n_thr, pstride, work, work_bytes, status, row_begin, rows, n_rows));
     if (P == 0 || n == 0) return WAGG_OK;
     WAGG_REQUIRE(out != nullptr, "NULL pointer (out_dev)");
     WAGG_REQUIRE(n_rows == 0 || Ttot == 0 || (X != nullptr && X2 != nullptr), "NULL pointer (tasmin_dev / tasmax_dev)");
     hipStream_t st = (hipStream_t)stream;
-    if (!(flags & WAGG_PERIOD_ROWS_CHECKED)) {                   // one blocking look at the lists, as wagg_period_reduce_* takes it
-        DevBuf<int> flag;
-        int bad = 0;
-        WAGG_HIP(flag.alloc(1));
-        WAGG_HIP(hipMemsetAsync(flag.p, 0, sizeof(int), st));
-        hipLaunchKernelGGL(ladder_check_kernel, dim3(256), dim3(256), 0, st, row_begin, (int64_t)P, rows, n_rows, Ttot, flag.p);
-        WAGG_HIP(hipGetLastError());
-        WAGG_HIP(staged_d2h(&bad, flag.p, sizeof(int), st));
-        WAGG_REQUIRE(bad == 0, "row lists: row_begin must ascend within [0, n_rows] and every row index lie in [0, T)");
-    }
-    constexpr int V = 16 / (int)sizeof(T);
-    const bool wide = ldx % V == 0 && (reinterpret_cast<uintptr_t>(X) & 15) == 0 && (reinterpret_cast<uintptr_t>(X2) & 15) == 0;
-    const int vec = wide ? V : 1;
-    LadderShape sh;
+    WAGG_TRY(rowlist_check_rows(row_begin, P, rows, n_rows, Ttot, flags, st));
+    RowlistShape sh;
     sh.T = Ttot; sh.n = n; sh.ldx = ldx; sh.n_rows = n_rows; sh.P = P;
-    sh.n_colblk = (int32_t)((n + (int64_t)EL_BLOCK * vec - 1) / ((int64_t)EL_BLOCK * vec));
-    sh.n_grp = (n_thr + EL_G - 1) / EL_G;
-    int split = ladder_split(n, P, n_rows, vec);
-    const int64_t per_part = 8 * (int64_t)n_thr * P * n;
-    if (split > 1 && (work == nullptr || work_bytes / per_part < 2)) split = 1;
-    if (split > 1 && work_bytes / per_part < split) split = (int)(work_bytes / per_part);
-    sh.split = split;
-    WAGG_REQUIRE((int64_t)sh.n_colblk * P * split * sh.n_grp < (int64_t)0x7fffffff, "too many pieces x periods x groups for one launch");
+    sh.aux = (n_thr + EL_G - 1) / EL_G;                          // threshold groups
+    bool wide;
+    WAGG_REQUIRE(rowlist_geometry(sh, wide, (int)sizeof(T), X, X2, n_thr, work, work_bytes, sh.aux),
+                 "too many pieces x periods x groups for one launch");
     LadderXf<T> xf;
     xf.off = (T)offset; xf.n_thr = n_thr;
     for (int k = 0; k < WAGG_EDD_LADDER_MAX; ++k) xf.thr[k] = (T)(k < n_thr ? thresholds[k] : 0.0);
     double *w = static_cast<double *>(work);
-    if (wide) launch_ladder<T, V>(X, X2, sh, row_begin, rows, doy, win, xf, out, ldo, pstride, w, status, st);
+    if (wide) launch_ladder<T, 16 / (int)sizeof(T)>(X, X2, sh, row_begin, rows, doy, win, xf, out, ldo, pstride, w, status, st);
     else launch_ladder<T, 1>(X, X2, sh, row_begin, rows, doy, win, xf, out, ldo, pstride, w, status, st);
     WAGG_HIP(hipGetLastError());
-    if (split > 1) {
-        const int64_t total = (int64_t)n_thr * P * n;
-        const int64_t nb = (total + 255) / 256;
-        hipLaunchKernelGGL((ladder_finish_kernel<T>), dim3((unsigned)(nb < 2048 ? nb : 2048)), dim3(256), 0, st, w, split, n_thr, (int64_t)P, n,
-                           out, ldo, pstride);
-        WAGG_HIP(hipGetLastError());
-    }
-    return WAGG_OK;
+    return rowlist_finish<T>(w, sh.split, n_thr, P, n, out, ldo, pstride, st);
 }
 
 }  // namespace wagg
 
 extern "C" int64_t wagg_edd_ladder_work_bytes(int64_t n, int32_t P, int64_t n_rows, int n_thr) {
-    if (n <= 0 || P <= 0 || n_rows <= 0 || n_thr <= 0) return 0;
-    int s = wagg::ladder_split(n, P, n_rows, 1);                 // (the scalar path has more column blocks: never below the wide one)
-    const int s4 = wagg::ladder_split(n, P, n_rows, 4);
-    if (s4 > s) s = s4;
-    return s > 1 ? 8 * (int64_t)s * n_thr * P * n : 0;
+    return wagg::rowlist_work_bytes(n, P, n_rows, n_thr);
 }
 
 extern "C" int wagg_edd_ladder_reduce_f32(const float *tasmin_dev, const float *tasmax_dev, int64_t T, int64_t n, int64_t ldx,

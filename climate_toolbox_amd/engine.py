@@ -749,66 +749,6 @@ def period_lists(row_begin, rows, T, device=None):
     return torch.from_numpy(rb.astype(np.int32)).to(dev), torch.from_numpy(rw.astype(np.int32)).to(dev)
 
 
-def period_reduce(X, row_begin, rows, X2=None, poly=None, edd=None, keep_nan=False, checked=False, out=None, status=None, stream=None):
-    """Period totals of the rows of a (T, n) CUDA tensor (``wagg_period_reduce_*``): ``out[k, p, j] = sum_t f_k(X[t, j])`` over
-    the rows ``t`` of period ``p`` in list order, fp64 accumulation.  ``row_begin`` / ``rows``: the CSR row lists -- host
-    integers (checked here, uploaded) or the int32 CUDA tensors of :func:`period_lists` (``checked=True``: the call is then
-    asynchronous; otherwise the library checks them on the device first, which blocks).  ``poly=(offset, pow_first, n_pow)``:
-    planes ``(x + offset) ** q``; ``edd=(offset, thresholds)`` with ``X2`` = tasmax: Snyder degree days per threshold; neither:
-    one plane of plain sums.  ``keep_nan``: NaN propagates (sums of aggregated results) instead of counting 0 (S6).
-    Returns ``(out, status)``: the (planes, P, n) tensor and the one-word int32 CUDA tensor ``status`` (zeroed here unless
-    handed in), bit 0 of which the kernel sets when a transformed value was +-inf -- reading it waits for the kernel."""
-    import torch
-    X = _check_X(X, "TG")
-    T, n = int(X.shape[0]), int(X.shape[1])
-    if not (isinstance(row_begin, torch.Tensor) and isinstance(rows, torch.Tensor)):
-        row_begin, rows = period_lists(row_begin, rows, T, device=X.device)
-        checked = True
-    for a in (row_begin, rows):
-        if not (a.is_cuda and a.dtype == torch.int32 and a.dim() == 1 and a.is_contiguous()):
-            raise TypeError("row_begin and rows must be contiguous int32 CUDA tensors (or host integers)")
-    P = int(row_begin.numel()) - 1
-    if P < 0:
-        raise ValueError("row_begin must hold P + 1 offsets")
-    transform, offset, pow_first, n_pow, thr, planes = _lib.XF_NONE, 0.0, 1, 1, None, 1
-    if poly is not None and edd is not None:
-        raise ValueError("one transform per call")
-    if poly is not None:
-        transform, (offset, pow_first, n_pow) = _lib.XF_POLY, poly
-        planes = int(n_pow)
-    elif edd is not None:
-        transform, offset = _lib.XF_EDD, edd[0]
-        thr = np.ascontiguousarray(np.atleast_1d(edd[1]), dtype=np.float64)
-        planes = len(thr)
-        X2 = _check_X(X2, "TG")
-        if X2.shape != X.shape or X2.dtype != X.dtype or _ld(X2) != _ld(X):
-            raise ValueError("tasmin and tasmax must have the same shape, dtype and row stride")
-    if not 1 <= planes <= 4:
-        raise ValueError("1..4 planes per call, got %d" % planes)
-    shape = (planes, P, n)
-    if out is None:
-        out = torch.empty(shape, dtype=X.dtype, device=X.device)
-    elif tuple(out.shape) != shape or out.dtype != X.dtype or not out.is_contiguous():
-        raise ValueError("out must be a contiguous %s %s tensor" % (shape, X.dtype))
-    if status is None:
-        status = torch.zeros(1, dtype=torch.int32, device=X.device)
-    L = _lib.load()
-    wb = int(L.wagg_period_reduce_work_bytes(n, P, int(rows.numel()), planes))
-    work = torch.empty(wb // 8, dtype=torch.float64, device=X.device) if wb else None
-    fn = L.wagg_period_reduce_f32 if X.dtype == torch.float32 else L.wagg_period_reduce_f64
-    flags = (_lib.PERIOD_KEEP_NAN if keep_nan else 0) | (_lib.PERIOD_ROWS_CHECKED if checked else 0)
-    _lib.check(fn(C.c_void_p(X.data_ptr()), C.c_void_p(X2.data_ptr()) if edd is not None else None, T, n, _ld(X),
-                  C.c_void_p(row_begin.data_ptr()), C.c_void_p(rows.data_ptr()), P, int(rows.numel()), transform, float(offset),
-                  int(pow_first), int(n_pow), None if thr is None else _np_ptr(thr, C.c_double), 0 if thr is None else len(thr), flags,
-                  C.c_void_p(out.data_ptr()), max(1, n), max(1, P * n), C.c_void_p(status.data_ptr()),
-                  None if work is None else C.c_void_p(work.data_ptr()), wb, _stream_handle(stream)), "wagg_period_reduce")
-    if stream is not None:                           # scratch and lists go back to torch's allocator on return: keep them alive
-        for t in (work, row_begin, rows):            # until the kernels on the caller's stream are through with them
-            if t is not None:
-                t.record_stream(stream)
-    return out, status
-
-
 def _season_vector(a, length, what, device):
     """``a`` (host integers or an int32 CUDA tensor) as the contiguous int32 CUDA tensor of ``length`` entries the season calls take"""
     import torch
@@ -826,28 +766,53 @@ def _season_vector(a, length, what, device):
     return a
 
 
-def season_reduce(X, row_begin, rows, doy, windows, X2=None, poly=None, edd=None, checked=False, out=None, status=None, stream=None):
-    """Growing-season totals of the rows of a (T, n) CUDA tensor (``wagg_season_reduce_*``): :func:`period_reduce` with one more
-    predicate -- ``out[k, p, j]`` sums ``f_k(X[t, j])`` over the rows ``t`` of period ``p`` on which cell ``j`` is in season.
-    ``doy``: the day of year of each of the T rows; ``windows``: one packed window per cell (``_lib.SEASON_*``: bits 0-9 first
-    day, 10-19 last day, bit 20 invert, bit 21 null; :func:`climate_toolbox_amd.seasons.season_windows` builds them) -- host
-    integers or int32 CUDA tensors.  Everything else as for :func:`period_reduce`, without ``keep_nan``: NaN in season counts 0
-    (S6), a value out of season is never looked at.  Returns ``(out, status)``; bit 0 of ``status``: an in-season transformed
-    value was +-inf."""
-    import torch
-    X = _check_X(X, "TG")
-    T, n = int(X.shape[0]), int(X.shape[1])
-    if not (isinstance(row_begin, torch.Tensor) and isinstance(rows, torch.Tensor)):
-        row_begin, rows = period_lists(row_begin, rows, T, device=X.device)
-        checked = True
-    for a in (row_begin, rows):
-        if not (a.is_cuda and a.dtype == torch.int32 and a.dim() == 1 and a.is_contiguous()):
-            raise TypeError("row_begin and rows must be contiguous int32 CUDA tensors (or host integers)")
-    doy = _season_vector(doy, T, "doy", X.device)
-    windows = _season_vector(windows, n, "windows", X.device)
-    P = int(row_begin.numel()) - 1
-    if P < 0:
-        raise ValueError("row_begin must hold P + 1 offsets")
+class _RowlistCall:
+    """What :func:`period_reduce`, :func:`season_reduce` and :func:`edd_ladder_reduce` do alike around their library call, in the
+    order they do it: the row lists (and, with ``season = (doy, windows)``, those two vectors) as int32 CUDA tensors and ``P``;
+    then ``out``, ``status`` and the workspace; at the end what must outlive the kernels on the caller's stream."""
+
+    def __init__(self, X, row_begin, rows, checked, season=None):
+        import torch
+        self.X, self.T, self.n = X, int(X.shape[0]), int(X.shape[1])
+        if not (isinstance(row_begin, torch.Tensor) and isinstance(rows, torch.Tensor)):
+            row_begin, rows = period_lists(row_begin, rows, self.T, device=X.device)
+            checked = True
+        for a in (row_begin, rows):
+            if not (a.is_cuda and a.dtype == torch.int32 and a.dim() == 1 and a.is_contiguous()):
+                raise TypeError("row_begin and rows must be contiguous int32 CUDA tensors (or host integers)")
+        doy = windows = None
+        if season is not None:
+            doy = _season_vector(season[0], self.T, "doy", X.device)
+            windows = _season_vector(season[1], self.n, "windows", X.device)
+        self.row_begin, self.rows, self.doy, self.windows, self.work = row_begin, rows, doy, windows, None
+        self.n_rows, self.P = int(rows.numel()), int(row_begin.numel()) - 1
+        self.flags = _lib.PERIOD_ROWS_CHECKED if checked else 0
+        if self.P < 0:
+            raise ValueError("row_begin must hold P + 1 offsets")
+
+    def alloc(self, work_bytes, planes, out, status):
+        """``(out, status, work pointer, work bytes)``; ``work_bytes``: the library's ``*_work_bytes`` for this call"""
+        import torch
+        X, shape = self.X, (planes, self.P, self.n)
+        if out is None:
+            out = torch.empty(shape, dtype=X.dtype, device=X.device)
+        elif tuple(out.shape) != shape or out.dtype != X.dtype or not out.is_contiguous():
+            raise ValueError("out must be a contiguous %s %s tensor" % (shape, X.dtype))
+        if status is None:
+            status = torch.zeros(1, dtype=torch.int32, device=X.device)
+        wb = int(work_bytes(self.n, self.P, self.n_rows, planes))
+        self.work = torch.empty(wb // 8, dtype=torch.float64, device=X.device) if wb else None
+        return out, status, None if self.work is None else C.c_void_p(self.work.data_ptr()), wb
+
+    def done(self, stream):
+        if stream is not None:                       # scratch and lists go back to torch's allocator on return: keep them alive
+            for t in (self.work, self.row_begin, self.rows, self.doy, self.windows):     # until the kernels on the caller's
+                if t is not None:                                                        # stream are through with them
+                    t.record_stream(stream)
+
+
+def _rowlist_transform(X, X2, poly, edd):
+    """``poly=`` / ``edd=`` of the four-plane calls as ``(transform, offset, pow_first, n_pow, thresholds, planes, X2)``"""
     transform, offset, pow_first, n_pow, thr, planes = _lib.XF_NONE, 0.0, 1, 1, None, 1
     if poly is not None and edd is not None:
         raise ValueError("one transform per call")
@@ -863,28 +828,56 @@ def season_reduce(X, row_begin, rows, doy, windows, X2=None, poly=None, edd=None
             raise ValueError("tasmin and tasmax must have the same shape, dtype and row stride")
     if not 1 <= planes <= 4:
         raise ValueError("1..4 planes per call, got %d" % planes)
-    shape = (planes, P, n)
-    if out is None:
-        out = torch.empty(shape, dtype=X.dtype, device=X.device)
-    elif tuple(out.shape) != shape or out.dtype != X.dtype or not out.is_contiguous():
-        raise ValueError("out must be a contiguous %s %s tensor" % (shape, X.dtype))
-    if status is None:
-        status = torch.zeros(1, dtype=torch.int32, device=X.device)
+    return transform, float(offset), int(pow_first), int(n_pow), thr, planes, X2
+
+
+def period_reduce(X, row_begin, rows, X2=None, poly=None, edd=None, keep_nan=False, checked=False, out=None, status=None, stream=None):
+    """Period totals of the rows of a (T, n) CUDA tensor (``wagg_period_reduce_*``): ``out[k, p, j] = sum_t f_k(X[t, j])`` over
+    the rows ``t`` of period ``p`` in list order, fp64 accumulation.  ``row_begin`` / ``rows``: the CSR row lists -- host
+    integers (checked here, uploaded) or the int32 CUDA tensors of :func:`period_lists` (``checked=True``: the call is then
+    asynchronous; otherwise the library checks them on the device first, which blocks).  ``poly=(offset, pow_first, n_pow)``:
+    planes ``(x + offset) ** q``; ``edd=(offset, thresholds)`` with ``X2`` = tasmax: Snyder degree days per threshold; neither:
+    one plane of plain sums.  ``keep_nan``: NaN propagates (sums of aggregated results) instead of counting 0 (S6).
+    Returns ``(out, status)``: the (planes, P, n) tensor and the one-word int32 CUDA tensor ``status`` (zeroed here unless
+    handed in), bit 0 of which the kernel sets when a transformed value was +-inf -- reading it waits for the kernel."""
+    import torch
+    X = _check_X(X, "TG")
+    c = _RowlistCall(X, row_begin, rows, checked)
+    transform, offset, pow_first, n_pow, thr, planes, X2 = _rowlist_transform(X, X2, poly, edd)
     L = _lib.load()
-    wb = int(L.wagg_season_reduce_work_bytes(n, P, int(rows.numel()), planes))
-    work = torch.empty(wb // 8, dtype=torch.float64, device=X.device) if wb else None
-    fn = L.wagg_season_reduce_f32 if X.dtype == torch.float32 else L.wagg_season_reduce_f64
-    _lib.check(fn(C.c_void_p(X.data_ptr()), C.c_void_p(X2.data_ptr()) if edd is not None else None, T, n, _ld(X),
-                  C.c_void_p(row_begin.data_ptr()), C.c_void_p(rows.data_ptr()), P, int(rows.numel()), C.c_void_p(doy.data_ptr()),
-                  C.c_void_p(windows.data_ptr()), transform, float(offset), int(pow_first), int(n_pow),
+    out, status, work, wb = c.alloc(L.wagg_period_reduce_work_bytes, planes, out, status)
+    fn = L.wagg_period_reduce_f32 if X.dtype == torch.float32 else L.wagg_period_reduce_f64
+    _lib.check(fn(C.c_void_p(X.data_ptr()), C.c_void_p(X2.data_ptr()) if edd is not None else None, c.T, c.n, _ld(X),
+                  C.c_void_p(c.row_begin.data_ptr()), C.c_void_p(c.rows.data_ptr()), c.P, c.n_rows, transform, offset, pow_first, n_pow,
                   None if thr is None else _np_ptr(thr, C.c_double), 0 if thr is None else len(thr),
-                  _lib.PERIOD_ROWS_CHECKED if checked else 0, C.c_void_p(out.data_ptr()), max(1, n), max(1, P * n),
-                  C.c_void_p(status.data_ptr()), None if work is None else C.c_void_p(work.data_ptr()), wb, _stream_handle(stream)),
-               "wagg_season_reduce")
-    if stream is not None:                           # (as in period_reduce: keep what torch's allocator would take back alive)
-        for t in (work, row_begin, rows, doy, windows):
-            if t is not None:
-                t.record_stream(stream)
+                  (_lib.PERIOD_KEEP_NAN if keep_nan else 0) | c.flags, C.c_void_p(out.data_ptr()), max(1, c.n), max(1, c.P * c.n),
+                  C.c_void_p(status.data_ptr()), work, wb, _stream_handle(stream)), "wagg_period_reduce")
+    c.done(stream)
+    return out, status
+
+
+def season_reduce(X, row_begin, rows, doy, windows, X2=None, poly=None, edd=None, checked=False, out=None, status=None, stream=None):
+    """Growing-season totals of the rows of a (T, n) CUDA tensor (``wagg_season_reduce_*``): :func:`period_reduce` with one more
+    predicate -- ``out[k, p, j]`` sums ``f_k(X[t, j])`` over the rows ``t`` of period ``p`` on which cell ``j`` is in season.
+    ``doy``: the day of year of each of the T rows; ``windows``: one packed window per cell (``_lib.SEASON_*``: bits 0-9 first
+    day, 10-19 last day, bit 20 invert, bit 21 null; :func:`climate_toolbox_amd.seasons.season_windows` builds them) -- host
+    integers or int32 CUDA tensors.  Everything else as for :func:`period_reduce`, without ``keep_nan``: NaN in season counts 0
+    (S6), a value out of season is never looked at.  Returns ``(out, status)``; bit 0 of ``status``: an in-season transformed
+    value was +-inf."""
+    import torch
+    X = _check_X(X, "TG")
+    c = _RowlistCall(X, row_begin, rows, checked, (doy, windows))
+    transform, offset, pow_first, n_pow, thr, planes, X2 = _rowlist_transform(X, X2, poly, edd)
+    L = _lib.load()
+    out, status, work, wb = c.alloc(L.wagg_season_reduce_work_bytes, planes, out, status)
+    fn = L.wagg_season_reduce_f32 if X.dtype == torch.float32 else L.wagg_season_reduce_f64
+    _lib.check(fn(C.c_void_p(X.data_ptr()), C.c_void_p(X2.data_ptr()) if edd is not None else None, c.T, c.n, _ld(X),
+                  C.c_void_p(c.row_begin.data_ptr()), C.c_void_p(c.rows.data_ptr()), c.P, c.n_rows, C.c_void_p(c.doy.data_ptr()),
+                  C.c_void_p(c.windows.data_ptr()), transform, offset, pow_first, n_pow,
+                  None if thr is None else _np_ptr(thr, C.c_double), 0 if thr is None else len(thr), c.flags,
+                  C.c_void_p(out.data_ptr()), max(1, c.n), max(1, c.P * c.n), C.c_void_p(status.data_ptr()), work, wb,
+                  _stream_handle(stream)), "wagg_season_reduce")
+    c.done(stream)
     return out, status
 
 
@@ -903,45 +896,21 @@ def edd_ladder_reduce(tasmin, tasmax, row_begin, rows, offset, thresholds, doy=N
     X2 = _check_X(tasmax, "TG")
     if X2.shape != X.shape or X2.dtype != X.dtype or _ld(X2) != _ld(X) or X2.device != X.device:
         raise ValueError("tasmin and tasmax must have the same shape, dtype, row stride and device")
-    T, n = int(X.shape[0]), int(X.shape[1])
     thr = np.ascontiguousarray(np.atleast_1d(thresholds), dtype=np.float64)
     if thr.ndim != 1 or not 1 <= len(thr) <= _lib.EDD_LADDER_MAX:
         raise ValueError("1..%d thresholds per call, got %s" % (_lib.EDD_LADDER_MAX, thr.shape))
     if (doy is None) != (windows is None):
         raise ValueError("doy and windows go together: both given, or both None (no season)")
-    if not (isinstance(row_begin, torch.Tensor) and isinstance(rows, torch.Tensor)):
-        row_begin, rows = period_lists(row_begin, rows, T, device=X.device)
-        checked = True
-    for a in (row_begin, rows):
-        if not (a.is_cuda and a.dtype == torch.int32 and a.dim() == 1 and a.is_contiguous()):
-            raise TypeError("row_begin and rows must be contiguous int32 CUDA tensors (or host integers)")
-    if doy is not None:
-        doy = _season_vector(doy, T, "doy", X.device)
-        windows = _season_vector(windows, n, "windows", X.device)
-    P = int(row_begin.numel()) - 1
-    if P < 0:
-        raise ValueError("row_begin must hold P + 1 offsets")
-    shape = (len(thr), P, n)
-    if out is None:
-        out = torch.empty(shape, dtype=X.dtype, device=X.device)
-    elif tuple(out.shape) != shape or out.dtype != X.dtype or not out.is_contiguous():
-        raise ValueError("out must be a contiguous %s %s tensor" % (shape, X.dtype))
-    if status is None:
-        status = torch.zeros(1, dtype=torch.int32, device=X.device)
+    c = _RowlistCall(X, row_begin, rows, checked, None if doy is None else (doy, windows))
     L = _lib.load()
-    wb = int(L.wagg_edd_ladder_work_bytes(n, P, int(rows.numel()), len(thr)))
-    work = torch.empty(wb // 8, dtype=torch.float64, device=X.device) if wb else None
+    out, status, work, wb = c.alloc(L.wagg_edd_ladder_work_bytes, len(thr), out, status)
     fn = L.wagg_edd_ladder_reduce_f32 if X.dtype == torch.float32 else L.wagg_edd_ladder_reduce_f64
-    _lib.check(fn(C.c_void_p(X.data_ptr()), C.c_void_p(X2.data_ptr()), T, n, _ld(X), C.c_void_p(row_begin.data_ptr()),
-                  C.c_void_p(rows.data_ptr()), P, int(rows.numel()), None if doy is None else C.c_void_p(doy.data_ptr()),
-                  None if windows is None else C.c_void_p(windows.data_ptr()), float(offset), _np_ptr(thr, C.c_double), len(thr),
-                  _lib.PERIOD_ROWS_CHECKED if checked else 0, C.c_void_p(out.data_ptr()), max(1, n), max(1, P * n),
-                  C.c_void_p(status.data_ptr()), None if work is None else C.c_void_p(work.data_ptr()), wb, _stream_handle(stream)),
-               "wagg_edd_ladder_reduce")
-    if stream is not None:                           # (as in period_reduce: keep what torch's allocator would take back alive)
-        for t in (work, row_begin, rows, doy, windows):
-            if t is not None:
-                t.record_stream(stream)
+    _lib.check(fn(C.c_void_p(X.data_ptr()), C.c_void_p(X2.data_ptr()), c.T, c.n, _ld(X), C.c_void_p(c.row_begin.data_ptr()),
+                  C.c_void_p(c.rows.data_ptr()), c.P, c.n_rows, None if doy is None else C.c_void_p(c.doy.data_ptr()),
+                  None if doy is None else C.c_void_p(c.windows.data_ptr()), float(offset), _np_ptr(thr, C.c_double), len(thr), c.flags,
+                  C.c_void_p(out.data_ptr()), max(1, c.n), max(1, c.P * c.n), C.c_void_p(status.data_ptr()), work, wb,
+                  _stream_handle(stream)), "wagg_edd_ladder_reduce")
+    c.done(stream)
     return out, status
 
 

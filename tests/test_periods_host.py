@@ -130,3 +130,31 @@ def test_abi_bad_arguments_return_codes():
     wb = L.wagg_period_reduce_work_bytes
     assert wb(1036800, 12, 365, 1) == 0 and wb(63, 70, 70, 1) == 0 and wb(0, 1, 10, 1) == 0 and wb(63, 0, 10, 1) == 0
     assert wb(24378, 1, 365, 1) >= 2 * 8 * 24378 and wb(24378, 1, 365, 4) == 4 * wb(24378, 1, 365, 1)
+
+
+def test_the_three_work_bytes_entry_points_agree():
+    """Period totals, season totals and degree-day ladders cut a period's row list into the same parts -- that is what makes an
+    all-year season equal the period sum and a ladder plane equal the four-plane kernels' plane bit for bit -- so the workspace
+    each asks for is the same number: no split, a split below the cap, the cap of 64, a split held down by the mean list length
+    (n_rows / P / 8), and non-positive arguments."""
+    from climate_toolbox_amd import _lib
+    L = _lib.load()
+    fns = (L.wagg_period_reduce_work_bytes, L.wagg_season_reduce_work_bytes, L.wagg_edd_ladder_work_bytes)
+    splits = set()
+    for n in (1, 63, 256, 1100, 300000, 0, -1):
+        for P in (1, 3, 40, 0, -1):
+            for n_rows in (0, 15, 16, 70, 5000, -1):
+                for planes in (1, 4, 0, -1):
+                    got = [int(f(n, P, n_rows, planes)) for f in fns]
+                    assert got[0] == got[1] == got[2], (n, P, n_rows, planes, got)
+                    if min(n, P, n_rows, planes) <= 0:
+                        assert got[0] == 0
+                    else:
+                        assert got[0] % (8 * planes * P * n) == 0
+                        splits.add(got[0] // (8 * planes * P * n))
+    assert 0 in splits and 64 in splits and any(1 < s < 64 for s in splits) and 1 not in splits
+    for f in fns:
+        assert f(63, 1, 15, 1) == 0 and f(63, 1, 70, 1) == 8 * 8 * 63          # one block: 15 // 8 = 1 part, 70 // 8 = 8 parts
+        assert f(63, 1, 5000, 1) == 64 * 8 * 63                                 # 625 parts by rows, 1024 wanted: the cap
+        assert f(300000, 1, 5000, 4) == 4 * 8 * 4 * 300000                      # 293 blocks of 16-byte pieces: ceil(1024 / 293) = 4
+        assert f(300000, 40, 5000, 1) == 0                                      # the grid fills the device
