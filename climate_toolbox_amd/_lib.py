@@ -49,6 +49,8 @@ EXPORTS = (
     "wagg_period_reduce_f32", "wagg_period_reduce_f64", "wagg_period_reduce_work_bytes",
     "wagg_season_reduce_f32", "wagg_season_reduce_f64", "wagg_season_reduce_work_bytes", "wagg_season_mask",
     "wagg_edd_ladder_reduce_f32", "wagg_edd_ladder_reduce_f64", "wagg_edd_ladder_work_bytes",
+    "wagg_plan_compact_info", "wagg_plan_compact_cells", "wagg_pack_rows_f32", "wagg_pack_rows_f64",
+    "wagg_pack_rows_host_f32", "wagg_pack_rows_host_f64",
 )
 STRUCT_PLAN_INFO, STRUCT_DENSE_INFO, STRUCT_HOST_STATS, STRUCT_APPLY_DESC = 0, 1, 2, 3
 PLAN_SEGMENT, PLAN_DENSE = 0, 1
@@ -56,6 +58,9 @@ SRC_DEVICE, SRC_HOST, SRC_HOST_MULTI, SRC_SHARDED = 0, 1, 2, 3
 XF_NONE, XF_POLY, XF_EDD = 0, 1, 2
 # wagg_apply_desc.flags with a dense-family plan: fp32 full form through the fp32 MFMA kernel instead of the split form
 APPLY_EXACT_F32 = 0x10000
+# ... with a single segment-table plan: x holds packed rows (wagg_pack_rows_*), read through the quads-only cell table
+APPLY_COMPACT_ROWS = 0x20000
+EUNSUPPORTED = -5
 T_F32, T_F64 = 7, 8
 PERIOD_KEEP_NAN, PERIOD_ROWS_CHECKED = 1, 2      # WAGG_PERIOD_*
 SEASON_INVERT, SEASON_NULL = 1 << 20, 1 << 21    # WAGG_SEASON_*: the packed day-of-year window (bits 0-9 a, 10-19 b)
@@ -282,6 +287,12 @@ def load():
                                      C.c_int, C.c_int, vp, C.c_int64, C.c_int64, vp, vp, C.c_int64, vp]
     L.wagg_edd_ladder_work_bytes.argtypes = [C.c_int64, C.c_int32, C.c_int64, C.c_int]
     L.wagg_edd_ladder_work_bytes.restype = C.c_int64
+    L.wagg_plan_compact_info.argtypes = [vp, C.c_int, i64p]
+    L.wagg_plan_compact_cells.argtypes = [vp, C.c_int, i32p]
+    for name in ("wagg_pack_rows_f32", "wagg_pack_rows_f64"):
+        getattr(L, name).argtypes = [vp, vp, vp, C.c_int64, C.c_int64, vp, C.c_int64, vp]
+    for name in ("wagg_pack_rows_host_f32", "wagg_pack_rows_host_f64"):
+        getattr(L, name).argtypes = [vp, vp, vp, C.c_int64, C.c_int64, vp, C.c_int64, C.c_int]
     for name in EXPORTS:
         fn = getattr(L, name)
         if name not in ("wagg_last_error", "wagg_scratch_bytes", "wagg_period_reduce_work_bytes", "wagg_season_reduce_work_bytes",

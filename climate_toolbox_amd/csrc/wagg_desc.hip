@@ -58,6 +58,13 @@ int run_segment(const wagg_apply_desc &d) {
         for (int i = 0; i < d.n_plans; ++i) if (entry::is_many_plan(plans[i])) return true;
         return false;
     };
+    if (d.flags & WAGG_APPLY_COMPACT_ROWS) {
+        if (d.source != WAGG_SRC_DEVICE || d.transform != WAGG_XF_NONE || d.layout != WAGG_LAYOUT_TG || d.out_layout != WAGG_OUT_TR)
+            return unsupported(d, "WAGG_APPLY_COMPACT_ROWS takes device-resident packed (time, cell) rows, no transform, and gives a (time, region) result");
+        if (entry::is_many_plan(plan)) return unsupported(d, "a many-plan has no compact row");
+        if constexpr (f32) return entry::apply_compact_f32(plan, x, d.T, d.ldx, out, d.ldo, d.stream);
+        else return entry::apply_compact_f64(plan, x, d.T, d.ldx, out, d.ldo, d.stream);
+    }
     switch (d.source) {
         case WAGG_SRC_DEVICE:
             if (entry::is_many_plan(plan)) return many();
@@ -114,6 +121,7 @@ int run_dense(const wagg_apply_desc &d) {
         return unsupported(d, "dense-family plans take (time, gridcell) data and give (time, region) results");
     const T *x = static_cast<const T *>(d.x), *x2 = static_cast<const T *>(d.x2);
     T *out = static_cast<T *>(d.out);
+    if (d.flags & WAGG_APPLY_COMPACT_ROWS) return unsupported(d, "a dense-family plan reads every cell of a row: it has no compact row");
     wagg_dense *plan = static_cast<wagg_dense *>(const_cast<void *>(d.plan));
     // WAGG_APPLY_EXACT_F32: fp32 full-form plans run the fp32-pipe kernel instead of the split form (no effect elsewhere)
     const bool exact = (d.flags & WAGG_APPLY_EXACT_F32) != 0;

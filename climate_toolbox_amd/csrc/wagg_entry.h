@@ -9,6 +9,9 @@ namespace wagg {
 namespace entry {
 int apply_f32(const wagg_plan *plan, const float *X_dev, int64_t T, int64_t ldx, int layout, float *out_dev, int64_t ldo, int out_layout, void *stream);
 int apply_f64(const wagg_plan *plan, const double *X_dev, int64_t T, int64_t ldx, int layout, double *out_dev, int64_t ldo, int out_layout, void *stream);
+// WAGG_APPLY_COMPACT_ROWS: X_dev holds packed rows (wagg_pack.hip), ldx >= Gq
+int apply_compact_f32(const wagg_plan *plan, const float *X_dev, int64_t T, int64_t ldx, float *out_dev, int64_t ldo, void *stream);
+int apply_compact_f64(const wagg_plan *plan, const double *X_dev, int64_t T, int64_t ldx, double *out_dev, int64_t ldo, void *stream);
 int apply_host_f32(const wagg_plan *plan, const float *X_host, int64_t T, int64_t ldx, int layout, float *out_host, int64_t ldo, int out_layout);
 int apply_host_f64(const wagg_plan *plan, const double *X_host, int64_t T, int64_t ldx, int layout, double *out_host, int64_t ldo, int out_layout);
 int apply_host_ex_f32(const wagg_plan *plan, const float *X_host, int64_t T, int64_t ldx, int layout, float *out_host, int64_t ldo, int out_layout, int flags);

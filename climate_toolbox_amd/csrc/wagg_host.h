@@ -75,7 +75,7 @@ struct DevicePipe {
     hipEvent_t ready[2] = {nullptr, nullptr}, kdone[2] = {nullptr, nullptr}, ddone[2] = {nullptr, nullptr};
     void *dx[2] = {nullptr, nullptr}, *dout[2] = {nullptr, nullptr};
     bool retire = false;                                        // the device blocks go back to the driver instead of the pool
-    hipError_t init(int dev, bool set_device, size_t x_bytes, size_t o_bytes, int nbuf);
+    hipError_t init(int dev, bool set_device, size_t x_bytes, size_t o_bytes, int nbuf, bool with_out = true);
     hipError_t drain();                                         // synchronise the three streams
     ~DevicePipe();
 };
@@ -103,6 +103,9 @@ struct HostRowsArgs {
     // out_dev + k * rows * ldo_bytes; plane k of the whole result starts at out_host + k * opstride_bytes
     int n_planes = 1;
     int64_t opstride_bytes = 0;
+    // "no result" (wagg_pack.hip): the blocks are all the call is after -- `apply` does with each arrived block what it wants
+    // (its out_dev argument is nullptr), no result block is allocated, nothing returns to the host and out_host is not touched
+    bool no_result = false;
 };
 int stream_host_rows_any(const HostRowsArgs &a);
 

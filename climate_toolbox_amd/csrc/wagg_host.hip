@@ -417,7 +417,7 @@ struct GatherTeam {
 }  // namespace
 
 // ---- one device's streams, events and block buffers ---------------------------------------------------------------
-hipError_t DevicePipe::init(int dev, bool set_device, size_t x_bytes, size_t o_bytes, int nbuf) {
+hipError_t DevicePipe::init(int dev, bool set_device, size_t x_bytes, size_t o_bytes, int nbuf, bool with_out) {
     // streams and block buffers from the scratch pool (wagg_scratch.hip): 0.6 GB of hipMalloc / hipFree and three stream
     // creations per call were 1.4 ms of every 31 ms host-resident apply and most of its tail (tools/host_apply_churn.py)
     hipError_t e = hipSuccess;
@@ -431,7 +431,7 @@ hipError_t DevicePipe::init(int dev, bool set_device, size_t x_bytes, size_t o_b
         if ((e = hipEventCreateWithFlags(&kdone[b], hipEventDisableTiming)) != hipSuccess) return e;
         if ((e = hipEventCreateWithFlags(&ddone[b], hipEventDisableTiming)) != hipSuccess) return e;
         if ((e = scratch_alloc(&dx[b], x_bytes)) != hipSuccess) return e;
-        if ((e = scratch_alloc(&dout[b], o_bytes)) != hipSuccess) return e;
+        if (with_out && (e = scratch_alloc(&dout[b], o_bytes)) != hipSuccess) return e;
     }
     return hipSuccess;
 }
@@ -481,7 +481,7 @@ static int run_device_(const HostRowsArgs &a, int slot, bool set_device, int64_t
     const int dev = a.devices ? a.devices[slot] : -1;
     int cur = 0;
     if (!set_device) WAGG_HIP(hipGetDevice(&cur));
-    WAGG_HIP(P.init(set_device ? dev : cur, set_device, (size_t)(B * (gather ? a.crow_bytes : a.ldx_bytes) * (a.X2_host ? 2 : 1)), (size_t)(B * a.ldo_bytes * a.n_planes), my_blocks >= 2 ? 2 : 1));
+    WAGG_HIP(P.init(set_device ? dev : cur, set_device, (size_t)(B * (gather ? a.crow_bytes : a.ldx_bytes) * (a.X2_host ? 2 : 1)), (size_t)(B * a.ldo_bytes * a.n_planes), my_blocks >= 2 ? 2 : 1, !a.no_result));
     if (gather) {
         team.reset(new (std::nothrow) GatherTeam(a));
         if (!team || !team->start()) return WAGG_EUNSUPPORTED;       // (nothing queued yet: the caller takes the plain path)
@@ -538,6 +538,7 @@ static int run_device_(const HostRowsArgs &a, int slot, bool set_device, int64_t
         if (rc != WAGG_OK) return rc;
         WAGG_HIP(hipEventRecord(P.kdone[b], P.sk));
         g_host_stats.blocks++;
+        if (a.no_result) continue;                                                 // (the block itself was the result: nothing returns)
         if (pin_o) {                                                               // page-locked destination: asynchronous
             WAGG_HIP(hipStreamWaitEvent(P.sd, P.kdone[b], 0));
             for (int k = 0; k < a.n_planes; ++k) {
@@ -625,7 +626,7 @@ int stream_host_rows_any(const HostRowsArgs &a) {
         const bool want = (a.flags & WAGG_HOST_PIN) != 0;
         bool pin_x = want && a.n_runs == 0 && px.acquire(a.X_host, xbytes, a.n_dev > 1);            // (gathered rows: the CPU reads X)
         if (pin_x && a.X2_host && !px2.acquire(a.X2_host, xbytes, a.n_dev > 1)) pin_x = false;      // (both fields, or both staged)
-        const bool pin_o = want && po.acquire(a.out_host, obytes, a.n_dev > 1);
+        const bool pin_o = want && !a.no_result && po.acquire(a.out_host, obytes, a.n_dev > 1);
         if (a.n_dev == 1 && a.devices == nullptr) {
             int64_t f = 0;
             rc = run_device(a, 0, false, B, nb, pin_x, pin_o, &f);      // (this thread: counted through fail0 below)

@@ -2312,6 +2312,34 @@ int wagg::entry::apply_f64(const wagg_plan *plan, const double *X_dev, int64_t T
 }
 
 namespace wagg {
+// WAGG_APPLY_COMPACT_ROWS: device-resident PACKED rows (wagg_pack.hip; ldx >= Gq) through the kernel of the lines-only host
+// path -- what host_rows_pipeline below does with every block it has shipped
+template <typename T>
+static int apply_compact(const wagg_plan *plan, const T *X, int64_t Tn, int64_t ldx, T *out, int64_t ldo, hipStream_t st) {
+    WAGG_REQUIRE(plan != nullptr, "plan is NULL");
+    WAGG_REQUIRE(Tn >= 0, "T < 0");
+    const SparsePlanDev &d = sizeof(T) == 4 ? plan->dl : plan->dl64;
+    const bool lcv_off = (plan->flags & (WAGG_PLAN_NO_LC | WAGG_PLAN_NO_STREAM | WAGG_PLAN_LC_MFMA)) != 0;
+    if (plan->is_many() || lcv_off || !(sizeof(T) == 4 ? plan->has_lines : plan->has_lines64) || d.Gq <= 0 || d.g0_normal != 0) {
+        set_error("wagg_apply: WAGG_APPLY_COMPACT_ROWS needs a single segment-table plan with the quads-only compact row of this element type");
+        return WAGG_EUNSUPPORTED;
+    }
+    if (Tn == 0) return WAGG_OK;
+    WAGG_REQUIRE(X != nullptr && out != nullptr, "X/out is NULL");
+    WAGG_REQUIRE(ldx >= d.Gq, "ldx %lld too small for packed rows of %lld cells", (long long)ldx, (long long)d.Gq);
+    WAGG_REQUIRE(ldo >= (int64_t)plan->info.R, "ldo %lld too small", (long long)ldo);
+    return launch_sparse<T, (sizeof(T) == 4 ? 64 : 32)>(plan, X, Tn, ldx, WAGG_LAYOUT_TG, out, ldo, WAGG_OUT_TR, st, T(0), 0, 1, 0, nullptr,
+                                                        nullptr, 0, COMPACT_QUADS);
+}
+}  // namespace wagg
+int wagg::entry::apply_compact_f32(const wagg_plan *plan, const float *X_dev, int64_t T, int64_t ldx, float *out_dev, int64_t ldo, void *stream) {
+    return wagg::apply_compact<float>(plan, X_dev, T, ldx, out_dev, ldo, (hipStream_t)stream);
+}
+int wagg::entry::apply_compact_f64(const wagg_plan *plan, const double *X_dev, int64_t T, int64_t ldx, double *out_dev, int64_t ldo, void *stream) {
+    return wagg::apply_compact<double>(plan, X_dev, T, ldx, out_dev, ldo, (hipStream_t)stream);
+}
+
+namespace wagg {
 // (x + offset)^p for p = 1..n_pow, each aggregated like wagg_apply.  Power p lands at
 // out + (p - 1) * out_pstride.
 template <typename T, int TB>

@@ -115,6 +115,11 @@ struct wagg_plan {
     wagg::ManyLevel many_lv[wagg::MANY_MAX_LEVELS];
     int many_nlv = 0;
     int32_t many_R0 = 0;
+    // wagg_pack.hip: the first cell of every quad of the quads-only compact row, in row order (Gq / 4 entries), of the fp32
+    // chunking `dl` ([0]) and the fp64 one `dl64` ([1]); uploaded by the first pack of that element type, freed with the plan
+    mutable std::mutex pack_mu;
+    mutable wagg::DevBuf<int32_t> pack_quads[2];
+    mutable bool pack_ready[2] = {false, false};
     bool is_many() const { return !many_w.empty(); }
     int64_t many_col(int level, int k) const {       // first column of plane (level, k): level-major, then weighting
         int64_t off = 0;

@@ -134,13 +134,42 @@ class SparsePlan:
         (``wagg_plan_status``)."""
         _lib.check(_lib.load().wagg_plan_status(self._h, _stream_handle(stream)), "wagg_plan_status")
 
-    def apply(self, X, layout="TG", out=None, out_layout="TR", stream=None):
-        """out[t, r] on the device; asynchronous on torch's current stream (or `stream`)."""
+    def compact_cells(self, dtype):
+        """The grid cell behind every position of the plan's quads-only compact row for element type ``dtype`` (float32 /
+        float64; ``wagg_plan_compact_cells``): an int32 array of ``Gq`` cells, quad ``i`` of the sorted distinct referenced quads
+        at positions ``4i .. 4i + 3`` -- the columns of :func:`pack_rows`.  None when the plan has no such row for that type
+        (region-shaped chunkings only, ``PLAN_NO_LINES``).  Cached; treat the array as read-only."""
+        eb = 8 if "float64" in str(dtype) else 4          # (torch / numpy dtypes, their names, the numpy scalar types)
+        cache = self.__dict__.setdefault("_compact_cells", {})
+        if eb not in cache:
+            L = _lib.load()
+            gq = C.c_int64(0)
+            _lib.check(L.wagg_plan_compact_info(self._h, eb, C.byref(gq)), "wagg_plan_compact_info")
+            cells = None
+            if gq.value > 0:
+                cells = np.empty(gq.value, dtype=np.int32)
+                _lib.check(L.wagg_plan_compact_cells(self._h, eb, _np_ptr(cells, C.c_int32)), "wagg_plan_compact_cells")
+                cells.setflags(write=False)
+            cache[eb] = cells
+        return cache[eb]
+
+    def apply(self, X, layout="TG", out=None, out_layout="TR", stream=None, compact=False):
+        """out[t, r] on the device; asynchronous on torch's current stream (or `stream`).  ``compact=True``: the rows of X are
+        PACKED rows (:func:`pack_rows`; at least ``len(compact_cells(X.dtype))`` columns, of which the first ``Gq`` are read)
+        -- ``WAGG_APPLY_COMPACT_ROWS``: "TG" in, "TR" out only; the same bits as the plain apply of the unpacked rows."""
         import torch
         X = _check_X(X, layout)
         T = X.shape[0] if layout == "TG" else X.shape[1]
         n_g = X.shape[1] if layout == "TG" else X.shape[0]
-        if n_g != self.G:
+        if compact:
+            if layout != "TG" or out_layout != "TR":
+                raise ValueError("compact rows are (time, cell) data and give a (time, region) result")
+            cells = self.compact_cells(X.dtype)
+            if cells is None:
+                raise WaggError("this plan has no compact row for %s data" % (X.dtype,))
+            if n_g < len(cells):
+                raise ValueError("X has %d columns, a packed row of this plan %d" % (n_g, len(cells)))
+        elif n_g != self.G:
             raise ValueError("X has %d grid cells, plan expects %d" % (n_g, self.G))
         shape = (T, self.R) if out_layout == "TR" else (self.R, T)
         if out is None:
@@ -149,7 +178,7 @@ class SparsePlan:
             raise ValueError("out must be a %s %s tensor with contiguous rows" % (shape, X.dtype))
         _lib.run("wagg_apply", plan_kind=_lib.PLAN_SEGMENT, plan=self._h, elem=_elem(X.dtype), source=_lib.SRC_DEVICE,
                  x=X.data_ptr(), T=T, ldx=_ld(X), layout=_LAYOUTS[layout], out=out.data_ptr(), ldo=_ld(out),
-                 out_layout=_OUTS[out_layout], stream=_stream_handle(stream))
+                 out_layout=_OUTS[out_layout], stream=_stream_handle(stream), flags=_lib.APPLY_COMPACT_ROWS if compact else 0)
         return out
 
     def apply_poly(self, X, offset, n_pow, layout="TG", out=None, out_layout="TR", stream=None, pow_first=1):
@@ -679,6 +708,68 @@ def gather(X, cell_idx_dev, layout="TG", out_layout="TR", stream=None):
     return out
 
 
+# which way the calls of pack_rows went: "device" (the pack kernel on a device tensor), "host" (the gather pipeline from host
+# arrays), "host_fallback" (host arrays the gather could not serve: uploaded whole, then the pack kernel)
+PACK_STATS = {"device": 0, "host": 0, "host_fallback": 0}
+
+
+def pack_rows(plan, X, X2=None, stream=None):
+    """The rows of a (T, G) field with only the quads the plan's table references: a (T, Gq) CUDA tensor, column ``j`` being cell
+    ``plan.compact_cells(X.dtype)[j]`` (``wagg_pack_rows_*``).  With ``X2`` (tasmax beside tasmin; same shape, dtype and row
+    stride) a (T, 2 Gq) tensor: field 0 in ``[:, :Gq]``, field 1 in ``[:, Gq:]``.  ``X`` / ``X2``: CUDA tensors (asynchronous on
+    torch's current stream, or ``stream``) or NumPy arrays -- then host threads pack the quads and only they cross PCIe
+    (``wagg_pack_rows_host_*``; blocking) where the library takes that way (a field of >= 64 MiB whose packed row is <= 80 % of
+    the row, enough CPUs), and the field is uploaded whole and packed on the device where it does not.  ``PACK_STATS`` counts
+    the ways taken.  WaggError for a plan without a compact row."""
+    torch = require_gpu()
+    if not isinstance(plan, SparsePlan):
+        raise TypeError("pack_rows takes a SparsePlan")
+    on_host = not isinstance(X, torch.Tensor)
+    if on_host:
+        X = np.ascontiguousarray(X)
+        X2 = None if X2 is None else np.ascontiguousarray(X2)
+        if X.dtype not in (np.float32, np.float64) or X.ndim != 2:
+            raise TypeError("X must be a 2-D float32/float64 array or CUDA tensor")
+    else:
+        X = _check_X(X, "TG")
+        X2 = None if X2 is None else _check_X(X2, "TG")
+    if X2 is not None and (isinstance(X2, torch.Tensor) == on_host or tuple(X2.shape) != tuple(X.shape) or X2.dtype != X.dtype):
+        raise ValueError("X and X2 must have the same residency, shape and dtype")
+    if X.shape[1] != plan.G:
+        raise ValueError("X has %d grid cells, plan expects %d" % (X.shape[1], plan.G))
+    cells = plan.compact_cells(X.dtype)
+    if cells is None:
+        raise WaggError("this plan has no compact row for %s data" % (X.dtype,))
+    T, nf, f32 = int(X.shape[0]), 1 if X2 is None else 2, _elem(X.dtype) == _lib.T_F32
+    L = _lib.load()
+    with _on_device(plan.device):
+        if on_host:
+            out = torch.empty((T, nf * len(cells)), dtype=torch.float32 if f32 else torch.float64, device="cuda")
+            torch.cuda.current_stream().synchronize()      # (the caching allocator may hand out memory the stream still writes)
+            fn = L.wagg_pack_rows_host_f32 if f32 else L.wagg_pack_rows_host_f64
+            rc = fn(plan._h, C.c_void_p(X.ctypes.data), None if X2 is None else C.c_void_p(X2.ctypes.data), T, X.shape[1],
+                    C.c_void_p(out.data_ptr()), max(1, out.shape[1]), 0)
+            if rc != _lib.EUNSUPPORTED:
+                _lib.check(rc, "wagg_pack_rows_host")
+                PACK_STATS["host"] += 1
+                return out
+            PACK_STATS["host_fallback"] += 1
+            X, X2 = upload(X), None if X2 is None else upload(X2)
+        else:
+            if X2 is not None and _ld(X2) != _ld(X):
+                raise ValueError("X and X2 must share one row stride")
+            out = torch.empty((T, nf * len(cells)), dtype=X.dtype, device=X.device)
+            PACK_STATS["device"] += 1
+        fn = L.wagg_pack_rows_f32 if f32 else L.wagg_pack_rows_f64
+        _lib.check(fn(plan._h, C.c_void_p(X.data_ptr()), None if X2 is None else C.c_void_p(X2.data_ptr()), T, _ld(X),
+                      C.c_void_p(out.data_ptr()), max(1, out.shape[1]), _stream_handle(stream)), "wagg_pack_rows")
+        if stream is not None:
+            for t in (X, X2):
+                if t is not None:
+                    t.record_stream(stream)
+    return out
+
+
 def _flat_dev(t):
     import torch
     if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype in (torch.float32, torch.float64)):
@@ -790,8 +881,9 @@ class _RowlistCall:
         if self.P < 0:
             raise ValueError("row_begin must hold P + 1 offsets")
 
-    def alloc(self, work_bytes, planes, out, status):
-        """``(out, status, work pointer, work bytes)``; ``work_bytes``: the library's ``*_work_bytes`` for this call"""
+    def alloc(self, work_bytes, planes, out, status, workspace=True):
+        """``(out, status, work pointer, work bytes)``; ``work_bytes``: the library's ``*_work_bytes`` for this call
+        (``workspace=False``: the library gets no scratch and sums every period's list in one part)"""
         import torch
         X, shape = self.X, (planes, self.P, self.n)
         if out is None:
@@ -800,7 +892,7 @@ class _RowlistCall:
             raise ValueError("out must be a contiguous %s %s tensor" % (shape, X.dtype))
         if status is None:
             status = torch.zeros(1, dtype=torch.int32, device=X.device)
-        wb = int(work_bytes(self.n, self.P, self.n_rows, planes))
+        wb = int(work_bytes(self.n, self.P, self.n_rows, planes)) if workspace else 0
         self.work = torch.empty(wb // 8, dtype=torch.float64, device=X.device) if wb else None
         return out, status, None if self.work is None else C.c_void_p(self.work.data_ptr()), wb
 
@@ -831,13 +923,16 @@ def _rowlist_transform(X, X2, poly, edd):
     return transform, float(offset), int(pow_first), int(n_pow), thr, planes, X2
 
 
-def period_reduce(X, row_begin, rows, X2=None, poly=None, edd=None, keep_nan=False, checked=False, out=None, status=None, stream=None):
+def period_reduce(X, row_begin, rows, X2=None, poly=None, edd=None, keep_nan=False, checked=False, out=None, status=None, stream=None,
+                  workspace=True):
     """Period totals of the rows of a (T, n) CUDA tensor (``wagg_period_reduce_*``): ``out[k, p, j] = sum_t f_k(X[t, j])`` over
     the rows ``t`` of period ``p`` in list order, fp64 accumulation.  ``row_begin`` / ``rows``: the CSR row lists -- host
     integers (checked here, uploaded) or the int32 CUDA tensors of :func:`period_lists` (``checked=True``: the call is then
     asynchronous; otherwise the library checks them on the device first, which blocks).  ``poly=(offset, pow_first, n_pow)``:
     planes ``(x + offset) ** q``; ``edd=(offset, thresholds)`` with ``X2`` = tasmax: Snyder degree days per threshold; neither:
     one plane of plain sums.  ``keep_nan``: NaN propagates (sums of aggregated results) instead of counting 0 (S6).
+    ``workspace=False``: no scratch for the library, so a period's list is never cut into parts -- the split then does not depend
+    on ``n``, and a column's sum has the same bits whatever matrix it sits in (here and in the two calls below).
     Returns ``(out, status)``: the (planes, P, n) tensor and the one-word int32 CUDA tensor ``status`` (zeroed here unless
     handed in), bit 0 of which the kernel sets when a transformed value was +-inf -- reading it waits for the kernel."""
     import torch
@@ -845,7 +940,7 @@ def period_reduce(X, row_begin, rows, X2=None, poly=None, edd=None, keep_nan=Fal
     c = _RowlistCall(X, row_begin, rows, checked)
     transform, offset, pow_first, n_pow, thr, planes, X2 = _rowlist_transform(X, X2, poly, edd)
     L = _lib.load()
-    out, status, work, wb = c.alloc(L.wagg_period_reduce_work_bytes, planes, out, status)
+    out, status, work, wb = c.alloc(L.wagg_period_reduce_work_bytes, planes, out, status, workspace)
     fn = L.wagg_period_reduce_f32 if X.dtype == torch.float32 else L.wagg_period_reduce_f64
     _lib.check(fn(C.c_void_p(X.data_ptr()), C.c_void_p(X2.data_ptr()) if edd is not None else None, c.T, c.n, _ld(X),
                   C.c_void_p(c.row_begin.data_ptr()), C.c_void_p(c.rows.data_ptr()), c.P, c.n_rows, transform, offset, pow_first, n_pow,
@@ -856,7 +951,8 @@ def period_reduce(X, row_begin, rows, X2=None, poly=None, edd=None, keep_nan=Fal
     return out, status
 
 
-def season_reduce(X, row_begin, rows, doy, windows, X2=None, poly=None, edd=None, checked=False, out=None, status=None, stream=None):
+def season_reduce(X, row_begin, rows, doy, windows, X2=None, poly=None, edd=None, checked=False, out=None, status=None, stream=None,
+                  workspace=True):
     """Growing-season totals of the rows of a (T, n) CUDA tensor (``wagg_season_reduce_*``): :func:`period_reduce` with one more
     predicate -- ``out[k, p, j]`` sums ``f_k(X[t, j])`` over the rows ``t`` of period ``p`` on which cell ``j`` is in season.
     ``doy``: the day of year of each of the T rows; ``windows``: one packed window per cell (``_lib.SEASON_*``: bits 0-9 first
@@ -869,7 +965,7 @@ def season_reduce(X, row_begin, rows, doy, windows, X2=None, poly=None, edd=None
     c = _RowlistCall(X, row_begin, rows, checked, (doy, windows))
     transform, offset, pow_first, n_pow, thr, planes, X2 = _rowlist_transform(X, X2, poly, edd)
     L = _lib.load()
-    out, status, work, wb = c.alloc(L.wagg_season_reduce_work_bytes, planes, out, status)
+    out, status, work, wb = c.alloc(L.wagg_season_reduce_work_bytes, planes, out, status, workspace)
     fn = L.wagg_season_reduce_f32 if X.dtype == torch.float32 else L.wagg_season_reduce_f64
     _lib.check(fn(C.c_void_p(X.data_ptr()), C.c_void_p(X2.data_ptr()) if edd is not None else None, c.T, c.n, _ld(X),
                   C.c_void_p(c.row_begin.data_ptr()), C.c_void_p(c.rows.data_ptr()), c.P, c.n_rows, C.c_void_p(c.doy.data_ptr()),
@@ -882,7 +978,7 @@ def season_reduce(X, row_begin, rows, doy, windows, X2=None, poly=None, edd=None
 
 
 def edd_ladder_reduce(tasmin, tasmax, row_begin, rows, offset, thresholds, doy=None, windows=None, checked=False, out=None, status=None,
-                      stream=None):
+                      stream=None, workspace=True):
     """Snyder degree days at every threshold of a ladder, summed per period, in ONE launch (``wagg_edd_ladder_reduce_*``):
     ``out[k, p, j]`` sums ``snyder_edd(tasmin[t, j] + offset, tasmax[t, j] + offset, thresholds[k])`` over the rows ``t`` of
     period ``p`` on which cell ``j`` is in season -- :func:`season_reduce` with ``edd=`` without its cap of four thresholds
@@ -903,7 +999,7 @@ def edd_ladder_reduce(tasmin, tasmax, row_begin, rows, offset, thresholds, doy=N
         raise ValueError("doy and windows go together: both given, or both None (no season)")
     c = _RowlistCall(X, row_begin, rows, checked, None if doy is None else (doy, windows))
     L = _lib.load()
-    out, status, work, wb = c.alloc(L.wagg_edd_ladder_work_bytes, len(thr), out, status)
+    out, status, work, wb = c.alloc(L.wagg_edd_ladder_work_bytes, len(thr), out, status, workspace)
     fn = L.wagg_edd_ladder_reduce_f32 if X.dtype == torch.float32 else L.wagg_edd_ladder_reduce_f64
     _lib.check(fn(C.c_void_p(X.data_ptr()), C.c_void_p(X2.data_ptr()), c.T, c.n, _ld(X), C.c_void_p(c.row_begin.data_ptr()),
                   C.c_void_p(c.rows.data_ptr()), c.P, c.n_rows, None if doy is None else C.c_void_p(c.doy.data_ptr()),

@@ -119,13 +119,17 @@ def _sum_time_axis(arr, axis, lists, P, keep_dev):
     return np.moveaxis(_to_host(out), 0, axis)
 
 
-def _contract(plan, field, P, R, edd, powers, rdims, agglev, keep_dev, planes=False):
+def _contract(plan, field, P, R, edd, powers, rdims, agglev, keep_dev, planes=False, compact=False):
     """The (planes, P, G) period sums of a field through the leased ``plan``: the list of (P, R) results (in ``rdims`` order;
     device tensors when ``keep_dev``), or None when a dense-family plan met +-inf.  ``planes``: every plane is a result of its
-    own, in order (a degree-day ladder) -- nothing is combined or picked."""
+    own, in order (a degree-day ladder) -- nothing is combined or picked.  ``compact``: the sums are (planes, P, Gq) sums of
+    packed rows (``cells="referenced"``; a segment-table plan), contracted through the plan's quads-only cell table."""
     K = field.shape[0]
     flat = field.reshape(K * P, field.shape[2])
-    out = plan.apply(flat) if isinstance(plan, DensePlan) else plan.apply(flat, layout="TG", out_layout="TR")
+    if compact:
+        out = plan.apply(flat, layout="TG", out_layout="TR", compact=True)
+    else:
+        out = plan.apply(flat) if isinstance(plan, DensePlan) else plan.apply(flat, layout="TG", out_layout="TR")
     if isinstance(plan, DensePlan) and plan.saw_inf():
         return None
     stack = out.reshape(K, P, R)
@@ -152,13 +156,15 @@ def _contract(plan, field, P, R, edd, powers, rdims, agglev, keep_dev, planes=Fa
     return res
 
 
-def _reduce_first(ds, variable, aggwt, agglev, weights, backup_aggwt, lists, P, powers, offset, force):
-    """The reduce-first route; None when this call cannot (or, unless forced, should not) take it, or met +-inf."""
+def _reduce_first(ds, variable, aggwt, agglev, weights, backup_aggwt, lists, P, powers, offset, force, cells="all"):
+    """The reduce-first route; None when this call cannot (or, unless forced, should not) take it, or met +-inf.
+    ``cells="referenced"``: the field(s) are packed to the quads the table references first (``engine.pack_rows``), summed with
+    n = Gq and contracted through the plan's quads-only cell table -- where the plan has one (seasons._compact_cells_of)."""
     if not (isinstance(ds, _agg.ReindexedDataset) and variable in ds._src_values):
         return None
     values, dims = ds._src_values[variable], ds._src_dims[variable]
     *_, others = _spatial_layout(dims)
-    if P == 0 or [dims[i] for i in others] != ["time"] or not (force or _is_device_tensor(values)):
+    if P == 0 or [dims[i] for i in others] != ["time"] or not (force or cells == "referenced" or _is_device_tensor(values)):
         return None
     xform, edd = ds._xforms.get(variable), ds._edds.get(variable)
     if (powers is not None or edd is not None) and xform is not None:
@@ -190,15 +196,23 @@ def _reduce_first(ds, variable, aggwt, agglev, weights, backup_aggwt, lists, P, 
                      is_f32=str(X2.dtype).endswith("float32"), layout=layout, prepared=prepared)
     try:
         family = "dense" if isinstance(plan, DensePlan) else "segment"
-        if not force and family not in REDUCE_FIRST_FAMILIES:
-            return None
-        Xd = _to_device(X2)
+        pos = None
+        if cells == "referenced":
+            from .seasons import _compact_cells_of
+            pos = _compact_cells_of(plan, X2.dtype)
+        if pos is None and not force and (family not in REDUCE_FIRST_FAMILIES or not _is_device_tensor(values)):
+            return None                              # (also cells="referenced" on a plan that cannot pack: as with "all")
+        H2 = None if edd is None else _flatten_for_device(edd[0], dims)[0]
+        if H2 is not None and (H2.shape != X2.shape or H2.dtype != X2.dtype):
+            raise ValueError("tasmin and tasmax must have the same shape and dtype")
+        if pos is not None:
+            packed = _engine.pack_rows(plan, X2, H2)
+            Xd, Hd = packed[:, :len(pos)], (None if H2 is None else packed[:, len(pos):])
+        else:
+            Xd, Hd = _to_device(X2), (None if H2 is None else _to_device(H2))
         rb, rw = lists(Xd.device)
         if edd is not None:
-            H2 = _flatten_for_device(edd[0], dims)[0]
-            if H2.shape != X2.shape or H2.dtype != X2.dtype:
-                raise ValueError("tasmin and tasmax must have the same shape and dtype")
-            field, status = _engine.period_reduce(Xd, rb, rw, X2=_to_device(H2), edd=(edd[1], [e for _, e in edd[2]]), checked=True)
+            field, status = _engine.period_reduce(Xd, rb, rw, X2=Hd, edd=(edd[1], [e for _, e in edd[2]]), checked=True)
         elif powers is not None:
             lo, hi = int(min(powers)), int(max(powers))
             field, status = _engine.period_reduce(Xd, rb, rw, poly=(offset, lo, hi - lo + 1), checked=True)
@@ -207,7 +221,7 @@ def _reduce_first(ds, variable, aggwt, agglev, weights, backup_aggwt, lists, P, 
         if int(status.item()) & 1:
             return None                              # +-inf somewhere: the daily path decides what it means (S6)
         res = _contract(plan, field, P, len(uniq), edd, powers, _result_dims(dims, agglev), agglev,
-                        _agg._device_results_wanted() and _is_device_tensor(values) and not ds._was_xarray)
+                        _agg._device_results_wanted() and _is_device_tensor(values) and not ds._was_xarray, compact=pos is not None)
         if res is None:
             return None                              # (finite days whose total overflows fp32)
         rdims = _result_dims(dims, agglev)
@@ -223,12 +237,14 @@ def _reduce_first(ds, variable, aggwt, agglev, weights, backup_aggwt, lists, P, 
 
 
 def _aggregate_periods(ds, variables, aggwt, agglev, weights, backup_aggwt, period, time_values, powers=None, offset=0.0, route=None,
-                       season=None, grid=None):
+                       season=None, grid=None, cells="all"):
     """Body of the period calls.  ``ds``: a reindexed dataset; ``variables``: the name to aggregate (``powers`` None) or the
     result names, one per power of variable "tas".  ``season`` (with ``grid`` = the dataset's own lat / lon labels): only
-    in-season days count (seasons.py).  Returns the Dataset with ``time`` replaced by ``period``."""
+    in-season days count (seasons.py).  ``cells``: "all", or "referenced" -- sum first, on the quads the table references
+    only.  Returns the Dataset with ``time`` replaced by ``period``."""
     if route not in (None, "reduce_first", "aggregate_first"):
         raise ValueError("_route must be None, 'reduce_first' or 'aggregate_first'")
+    _check_cells(cells, route)
     if season is not None and route is not None:
         raise ValueError("_route cannot be combined with season=: season totals always sum the field first")
     labels, row_begin, rows = period_rows(time_values, period)
@@ -246,9 +262,10 @@ def _aggregate_periods(ds, variables, aggwt, agglev, weights, backup_aggwt, peri
     if season is not None:
         from . import seasons
         got = seasons._season_totals(ds, variable, aggwt, agglev, weights, backup_aggwt, lists, P, powers, offset, season, grid,
-                                     time_values)
+                                     time_values, cells=cells)
     elif route != "aggregate_first":
-        got = _reduce_first(ds, variable, aggwt, agglev, weights, backup_aggwt, lists, P, powers, offset, route == "reduce_first")
+        got = _reduce_first(ds, variable, aggwt, agglev, weights, backup_aggwt, lists, P, powers, offset, route == "reduce_first",
+                            cells=cells)
         if got is None and route == "reduce_first" and not _reduce_first_possible(ds, variable, powers):
             raise ValueError("reduce-first needs a (time, gridcell) field whose only other dimension is time")
     if got is None:
@@ -270,6 +287,14 @@ def _aggregate_periods(ds, variables, aggwt, agglev, weights, backup_aggwt, peri
     return _agg._as_dataset(data, rdims, coords, was_xr)
 
 
+def _check_cells(cells, route=None):
+    """``cells=`` of the period calls: "all" or "referenced"; the latter sums the field first, so it excludes ``_route="aggregate_first"``"""
+    if cells not in ("all", "referenced"):
+        raise ValueError("cells must be 'all' or 'referenced', got %r" % (cells,))
+    if cells == "referenced" and route == "aggregate_first":
+        raise ValueError("cells='referenced' sums the field first: it cannot be combined with _route='aggregate_first'")
+
+
 def _reduce_first_possible(ds, variable, powers):
     if not (isinstance(ds, _agg.ReindexedDataset) and variable in ds._src_values):
         return False
@@ -285,7 +310,7 @@ def _flatten_for_device_layout(dims):
 
 
 def weighted_aggregate_grid_to_regions_periods(ds, variable, aggwt, agglev, weights, period="year", backup_aggwt="areawt",
-                                               _route=None, season=None):
+                                               _route=None, season=None, cells="all"):
     """``weighted_aggregate_grid_to_regions`` followed by the sum over each period's time steps, all on the device.
 
     ds, variable, aggwt, agglev, weights   as for :func:`weighted_aggregate_grid_to_regions` (``weights``: the segment table,
@@ -305,6 +330,16 @@ def weighted_aggregate_grid_to_regions_periods(ds, variable, aggwt, agglev, weig
               contracted.  A (lat, lon, time) field is transposed on the device; a host-resident field is uploaded WHOLE --
               this route does not use the quads-only host pipeline of the daily call.  A further non-time dimension, an
               in-season +-inf (there is no daily masked route to fall back to) or ``_route=`` with it raise ValueError.
+    cells     "all" (the default: everything above, unchanged) or "referenced": the field is first PACKED to the 16-byte quads
+              the segment table references (``engine.pack_rows``: a third of a c2-real row) -- by host threads for a
+              host-resident field, so that only those quads cross PCIe (where the library takes that way: a field of >= 64 MiB,
+              enough CPUs; else it is uploaded whole and packed on the device), by one kernel for a device-resident one -- then
+              summed per period over Gq cells instead of G and contracted through the plan's quads-only cell table.  It always
+              sums the field first (with ``_route="aggregate_first"`` ValueError), with or without ``season=``.  Results agree
+              with "all" to the rounding of the fp64 partial sums.  One difference: a +-inf in a cell of a quad no table row
+              reads is no longer seen -- it neither raises (``season=``) nor sends the call down the daily route.  Where the
+              plan has no quads map (a dense-family plan, a grid the whole-line chunkings do not serve) or the packed row
+              exceeds 80 % of the row, the call runs as with "all": the keyword permits, it never fails.
 
     Returns the single call's Dataset with ``time`` replaced by a dimension ``period`` carrying the labels; region labels,
     other coordinates and the variable name are unchanged.  Lazy variables (``tas_poly``, ``convert_kelvin_to_celsius``,
@@ -318,6 +353,7 @@ def weighted_aggregate_grid_to_regions_periods(ds, variable, aggwt, agglev, weig
     aggregates daily and sums the (T x R) result on the device (``REDUCE_FIRST_FAMILIES``; the module docstring)."""
     if season is not None and _route is not None:
         raise ValueError("_route cannot be combined with season=: season totals always sum the field first")
+    _check_cells(cells, _route)
     if weights is None:
         weights = _agg.prepare_spatial_weights_data()         # TypeError, like the reference
     elif isinstance(weights, str):
@@ -328,4 +364,4 @@ def weighted_aggregate_grid_to_regions_periods(ds, variable, aggwt, agglev, weig
     grid = None if season is None else (np.asarray(ds.coords["lat"].values), np.asarray(ds.coords["lon"].values))
     re = _agg._reindex_spatial_data_to_regions(ds, weights)
     return _aggregate_periods(re, variable, aggwt, agglev, weights, backup_aggwt, period, time_values, route=_route, season=season,
-                              grid=grid)
+                              grid=grid, cells=cells)

@@ -220,6 +220,46 @@ def _time_by_cell(buf, dims):
     return Xd if layout == "TG" else _engine.relayout(Xd, [1, 0])
 
 
+def _check_cells(cells):
+    if cells not in ("all", "referenced"):
+        raise ValueError("cells must be 'all' or 'referenced', got %r" % (cells,))
+    return cells
+
+
+def _compact_cells_of(plan, dtype):
+    """``cells="referenced"``: the cells of the plan's compact row (``SparsePlan.compact_cells``), or None where the call falls
+    back to whole rows -- a dense-family plan, a plan without the quads map, a packed row above 80 % of the row"""
+    if not isinstance(plan, _engine.SparsePlan):
+        return None
+    pos = plan.compact_cells(dtype)
+    return None if pos is None or 5 * len(pos) > 4 * plan.G else pos
+
+
+def _referenced_rows(values, second, dims, make_plan):
+    """``cells="referenced"`` of the sum-first routes: ``(plan, X, H, cell_of_pos)`` -- the leased plan (``make_plan(dtype)``)
+    and the field(s) as (time, Gq) device matrices holding only the quads the table references (``engine.pack_rows``: a
+    host-resident field is packed by host threads and only the quads cross PCIe, a (gridcell, time) one is transposed on the
+    device first), column j being cell ``cell_of_pos[j]``.  ``cell_of_pos`` None: the call falls back (:func:`_compact_cells_of`)
+    and X / H are the whole (time, gridcell) rows of ``_time_by_cell``.  ``second``: tasmax, or None."""
+    X2, layout, _, _ = _flatten_for_device(values, dims)
+    H2 = None if second is None else _flatten_for_device(second, dims)[0]
+    if H2 is not None and (tuple(H2.shape) != tuple(X2.shape) or H2.dtype != X2.dtype):
+        raise ValueError("tasmin and tasmax must have the same shape and dtype")
+    plan = make_plan(X2.dtype)
+    try:
+        pos = _compact_cells_of(plan, X2.dtype)
+        if pos is None or layout != "TG":
+            whole = lambda a: None if a is None else (_to_device(a) if layout == "TG" else _engine.relayout(_to_device(a), [1, 0]))
+            X2, H2 = whole(X2), whole(H2)
+            if pos is None:
+                return plan, X2, H2, None
+        packed = _engine.pack_rows(plan, X2, H2)
+        return plan, packed[:, :len(pos)], (None if H2 is None else packed[:, len(pos):]), pos
+    except BaseException:
+        plan._lease.release()
+        raise
+
+
 def _result_coords(ds, rdims, agglev, uniq):
     carried = ds.coords
     coords = {d: np.asarray(carried[d].values) for d in rdims if d != agglev and d in carried and tuple(carried[d].dims) == (d,)}
@@ -227,10 +267,11 @@ def _result_coords(ds, rdims, agglev, uniq):
     return coords
 
 
-def _season_totals(ds, variable, aggwt, agglev, weights, backup_aggwt, lists, P, powers, offset, season, grid, time_values):
+def _season_totals(ds, variable, aggwt, agglev, weights, backup_aggwt, lists, P, powers, offset, season, grid, time_values,
+                   cells="all"):
     """The one route of a ``season=`` call: sum first (``wagg_season_reduce_*``), then contract P rows on whatever plan serves
     the table.  Returns what ``periods._reduce_first`` returns; raises where that one would fall back -- there is no daily masked
-    route to fall back to."""
+    route to fall back to.  ``cells="referenced"``: all of it on the packed rows of :func:`_referenced_rows`."""
     from . import periods as _periods
     values, dims = _gridded_field(ds, variable, P, "season=")
     xform, edd = ds._xforms.get(variable), ds._edds.get(variable)
@@ -248,13 +289,20 @@ def _season_totals(ds, variable, aggwt, agglev, weights, backup_aggwt, lists, P,
     ia, io, *_ = _spatial_layout(dims)
     doy, win = _stored_season(ds, variable, season, grid, dims, shape, time_values)
     _engine.require_gpu()
-    Xd = _time_by_cell(values, dims)
-    plan = _plan_for(cell_idx, codes, w_eff, G, len(uniq), shape["lon"] if ia < io else shape["lat"],
-                     is_f32=str(Xd.dtype).endswith("float32"), layout="TG", prepared=prepared)
+    make_plan = lambda dtype: _plan_for(cell_idx, codes, w_eff, G, len(uniq), shape["lon"] if ia < io else shape["lat"],
+                                        is_f32=str(dtype).endswith("float32"), layout="TG", prepared=prepared)
+    Hd = pos = None
+    if cells == "referenced":
+        plan, Xd, Hd, pos = _referenced_rows(values, None if edd is None else edd[0], dims, make_plan)
+        if pos is not None:
+            win = win[pos]
+    else:
+        Xd = _time_by_cell(values, dims)
+        plan = make_plan(Xd.dtype)
     try:
         rb, rw = lists(Xd.device)
         if edd is not None:
-            Hd = _time_by_cell(edd[0], dims)
+            Hd = _time_by_cell(edd[0], dims) if Hd is None else Hd
             if Hd.shape != Xd.shape or Hd.dtype != Xd.dtype:
                 raise ValueError("tasmin and tasmax must have the same shape and dtype")
             field, status = _engine.season_reduce(Xd, rb, rw, doy, win, X2=Hd, edd=(edd[1], [e for _, e in edd[2]]), checked=True)
@@ -268,7 +316,7 @@ def _season_totals(ds, variable, aggwt, agglev, weights, backup_aggwt, lists, P,
                              "have no daily route that could give it the daily treatment" % (variable,))
         rdims = _result_dims(dims, agglev)
         res = _periods._contract(plan, field, P, len(uniq), edd, powers, rdims, agglev,
-                                 _agg._device_results_wanted() and _is_device_tensor(values) and not ds._was_xarray)
+                                 _agg._device_results_wanted() and _is_device_tensor(values) and not ds._was_xarray, compact=pos is not None)
         if res is None:
             raise ValueError("season=: the season totals of %r overflow the element type (the dense-family plan met +-inf)" % (variable,))
     except _engine.WaggError:
@@ -279,11 +327,12 @@ def _season_totals(ds, variable, aggwt, agglev, weights, backup_aggwt, lists, P,
     return (res[0] if single or edd is not None else res), rdims, _result_coords(ds, rdims, agglev, uniq), ds._was_xarray
 
 
-def _ladder_totals(ds, variable, aggwt, agglev, weights, backup_aggwt, lists, P, ladder, season, grid, time_values):
+def _ladder_totals(ds, variable, aggwt, agglev, weights, backup_aggwt, lists, P, ladder, season, grid, time_values, cells="all"):
     """Period totals of the degree days of ``variable`` (a degree-day variable; its own terms are ignored) at EVERY threshold of
     ``ladder``: summed first (``wagg_edd_ladder_reduce_*``, up to 64 thresholds a launch), then one apply per launch contracts
     its n_thr * P rows on whatever plan serves the table.  ``season`` None: every day counts.  Returns ``(stack, rdims, coords,
-    was_xarray)`` like :func:`_season_totals`, ``stack`` being the (n_thr, P | R, R | P) results in the ladder's order."""
+    was_xarray)`` like :func:`_season_totals`, ``stack`` being the (n_thr, P | R, R | P) results in the ladder's order.
+    ``cells="referenced"``: all of it on the packed rows of :func:`_referenced_rows`."""
     from . import periods as _periods
     values, dims = _gridded_field(ds, variable, P, "a degree-day ladder")
     edd = ds._edds.get(variable)
@@ -294,12 +343,19 @@ def _ladder_totals(ds, variable, aggwt, agglev, weights, backup_aggwt, lists, P,
     ia, io, *_ = _spatial_layout(dims)
     doy, win = (None, None) if season is None else _stored_season(ds, variable, season, grid, dims, shape, time_values)
     _engine.require_gpu()
-    Xd = _time_by_cell(values, dims)
-    plan = _plan_for(cell_idx, codes, w_eff, G, len(uniq), shape["lon"] if ia < io else shape["lat"],
-                     is_f32=str(Xd.dtype).endswith("float32"), layout="TG", prepared=prepared)
+    make_plan = lambda dtype: _plan_for(cell_idx, codes, w_eff, G, len(uniq), shape["lon"] if ia < io else shape["lat"],
+                                        is_f32=str(dtype).endswith("float32"), layout="TG", prepared=prepared)
+    Hd = pos = None
+    if cells == "referenced":
+        plan, Xd, Hd, pos = _referenced_rows(values, edd[0], dims, make_plan)
+        if pos is not None and win is not None:
+            win = win[pos]
+    else:
+        Xd = _time_by_cell(values, dims)
+        plan = make_plan(Xd.dtype)
     try:
         rb, rw = lists(Xd.device)
-        Hd = _time_by_cell(edd[0], dims)
+        Hd = _time_by_cell(edd[0], dims) if Hd is None else Hd
         if Hd.shape != Xd.shape or Hd.dtype != Xd.dtype:
             raise ValueError("tasmin and tasmax must have the same shape and dtype")
         rdims = _result_dims(dims, agglev)
@@ -311,7 +367,7 @@ def _ladder_totals(ds, variable, aggwt, agglev, weights, backup_aggwt, lists, P,
             if int(status.item()) & 1:
                 raise ValueError("degree-day ladder: a counted value of %r is +-inf; period totals of a ladder have no daily "
                                  "route that could give it the daily treatment" % (variable,))
-            got = _periods._contract(plan, field, P, len(uniq), None, None, rdims, agglev, keep_dev, planes=True)
+            got = _periods._contract(plan, field, P, len(uniq), None, None, rdims, agglev, keep_dev, planes=True, compact=pos is not None)
             if got is None:
                 raise ValueError("degree-day ladder: the totals of %r overflow the element type (the dense-family plan met "
                                  "+-inf)" % (variable,))

@@ -137,7 +137,7 @@ def tas_poly(ds, power, varname):
 
 
 def tas_poly_aggregate(ds, powers, aggwt, agglev, weights, varnames=None, backup_aggwt="areawt", period=None, _route=None,
-                       season=None):
+                       season=None, cells="all"):
     """``tas_poly`` for several powers followed by ``weighted_aggregate_grid_to_regions`` of each --
     as ONE pass over the temperature field (powers 1..4 of fp32 (time, lat, lon) data share a single
     read of the grid from HBM).  ``varnames`` defaults to ``tas-poly-<p>``.  Returns one Dataset
@@ -145,11 +145,17 @@ def tas_poly_aggregate(ds, powers, aggwt, agglev, weights, varnames=None, backup
     a label per remaining day; None: daily results as ever): every power summed over each period's days on the device, ``time``
     replaced by ``period`` (:func:`climate_toolbox_amd.periods.weighted_aggregate_grid_to_regions_periods`).  ``season`` (a
     growing-season mask, seasons.py; needs ``period``): only a cell's in-season days count, the days being those of the
-    365-day calendar left after the leap-day drop."""
+    365-day calendar left after the leap-day drop.  ``cells`` ("all" | "referenced"; needs ``period``): as for
+    :func:`climate_toolbox_amd.periods.weighted_aggregate_grid_to_regions_periods` -- "referenced" sums only the quads the
+    table references."""
     if season is not None and period is None:
         raise ValueError("season= needs period=: a growing-season total is a sum over days")
     if season is not None and _route is not None:
         raise ValueError("_route cannot be combined with season=: season totals always sum the field first")
+    from .periods import _check_cells
+    _check_cells(cells, _route)
+    if cells == "referenced" and period is None:
+        raise ValueError("cells='referenced' needs period=: it sums the field over each period first")
     powers = [int(p) for p in powers]
     if not powers or min(powers) < 1 or len(set(powers)) != len(powers):
         raise ValueError("powers must be distinct positive integers, got %r" % (powers,))
@@ -168,7 +174,7 @@ def tas_poly_aggregate(ds, powers, aggwt, agglev, weights, varnames=None, backup
     if period is not None:
         from . import periods
         return periods._aggregate_periods(re, varnames, aggwt, agglev, weights, backup_aggwt, period, day, powers=powers,
-                                          offset=-KELVIN, route=_route, season=season, grid=grid)
+                                          offset=-KELVIN, route=_route, season=season, grid=grid, cells=cells)
     res, rdims, coords, was_xr = _agg._aggregate_core(re, "tas", aggwt, agglev, weights, backup_aggwt,
                                                       powers=powers, offset=-KELVIN)
     return _agg._as_dataset(dict(zip(varnames, res)), rdims, coords, was_xr)
@@ -236,7 +242,7 @@ def _ladder_thresholds(thresholds):
 
 
 def snyder_edd_aggregate(ds, thresholds, aggwt, agglev, weights, tasmin="tasmin", tasmax="tasmax", varname="edd",
-                         backup_aggwt="areawt", period=None, season=None):
+                         backup_aggwt="areawt", period=None, season=None, cells="all"):
     """Snyder degree days at EVERY threshold of a ladder, aggregated to regions: the reference's agricultural product (what
     ``validate_edd_snyder_agriculture`` accepts), in one call -- ``snyder_edd`` of ``ds[tasmin]`` / ``ds[tasmax]`` (degrees C, or
     Kelvin fields shifted by ``convert_kelvin_to_celsius``; same checks: equal units, tasmin <= tasmax everywhere) for every
@@ -251,10 +257,17 @@ def snyder_edd_aggregate(ds, thresholds, aggwt, agglev, weights, tasmin="tasmin"
              per 64 thresholds (``wagg_edd_ladder_reduce_*``), and one apply contracts the n_thr x P rows -- whatever the plan;
              a (lat, lon, time) field is transposed on the device, a host-resident one uploaded whole.  A counted +-inf raises
              ValueError.  None: daily results, from the fused daily apply in groups of up to four thresholds.
-    season   a growing-season mask (seasons.py; needs ``period``): only a cell's in-season days count."""
+    season   a growing-season mask (seasons.py; needs ``period``): only a cell's in-season days count.
+    cells    "all" or "referenced" (needs ``period``): as for ``weighted_aggregate_grid_to_regions_periods`` -- "referenced" packs
+             both fields to the quads the table references, evaluates every threshold on those cells only and contracts through
+             the plan's quads-only cell table; a +-inf in a quad no table row reads is not seen."""
     thr = _ladder_thresholds(thresholds)
     if season is not None and period is None:
         raise ValueError("season= needs period=: a growing-season total is a sum over days")
+    from .periods import _check_cells
+    _check_cells(cells)
+    if cells == "referenced" and period is None:
+        raise ValueError("cells='referenced' needs period=: it sums the field over each period first")
     if isinstance(weights, str):
         weights = _agg.prepare_spatial_weights_data(weights)
     lo, hi = ds[tasmin], ds[tasmax]
@@ -282,7 +295,7 @@ def snyder_edd_aggregate(ds, thresholds, aggwt, agglev, weights, tasmin="tasmin"
             return cache[str(device)]
 
         res, rdims, coords, was_xr = seasons._ladder_totals(reindexed(base._values, base._edd[0]), varname, aggwt, agglev, weights,
-                                                            backup_aggwt, lists, len(labels), thr, season, grid, time_values)
+                                                            backup_aggwt, lists, len(labels), thr, season, grid, time_values, cells=cells)
         rdims = tuple("period" if d == "time" else d for d in rdims)
         coords = dict({k: v for k, v in coords.items() if k != "time"}, period=labels)
     else:

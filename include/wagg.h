@@ -82,7 +82,8 @@ typedef struct wagg_plan_info {
 
 /* ---- process / device ------------------------------------------------------------------- */
 int wagg_version(void);                 /* 10000*major + 100*minor + patch; 0.4.0: sized struct getters, wagg_apply_desc,
-                                           wagg_host_stats has 18 fields; 0.5.0: many-plans (wagg_plan_create_many) */
+                                           wagg_host_stats has 18 fields; 0.5.0: many-plans (wagg_plan_create_many);
+                                           0.9.0: packed rows (wagg_pack_rows_*, WAGG_APPLY_COMPACT_ROWS) */
 int wagg_device_count(void);            /* number of visible HIP devices (0 if none), never <0  */
 /* Time-axis sharding rule of the multi-GPU form (one process per GPU; climate_toolbox_amd/timeshard.py):
  * rank `rank` of `world` owns rows [*start, *stop) of T; the first T mod world ranks hold one row more. */
@@ -595,6 +596,11 @@ int wagg_dense_apply_sharded_f64(wagg_shard_group *g, wagg_dense *const *plans, 
  *                HOST): an fp32 full-form plan then runs the fp32 MFMA kernel, bit for bit what library 0.5.0 computed,
  *                instead of the default split form (f16 high + low parts of both operands, power-of-two scaled, fp32
  *                accumulation: DESIGN.md gives the error bound).  No effect on other forms or on fp64 plans.
+ *                WAGG_APPLY_COMPACT_ROWS (0.9.0): x holds PACKED rows (wagg_pack_rows_*: ldx >= Gq, field 0 of a row) instead of
+ *                grid rows.  A single segment-table plan that has the compact row for `elem`, WAGG_SRC_DEVICE, WAGG_LAYOUT_TG in,
+ *                WAGG_OUT_TR out, WAGG_XF_NONE only: the kernel of the lines-only host path reads the rows through the plan's
+ *                quads-only cell table -- the same cells in the same order as a plain apply of the unpacked rows, the same bits.
+ *                With anything else the bit is WAGG_EUNSUPPORTED.
  * A combination the library has no kernel path for returns WAGG_EUNSUPPORTED with a message that names it; nothing is
  * emulated.                                                                                                            */
 #define WAGG_PLAN_SEGMENT 0
@@ -607,6 +613,7 @@ int wagg_dense_apply_sharded_f64(wagg_shard_group *g, wagg_dense *const *plans, 
 #define WAGG_XF_POLY 1
 #define WAGG_XF_EDD 2
 #define WAGG_APPLY_EXACT_F32 0x10000
+#define WAGG_APPLY_COMPACT_ROWS 0x20000
 typedef struct wagg_apply_desc {
     uint64_t struct_size;
     int32_t plan_kind, elem, source, transform;
@@ -753,6 +760,39 @@ int wagg_edd_ladder_reduce_f64(const double *tasmin_dev, const double *tasmax_de
                                int flags, double *out_dev, int64_t ldo, int64_t out_pstride, int32_t *status_dev, void *work_dev,
                                int64_t work_bytes, void *stream);
 int64_t wagg_edd_ladder_work_bytes(int64_t n, int32_t P, int64_t n_rows, int n_thr);
+
+/* ---- packed rows: only the quads a segment table references, as a device matrix (0.9.0) ---------------------------------------
+ * A single segment-table plan with a whole-line chunking (wagg_plan_info.lines) knows the distinct aligned 4-cell QUADS of a
+ * grid row that hold a referenced cell (c2-real: a third of the row).  Its compact row lays them side by side in grid order:
+ * quad i of the sorted distinct referenced quads at positions 4i .. 4i + 3, Gq cells in all -- the row the lines-only host
+ * path ships (WAGG_HOST_LINES).  Here that row becomes a (T, Gq) device matrix of its own, for work that sums the field over
+ * time first: the row-list reductions above take it with n = Gq (a per-cell vector such as win_dev gathered through
+ * wagg_plan_compact_cells), and wagg_apply with WAGG_APPLY_COMPACT_ROWS contracts what they leave.  The map belongs to an
+ * element type (elem_bytes 4 / 8: the fp32 and fp64 chunkings differ in the quads they count as referenced).
+ *   wagg_plan_compact_info    *Gq = cells of the compact row; 0: the plan has none for that element type (region-shaped
+ *                             chunkings only, WAGG_PLAN_NO_LINES and the other kernel-form flags, many-plans)
+ *   wagg_plan_compact_cells   cell_of_pos_host[pos] = the grid cell at position pos, Gq values (WAGG_EUNSUPPORTED if Gq = 0)
+ *   wagg_pack_rows_*          out[t][pos] = X[t][cell_of_pos[pos]] for device-resident rows (ldx >= G).  With X2_dev (tasmax
+ *                             beside tasmin; same ldx) a packed row holds field 0 then field 1: out[t][Gq + pos] = X2[t][..],
+ *                             ldo >= 2 * Gq.  One 16-byte piece per lane; bases or pitches that are not 16-byte aligned take
+ *                             an element-wise kernel.  Asynchronous on `stream` (the first call of a plan and element type
+ *                             uploads the quad table, which blocks once).
+ *   wagg_pack_rows_host_*     the same from HOST arrays through the gather of the lines-only host path: host threads pack
+ *                             the quads, only they cross PCIe (wagg_host_stats.lines_h2d_bytes), every block is copied into
+ *                             its rows of out_dev.  Blocking.  Taken when the packed row is <= 80 % of the row, the field
+ *                             >= 64 MiB, at least ten packing threads can be had and the ring is free; otherwise
+ *                             WAGG_EUNSUPPORTED with nothing queued: the caller uploads the field and packs on the device.
+ *                             flags: 0 or WAGG_HOST_PIN (which has nothing to lock here: X is read by the CPU).           */
+int wagg_plan_compact_info(const wagg_plan *plan, int elem_bytes, int64_t *Gq);
+int wagg_plan_compact_cells(const wagg_plan *plan, int elem_bytes, int32_t *cell_of_pos_host /* Gq */);
+int wagg_pack_rows_f32(const wagg_plan *plan, const float *X_dev, const float *X2_dev /* NULL or tasmax */, int64_t T, int64_t ldx,
+                       float *out_dev, int64_t ldo, void *stream);
+int wagg_pack_rows_f64(const wagg_plan *plan, const double *X_dev, const double *X2_dev /* NULL or tasmax */, int64_t T, int64_t ldx,
+                       double *out_dev, int64_t ldo, void *stream);
+int wagg_pack_rows_host_f32(const wagg_plan *plan, const float *X_host, const float *X2_host, int64_t T, int64_t ldx, float *out_dev,
+                            int64_t ldo, int flags);
+int wagg_pack_rows_host_f64(const wagg_plan *plan, const double *X_host, const double *X2_host, int64_t T, int64_t ldx, double *out_dev,
+                            int64_t ldo, int flags);
 
 #ifdef __cplusplus
 }
