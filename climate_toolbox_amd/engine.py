@@ -858,7 +858,7 @@ def _season_vector(a, length, what, device):
 
 
 class _RowlistCall:
-    """What :func:`period_reduce`, :func:`season_reduce` and :func:`edd_ladder_reduce` do alike around their library call, in the
+    """What :func:`period_reduce`, :func:`season_reduce`, :func:`edd_ladder_reduce` and :func:`bin_days_reduce` do alike around their library call, in the
     order they do it: the row lists (and, with ``season = (doy, windows)``, those two vectors) as int32 CUDA tensors and ``P``;
     then ``out``, ``status`` and the workspace; at the end what must outlive the kernels on the caller's stream."""
 
@@ -1006,6 +1006,56 @@ def edd_ladder_reduce(tasmin, tasmax, row_begin, rows, offset, thresholds, doy=N
                   None if doy is None else C.c_void_p(c.windows.data_ptr()), float(offset), _np_ptr(thr, C.c_double), len(thr), c.flags,
                   C.c_void_p(out.data_ptr()), max(1, c.n), max(1, c.P * c.n), C.c_void_p(status.data_ptr()), work, wb,
                   _stream_handle(stream)), "wagg_edd_ladder_reduce")
+    c.done(stream)
+    return out, status
+
+
+def bin_thresholds(edges, offset, dtype):
+    """The thresholds ``wagg_bin_days_reduce_*`` compares the raw field against, restated: ``ceilT(edges[k] - offset)``, the
+    difference taken in fp64 and ``ceilT(c)`` the smallest value of ``dtype`` (float32 or float64) that is not below ``c`` --
+    ``float32(c)``, stepped up once where that lies below ``c``; infinities pass through.  For every ``x`` of ``dtype``,
+    ``x >= ceilT(c)`` holds exactly when ``float64(x) >= c``."""
+    c = np.asarray(edges, dtype=np.float64) - np.float64(offset)
+    if np.dtype(dtype) == np.float64:
+        return c
+    if np.dtype(dtype) != np.float32:
+        raise TypeError("dtype must be float32 or float64")
+    with np.errstate(over="ignore"):
+        f = c.astype(np.float32)                       # (to nearest; beyond the largest float: +-inf)
+    below = f.astype(np.float64) < c
+    return np.where(below, np.nextafter(f, np.float32(np.inf)), f).astype(np.float32)
+
+
+def bin_days_reduce(X, row_begin, rows, offset, edges, doy=None, windows=None, checked=False, out=None, status=None, workspace=None,
+                    stream=None):
+    """The days a cell spends in each temperature bin, per period, in ONE launch (``wagg_bin_days_reduce_*``): ``out[k, p, j]``
+    counts the rows ``t`` of period ``p`` on which cell ``j`` is in season and ``edges[k] <= X[t, j] + offset < edges[k + 1]``.
+    ``X``: a (T, n) CUDA tensor; ``edges``: 2 .. ``_lib.BIN_EDGES_MAX`` strictly ascending numbers, ``-inf`` allowed first and
+    ``+inf`` last (the kernel takes the bins ``_lib.BIN_GROUP`` at a time); ``row_begin`` / ``rows`` / ``doy`` / ``windows`` /
+    ``checked`` as for :func:`edd_ladder_reduce` (``doy`` and ``windows`` both None: no season).  The comparison is that of
+    :func:`bin_thresholds`: the raw value against ``ceilT(edges[k] - offset)``, so an fp32 field is binned as its exact values
+    would be in fp64.  NaN is in no bin, ``-inf`` only in a first bin open below, ``+inf`` in none.  ``workspace`` (None = True:
+    the library gets the scratch its ``*_work_bytes`` reports; False: none) never changes a count.  Returns ``(counts,
+    status)``: the (n_bins, P, n) tensor of ``X``'s dtype (exact in fp32 up to 2^24 days) and the status word (bit 0: an
+    in-season value was +-inf)."""
+    import torch
+    X = _check_X(X, "TG")
+    e = np.ascontiguousarray(np.atleast_1d(edges), dtype=np.float64)
+    if e.ndim != 1 or not 2 <= len(e) <= _lib.BIN_EDGES_MAX:
+        raise ValueError("2..%d bin edges per call, got %s" % (_lib.BIN_EDGES_MAX, e.shape))
+    if np.isnan(e).any() or not (e[1:] > e[:-1]).all():
+        raise ValueError("bin edges must ascend strictly and hold no NaN, got %r" % (e.tolist(),))
+    if (doy is None) != (windows is None):
+        raise ValueError("doy and windows go together: both given, or both None (no season)")
+    c = _RowlistCall(X, row_begin, rows, checked, None if doy is None else (doy, windows))
+    L = _lib.load()
+    out, status, work, wb = c.alloc(lambda n, P, n_rows, planes: L.wagg_bin_days_work_bytes(n, P, n_rows, planes + 1), len(e) - 1, out,
+                                    status, True if workspace is None else workspace)
+    fn = L.wagg_bin_days_reduce_f32 if X.dtype == torch.float32 else L.wagg_bin_days_reduce_f64
+    _lib.check(fn(C.c_void_p(X.data_ptr()), c.T, c.n, _ld(X), C.c_void_p(c.row_begin.data_ptr()), C.c_void_p(c.rows.data_ptr()), c.P,
+                  c.n_rows, None if doy is None else C.c_void_p(c.doy.data_ptr()), None if doy is None else C.c_void_p(c.windows.data_ptr()),
+                  float(offset), _np_ptr(e, C.c_double), len(e), c.flags, C.c_void_p(out.data_ptr()), max(1, c.n), max(1, c.P * c.n),
+                  C.c_void_p(status.data_ptr()), work, wb, _stream_handle(stream)), "wagg_bin_days_reduce")
     c.done(stream)
     return out, status
 

@@ -33,7 +33,7 @@ import numpy as np
 from . import aggregations as _agg, engine as _engine, minixr
 from ._labels import _exact_index
 from ._layout import _flatten_for_device, _is_device_tensor, _result_dims, _spatial_layout, _to_device
-from ._lib import EDD_LADDER_MAX as _EDD_LADDER_MAX, SEASON_INVERT, SEASON_NULL
+from ._lib import BIN_EDGES_MAX as _BIN_EDGES_MAX, EDD_LADDER_MAX as _EDD_LADDER_MAX, SEASON_INVERT, SEASON_NULL
 from ._plans import _drop_plan, _plan_for
 from ._prepared import PreparedWeights
 
@@ -371,6 +371,58 @@ def _ladder_totals(ds, variable, aggwt, agglev, weights, backup_aggwt, lists, P,
             if got is None:
                 raise ValueError("degree-day ladder: the totals of %r overflow the element type (the dense-family plan met "
                                  "+-inf)" % (variable,))
+            res.extend(got)
+    except _engine.WaggError:
+        _drop_plan(plan)
+        raise
+    finally:
+        plan._lease.release()
+    stack = _engine.require_gpu().stack(res) if keep_dev else np.stack(res)
+    return stack, rdims, _result_coords(ds, rdims, agglev, uniq), ds._was_xarray
+
+
+def _bin_totals(ds, variable, aggwt, agglev, weights, backup_aggwt, lists, P, edges, season, grid, time_values, cells="all"):
+    """Period totals of the days ``variable`` spends in every bin ``[edges[k], edges[k + 1])``: counted first
+    (``wagg_bin_days_reduce_*``, up to 64 bins a launch), then one apply per launch contracts its n_bins * P rows on whatever
+    plan serves the table.  ``variable``: a plain temperature variable, or one shifted by ``convert_kelvin_to_celsius`` (the
+    edges are then in degrees C); a power or a degree-day variable is ValueError.  ``season`` None: every day counts.  Returns
+    ``(stack, rdims, coords, was_xarray)`` like :func:`_ladder_totals`, ``stack`` being the (n_bins, P | R, R | P) results in
+    bin order.  ``cells="referenced"``: all of it on the packed rows of :func:`_referenced_rows`."""
+    from . import periods as _periods
+    values, dims = _gridded_field(ds, variable, P, "a bin count")
+    xform = ds._xforms.get(variable)
+    if ds._edds.get(variable) is not None or (xform is not None and xform[1] != 1):
+        raise ValueError("a bin count needs a plain (or Kelvin-shifted) temperature variable, got %r" % (variable,))
+    offset = 0.0 if xform is None else float(xform[0])
+    prepared, w_eff, uniq, codes, cell_idx, G = _segment_table(ds, variable, aggwt, agglev, weights, backup_aggwt)
+    shape = dict(zip(dims, tuple(values.shape)))
+    ia, io, *_ = _spatial_layout(dims)
+    doy, win = (None, None) if season is None else _stored_season(ds, variable, season, grid, dims, shape, time_values)
+    _engine.require_gpu()
+    make_plan = lambda dtype: _plan_for(cell_idx, codes, w_eff, G, len(uniq), shape["lon"] if ia < io else shape["lat"],
+                                        is_f32=str(dtype).endswith("float32"), layout="TG", prepared=prepared)
+    pos = None
+    if cells == "referenced":
+        plan, Xd, _, pos = _referenced_rows(values, None, dims, make_plan)
+        if pos is not None and win is not None:
+            win = win[pos]
+    else:
+        Xd = _time_by_cell(values, dims)
+        plan = make_plan(Xd.dtype)
+    try:
+        rb, rw = lists(Xd.device)
+        rdims = _result_dims(dims, agglev)
+        keep_dev = _agg._device_results_wanted() and _is_device_tensor(values) and not ds._was_xarray
+        res = []
+        for k0 in range(0, len(edges) - 1, _BIN_EDGES_MAX - 1):                  # (consecutive launches share an edge)
+            part = [float(e) for e in edges[k0:k0 + _BIN_EDGES_MAX]]
+            field, status = _engine.bin_days_reduce(Xd, rb, rw, offset, part, doy=doy, windows=win, checked=True)
+            if int(status.item()) & 1:
+                raise ValueError("bin count: a counted value of %r is +-inf; period totals of bins have no daily route that could "
+                                 "give it the daily treatment" % (variable,))
+            got = _periods._contract(plan, field, P, len(uniq), None, None, rdims, agglev, keep_dev, planes=True, compact=pos is not None)
+            if got is None:
+                raise ValueError("bin count: the totals of %r overflow the element type (the dense-family plan met +-inf)" % (variable,))
             res.extend(got)
     except _engine.WaggError:
         _drop_plan(plan)

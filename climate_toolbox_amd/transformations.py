@@ -23,8 +23,8 @@ import numpy as np
 from . import minixr
 from . import aggregations as _agg
 
-__all__ = ["tas_poly", "tas_poly_aggregate", "snyder_edd", "snyder_gdd", "snyder_edd_aggregate", "validate_edd_snyder_agriculture",
-           "ordinal", "remove_leap_days", "convert_kelvin_to_celsius"]
+__all__ = ["tas_poly", "tas_poly_aggregate", "snyder_edd", "snyder_gdd", "snyder_edd_aggregate", "tas_bins_aggregate",
+           "validate_edd_snyder_agriculture", "ordinal", "remove_leap_days", "convert_kelvin_to_celsius"]
 
 KELVIN = 273.15
 
@@ -318,6 +318,81 @@ def snyder_edd_aggregate(ds, thresholds, aggwt, agglev, weights, tasmin="tasmin"
             res = np.stack(planes)
     out = _agg._as_dataset({varname: res}, ("refTemp",) + tuple(rdims), dict(coords, refTemp=thr), was_xr)
     out[varname].attrs["units"] = units
+    return out
+
+
+def _bin_edges(edges):
+    """``edges`` as a float64 vector: at least two numbers, strictly ascending, no NaN (infinite ends allowed) -- else ValueError"""
+    try:
+        e = np.asarray(list(edges), dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError("edges must be a sequence of numbers, got %r" % (edges,)) from None
+    if e.ndim != 1 or len(e) < 2 or np.isnan(e).any() or not (e[1:] > e[:-1]).all():
+        raise ValueError("edges must be at least two strictly ascending numbers (-inf / +inf allowed at the ends), got %r" % (edges,))
+    return e
+
+
+def tas_bins_aggregate(ds, edges, aggwt, agglev, weights, tas="tas", varname="tas-bins", backup_aggwt="areawt", period="year",
+                       season=None, cells="all", leap_days="keep"):
+    """The days a cell's daily mean temperature spends in each bin ``[edges[k], edges[k + 1])``, summed per period (and growing
+    season) and aggregated to regions: the third temperature statistic of climate-impact regressions beside the polynomials
+    (:func:`tas_poly_aggregate`) and the degree days (:func:`snyder_edd_aggregate`), counted on the device in ONE pass per 64
+    bins (``wagg_bin_days_reduce_*``) instead of one masked grid per bin.
+
+    edges    at least two strictly ascending numbers, ``-inf`` allowed first and ``+inf`` last (open end bins), else ValueError;
+             in degrees C when ``ds[tas]`` carries the Kelvin shift of ``convert_kelvin_to_celsius``, otherwise in the field's own
+             units.  A value equal to an edge lands in the upper bin.  The comparison is exact: the raw value is compared
+             against ``edges[k] - offset`` rounded UP to the element type, so an fp32 Kelvin field is binned as its exact
+             values would be in fp64 (``engine.bin_thresholds``).  NaN is in no bin; a counted +-inf raises ValueError.
+    tas      the variable: a plain temperature field or a Kelvin-shifted one; a power (``tas_poly``) or a degree-day variable
+             is ValueError.
+    period   "year", "month" or a label per day, as for
+             :func:`~climate_toolbox_amd.periods.weighted_aggregate_grid_to_regions_periods`; required (None is ValueError: a
+             bin count is a sum over days).
+    season, cells   exactly as in :func:`snyder_edd_aggregate`.
+    leap_days   "keep" (the default) or "drop": ``remove_leap_days`` first, as ``tas_poly`` does.
+
+    Returns one Dataset with the variable ``varname`` of dims ``("bin", "period", agglev)`` (the last two in the order the
+    period call gives them), the coordinate ``bin`` = the lower edges as float64, ``attrs["units"] = "days"`` and
+    ``attrs["bin_edges"]`` = the edges as one string (``", ".join(repr(float(e)) ...)``); ``results_on_device()`` is honoured;
+    a (lat, lon, time) field is transposed on the device, a host-resident one uploaded whole (packed for "referenced")."""
+    e = _bin_edges(edges)
+    if period is None:
+        raise ValueError("tas_bins_aggregate needs period=: a bin count is a sum over days" +
+                         ("" if season is None else " (season= needs period=)"))
+    from .periods import _check_cells
+    _check_cells(cells)
+    if leap_days not in ("keep", "drop"):
+        raise ValueError("leap_days must be 'keep' or 'drop', got %r" % (leap_days,))
+    if isinstance(weights, str):
+        weights = _agg.prepare_spatial_weights_data(weights)
+    from . import periods, seasons
+    if "time" not in ds.coords:
+        raise ValueError("the dataset has no 'time' coordinate to form periods from")
+    if leap_days == "drop":
+        ds = remove_leap_days(ds)
+    var = ds[tas]
+    xform = getattr(var, "_xform", None)
+    if getattr(var, "_edd", None) is not None or (xform is not None and xform[1] != 1):
+        raise ValueError("a bin count needs a plain (or Kelvin-shifted) temperature variable, got %r" % (tas,))
+    time_values = np.asarray(ds.coords["time"].values)
+    labels, row_begin, rows = periods.period_rows(time_values, period)
+    grid = None if season is None else (np.asarray(ds.coords["lat"].values), np.asarray(ds.coords["lon"].values))
+    re = _agg._reindex_spatial_data_to_regions(minixr.Dataset({tas: var}, coords=dict(ds.coords)), weights)
+    cache = {}
+
+    def lists(device):
+        if str(device) not in cache:
+            cache[str(device)] = periods._engine.period_lists(row_begin, rows, len(time_values), device=device)
+        return cache[str(device)]
+
+    res, rdims, coords, was_xr = seasons._bin_totals(re, tas, aggwt, agglev, weights, backup_aggwt, lists, len(labels), e, season, grid,
+                                                     time_values, cells=cells)
+    rdims = tuple("period" if d == "time" else d for d in rdims)
+    coords = dict({k: v for k, v in coords.items() if k != "time"}, period=labels, bin=e[:-1].copy())
+    out = _agg._as_dataset({varname: res}, ("bin",) + tuple(rdims), coords, was_xr)
+    out[varname].attrs["units"] = "days"
+    out[varname].attrs["bin_edges"] = ", ".join(repr(float(x)) for x in e)
     return out
 
 

@@ -761,6 +761,38 @@ int wagg_edd_ladder_reduce_f64(const double *tasmin_dev, const double *tasmax_de
                                int64_t work_bytes, void *stream);
 int64_t wagg_edd_ladder_work_bytes(int64_t n, int32_t P, int64_t n_rows, int n_thr);
 
+/* ---- temperature bins: the days a cell spends in each bin, per period and season, in one pass (0.10.0) ------------------------
+ * out[k][p][j] = the number of rows t of period p's list on which cell j is in season and
+ * edges[k] <= X[t, j] + offset < edges[k + 1],  k = 0 .. n_edges - 2,  2 <= n_edges <= WAGG_BIN_EDGES_MAX (64 bins) -- one
+ * launch, the bins taken in groups of WAGG_BIN_GROUP.  Arguments as for wagg_edd_ladder_reduce_* with ONE field, except
+ *   edges              n_edges host doubles, strictly ascending; -inf may come first and +inf last (open end bins); a NaN edge,
+ *                      equal or descending edges are WAGG_EINVAL
+ *   offset             finite; the edges are in the units of X + offset (degrees C for a Kelvin field with offset -273.15)
+ *   flags              WAGG_PERIOD_ROWS_CHECKED only
+ *   out_dev            plane k (a bin) at out_dev + k * out_pstride, row p at + p * ldo (out_pstride >= P * ldo when n_edges > 2);
+ *                      the count as a value of the element type, exact in fp32 up to 2^24 days
+ *   work_dev           wagg_bin_days_work_bytes(n, P, n_rows, n_edges) bytes: what wagg_period_reduce_work_bytes reports for
+ *                      n_edges - 1 planes
+ * THE COMPARISON RULE: nothing is shifted in the element type.  The host forms c_k = edges[k] - offset in fp64 and the kernel
+ * compares the RAW X[t, j] against ceilT(c_k), the smallest value of the element type that is not below c_k (fp32: (float)c_k,
+ * stepped up once by nextafterf if that lies below c_k; infinities pass through).  For every representable x, x >= ceilT(c)
+ * holds exactly when (double)x >= c: an fp32 field is binned as its exact values would be in fp64, a value equal to an edge
+ * lands in the upper bin, and no value near an edge can flip.
+ * NaN is in no bin (S6: it counts 0).  -inf lands in a first bin that is open below (edges[0] = -inf) and nowhere else, +inf in
+ * no bin; an IN-SEASON +-inf sets bit 0 of status_dev.  A value out of season is never counted and sets no status; a piece
+ * none of whose cells is in season is not read.  Counts are integers: every split of a list, and every run, gives the same bits. */
+#define WAGG_BIN_EDGES_MAX 65
+#define WAGG_BIN_GROUP 8
+int wagg_bin_days_reduce_f32(const float *X_dev, int64_t T, int64_t n, int64_t ldx, const int32_t *row_begin_dev,
+                             const int32_t *rows_dev, int32_t P, int64_t n_rows, const int32_t *doy_dev, const int32_t *win_dev,
+                             double offset, const double *edges, int n_edges, int flags, float *out_dev, int64_t ldo,
+                             int64_t out_pstride, int32_t *status_dev, void *work_dev, int64_t work_bytes, void *stream);
+int wagg_bin_days_reduce_f64(const double *X_dev, int64_t T, int64_t n, int64_t ldx, const int32_t *row_begin_dev,
+                             const int32_t *rows_dev, int32_t P, int64_t n_rows, const int32_t *doy_dev, const int32_t *win_dev,
+                             double offset, const double *edges, int n_edges, int flags, double *out_dev, int64_t ldo,
+                             int64_t out_pstride, int32_t *status_dev, void *work_dev, int64_t work_bytes, void *stream);
+int64_t wagg_bin_days_work_bytes(int64_t n, int32_t P, int64_t n_rows, int n_edges);
+
 /* ---- packed rows: only the quads a segment table references, as a device matrix (0.9.0) ---------------------------------------
  * A single segment-table plan with a whole-line chunking (wagg_plan_info.lines) knows the distinct aligned 4-cell QUADS of a
  * grid row that hold a referenced cell (c2-real: a third of the row).  Its compact row lays them side by side in grid order:
