@@ -858,7 +858,7 @@ def _season_vector(a, length, what, device):
 
 
 class _RowlistCall:
-    """What :func:`period_reduce`, :func:`season_reduce`, :func:`edd_ladder_reduce` and :func:`bin_days_reduce` do alike around their library call, in the
+    """What :func:`period_reduce`, :func:`season_reduce`, :func:`edd_ladder_reduce`, :func:`bin_days_reduce` and :func:`hinge_reduce` do alike around their library call, in the
     order they do it: the row lists (and, with ``season = (doy, windows)``, those two vectors) as int32 CUDA tensors and ``P``;
     then ``out``, ``status`` and the workspace; at the end what must outlive the kernels on the caller's stream."""
 
@@ -1056,6 +1056,50 @@ def bin_days_reduce(X, row_begin, rows, offset, edges, doy=None, windows=None, c
                   c.n_rows, None if doy is None else C.c_void_p(c.doy.data_ptr()), None if doy is None else C.c_void_p(c.windows.data_ptr()),
                   float(offset), _np_ptr(e, C.c_double), len(e), c.flags, C.c_void_p(out.data_ptr()), max(1, c.n), max(1, c.P * c.n),
                   C.c_void_p(status.data_ptr()), work, wb, _stream_handle(stream)), "wagg_bin_days_reduce")
+    c.done(stream)
+    return out, status
+
+
+def hinge_reduce(X, row_begin, rows, offset, knots, power=1, side="above", tail=None, doy=None, windows=None, checked=False, out=None,
+                 status=None, workspace=None, stream=None):
+    """Truncated powers of a field about every knot of a list, summed per period, in ONE launch (``wagg_hinge_reduce_*``):
+    ``out[j, p, i]`` sums ``max(+-((X[t, i] + offset) - knots[j]), 0) ** power`` over the rows ``t`` of period ``p`` on which
+    cell ``i`` is in season; ``+`` for ``side="above"``, ``-`` for ``"below"``.  ``X``: a (T, n) CUDA tensor; ``knots``:
+    1 .. ``_lib.HINGE_MAX`` finite numbers in any order (the kernel takes them ``_lib.HINGE_GROUP`` at a time); ``power``: 1, 2
+    or 3; ``row_begin`` / ``rows`` / ``doy`` / ``windows`` / ``checked`` / ``workspace`` as for :func:`bin_days_reduce`.
+    ``tail=(tail_knots, a, b)``: two more knots and a coefficient pair per plane; plane ``j`` is then ``S_j + a[j] * S_A +
+    b[j] * S_B`` with the same sums at the tail knots, combined in fp64 before the cast (the restricted cubic spline).
+    The difference is formed in ``X``'s dtype, in the two roundings written above; powers are products in that dtype; sums are
+    fp64.  NaN counts 0.  Returns ``(planes, status)``: the (n_knots, P, n) tensor of ``X``'s dtype and the status word (bit 0:
+    an in-season value of the field was +-inf)."""
+    import torch
+    X = _check_X(X, "TG")
+    k = np.ascontiguousarray(np.atleast_1d(knots), dtype=np.float64)
+    if k.ndim != 1 or not 1 <= len(k) <= _lib.HINGE_MAX:
+        raise ValueError("1..%d knots per call, got %s" % (_lib.HINGE_MAX, k.shape))
+    if not np.isfinite(k).all():
+        raise ValueError("knots must be finite, got %r" % (k.tolist(),))
+    if power not in (1, 2, 3):
+        raise ValueError("power must be 1, 2 or 3, got %r" % (power,))
+    if side not in ("above", "below"):
+        raise ValueError("side must be 'above' or 'below', got %r" % (side,))
+    tk = ta = tb = None
+    if tail is not None:
+        tk, ta, tb = (np.ascontiguousarray(np.atleast_1d(v), dtype=np.float64) for v in tail)
+        if tk.shape != (2,) or ta.shape != k.shape or tb.shape != k.shape or not all(np.isfinite(v).all() for v in (tk, ta, tb)):
+            raise ValueError("tail must be (two knots, a coefficient per knot, a coefficient per knot), all finite")
+    if (doy is None) != (windows is None):
+        raise ValueError("doy and windows go together: both given, or both None (no season)")
+    c = _RowlistCall(X, row_begin, rows, checked, None if doy is None else (doy, windows))
+    L = _lib.load()
+    out, status, work, wb = c.alloc(L.wagg_hinge_work_bytes, len(k), out, status, True if workspace is None else workspace)
+    fn = L.wagg_hinge_reduce_f32 if X.dtype == torch.float32 else L.wagg_hinge_reduce_f64
+    dptr = lambda v: None if v is None else _np_ptr(v, C.c_double)
+    _lib.check(fn(C.c_void_p(X.data_ptr()), c.T, c.n, _ld(X), C.c_void_p(c.row_begin.data_ptr()), C.c_void_p(c.rows.data_ptr()), c.P,
+                  c.n_rows, None if doy is None else C.c_void_p(c.doy.data_ptr()), None if doy is None else C.c_void_p(c.windows.data_ptr()),
+                  float(offset), _np_ptr(k, C.c_double), len(k), int(power), _lib.HINGE_ABOVE if side == "above" else _lib.HINGE_BELOW,
+                  dptr(tk), dptr(ta), dptr(tb), c.flags, C.c_void_p(out.data_ptr()), max(1, c.n), max(1, c.P * c.n),
+                  C.c_void_p(status.data_ptr()), work, wb, _stream_handle(stream)), "wagg_hinge_reduce")
     c.done(stream)
     return out, status
 

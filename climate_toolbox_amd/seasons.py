@@ -33,7 +33,7 @@ import numpy as np
 from . import aggregations as _agg, engine as _engine, minixr
 from ._labels import _exact_index
 from ._layout import _flatten_for_device, _is_device_tensor, _result_dims, _spatial_layout, _to_device
-from ._lib import BIN_EDGES_MAX as _BIN_EDGES_MAX, EDD_LADDER_MAX as _EDD_LADDER_MAX, SEASON_INVERT, SEASON_NULL
+from ._lib import BIN_EDGES_MAX as _BIN_EDGES_MAX, EDD_LADDER_MAX as _EDD_LADDER_MAX, HINGE_MAX as _HINGE_MAX, SEASON_INVERT, SEASON_NULL
 from ._plans import _drop_plan, _plan_for
 from ._prepared import PreparedWeights
 
@@ -423,6 +423,62 @@ def _bin_totals(ds, variable, aggwt, agglev, weights, backup_aggwt, lists, P, ed
             got = _periods._contract(plan, field, P, len(uniq), None, None, rdims, agglev, keep_dev, planes=True, compact=pos is not None)
             if got is None:
                 raise ValueError("bin count: the totals of %r overflow the element type (the dense-family plan met +-inf)" % (variable,))
+            res.extend(got)
+    except _engine.WaggError:
+        _drop_plan(plan)
+        raise
+    finally:
+        plan._lease.release()
+    stack = _engine.require_gpu().stack(res) if keep_dev else np.stack(res)
+    return stack, rdims, _result_coords(ds, rdims, agglev, uniq), ds._was_xarray
+
+
+def _hinge_totals(ds, variable, aggwt, agglev, weights, backup_aggwt, lists, P, knots, power, side, tail, season, grid, time_values,
+                  cells="all"):
+    """Period totals of the hinges ``max(+-(variable - knots[j]), 0) ** power`` at EVERY knot: summed first
+    (``wagg_hinge_reduce_*``, up to 64 knots a launch), then one apply per launch contracts its n_knots * P rows on whatever
+    plan serves the table.  ``variable``: a plain temperature variable, or one shifted by ``convert_kelvin_to_celsius`` (the
+    knots are then in degrees C and the shift is the kernel's offset); a power or a degree-day variable is ValueError.
+    ``tail``: None, or ``(two tail knots, a, b)`` with a coefficient per knot (``engine.hinge_reduce``).  ``season`` None: every
+    day counts.  Returns ``(stack, rdims, coords, was_xarray)`` like :func:`_bin_totals`, ``stack`` being the (n_knots, P | R,
+    R | P) results in the knots' order.  ``cells="referenced"``: all of it on the packed rows of :func:`_referenced_rows`."""
+    from . import periods as _periods
+    values, dims = _gridded_field(ds, variable, P, "a hinge total")
+    xform = ds._xforms.get(variable)
+    if ds._edds.get(variable) is not None or (xform is not None and xform[1] != 1):
+        raise ValueError("a hinge total needs a plain (or Kelvin-shifted) temperature variable, got %r" % (variable,))
+    offset = 0.0 if xform is None else float(xform[0])
+    prepared, w_eff, uniq, codes, cell_idx, G = _segment_table(ds, variable, aggwt, agglev, weights, backup_aggwt)
+    shape = dict(zip(dims, tuple(values.shape)))
+    ia, io, *_ = _spatial_layout(dims)
+    doy, win = (None, None) if season is None else _stored_season(ds, variable, season, grid, dims, shape, time_values)
+    _engine.require_gpu()
+    make_plan = lambda dtype: _plan_for(cell_idx, codes, w_eff, G, len(uniq), shape["lon"] if ia < io else shape["lat"],
+                                        is_f32=str(dtype).endswith("float32"), layout="TG", prepared=prepared)
+    pos = None
+    if cells == "referenced":
+        plan, Xd, _, pos = _referenced_rows(values, None, dims, make_plan)
+        if pos is not None and win is not None:
+            win = win[pos]
+    else:
+        Xd = _time_by_cell(values, dims)
+        plan = make_plan(Xd.dtype)
+    try:
+        rb, rw = lists(Xd.device)
+        rdims = _result_dims(dims, agglev)
+        keep_dev = _agg._device_results_wanted() and _is_device_tensor(values) and not ds._was_xarray
+        res = []
+        for k0 in range(0, len(knots), _HINGE_MAX):
+            sl = slice(k0, k0 + _HINGE_MAX)
+            part = None if tail is None else (tail[0], tail[1][sl], tail[2][sl])
+            field, status = _engine.hinge_reduce(Xd, rb, rw, offset, [float(k) for k in knots[sl]], power=power, side=side, tail=part,
+                                                 doy=doy, windows=win, checked=True)
+            if int(status.item()) & 1:
+                raise ValueError("hinge total: a counted value of %r is +-inf; period totals of hinges have no daily route that "
+                                 "could give it the daily treatment" % (variable,))
+            got = _periods._contract(plan, field, P, len(uniq), None, None, rdims, agglev, keep_dev, planes=True, compact=pos is not None)
+            if got is None:
+                raise ValueError("hinge total: the totals of %r overflow the element type (the dense-family plan met +-inf)" % (variable,))
             res.extend(got)
     except _engine.WaggError:
         _drop_plan(plan)

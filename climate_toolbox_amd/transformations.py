@@ -24,6 +24,7 @@ from . import minixr
 from . import aggregations as _agg
 
 __all__ = ["tas_poly", "tas_poly_aggregate", "snyder_edd", "snyder_gdd", "snyder_edd_aggregate", "tas_bins_aggregate",
+           "tas_hinge_aggregate", "tas_rcspline_aggregate",
            "validate_edd_snyder_agriculture", "ordinal", "remove_leap_days", "convert_kelvin_to_celsius"]
 
 KELVIN = 273.15
@@ -393,6 +394,132 @@ def tas_bins_aggregate(ds, edges, aggwt, agglev, weights, tas="tas", varname="ta
     out = _agg._as_dataset({varname: res}, ("bin",) + tuple(rdims), coords, was_xr)
     out[varname].attrs["units"] = "days"
     out[varname].attrs["bin_edges"] = ", ".join(repr(float(x)) for x in e)
+    return out
+
+
+def _hinge_call(name, ds, knots, tail, power, side, aggwt, agglev, weights, tas, backup_aggwt, period, season, cells, leap_days):
+    """what :func:`tas_hinge_aggregate` and :func:`tas_rcspline_aggregate` do alike behind their own checks of the knots: the
+    remaining argument checks, the period lists and ``seasons._hinge_totals``.  Returns ``(stack, rdims, coords, was_xarray,
+    units)`` with "time" already renamed to "period"."""
+    if power not in (1, 2, 3):
+        raise ValueError("power must be 1, 2 or 3, got %r" % (power,))
+    if side not in ("above", "below"):
+        raise ValueError("side must be 'above' or 'below', got %r" % (side,))
+    if period is None:
+        raise ValueError("%s needs period=: a hinge total is a sum over days" % name + ("" if season is None else " (season= needs period=)"))
+    from .periods import _check_cells
+    _check_cells(cells)
+    if leap_days not in ("keep", "drop"):
+        raise ValueError("leap_days must be 'keep' or 'drop', got %r" % (leap_days,))
+    if isinstance(weights, str):
+        weights = _agg.prepare_spatial_weights_data(weights)
+    from . import periods, seasons
+    if "time" not in ds.coords:
+        raise ValueError("the dataset has no 'time' coordinate to form periods from")
+    if leap_days == "drop":
+        ds = remove_leap_days(ds)
+    var = ds[tas]
+    xform = getattr(var, "_xform", None)
+    if getattr(var, "_edd", None) is not None or (xform is not None and xform[1] != 1):
+        raise ValueError("a hinge total needs a plain (or Kelvin-shifted) temperature variable, got %r" % (tas,))
+    time_values = np.asarray(ds.coords["time"].values)
+    labels, row_begin, rows = periods.period_rows(time_values, period)
+    grid = None if season is None else (np.asarray(ds.coords["lat"].values), np.asarray(ds.coords["lon"].values))
+    re = _agg._reindex_spatial_data_to_regions(minixr.Dataset({tas: var}, coords=dict(ds.coords)), weights)
+    cache = {}
+
+    def lists(device):
+        if str(device) not in cache:
+            cache[str(device)] = periods._engine.period_lists(row_begin, rows, len(time_values), device=device)
+        return cache[str(device)]
+
+    res, rdims, coords, was_xr = seasons._hinge_totals(re, tas, aggwt, agglev, weights, backup_aggwt, lists, len(labels), knots, power,
+                                                       side, tail, season, grid, time_values, cells=cells)
+    rdims = tuple("period" if d == "time" else d for d in rdims)
+    coords = dict({k: v for k, v in coords.items() if k != "time"}, period=labels)
+    return res, rdims, coords, was_xr, _units(var)
+
+
+def tas_hinge_aggregate(ds, knots, aggwt, agglev, weights, power=1, side="above", tas="tas", varname="tas-hinge", backup_aggwt="areawt",
+                        period="year", season=None, cells="all", leap_days="keep"):
+    """Truncated powers of a cell's daily temperature about every knot of a list, ``max(+-(tas - k), 0) ** power``, summed per
+    period (and growing season) and aggregated to regions: the fourth temperature statistic of climate-impact regressions
+    beside the polynomials (:func:`tas_poly_aggregate`), the Snyder degree days (:func:`snyder_edd_aggregate`) and the bins
+    (:func:`tas_bins_aggregate`), evaluated on the device in ONE pass per 64 knots (``wagg_hinge_reduce_*``) instead of one
+    clamped grid per knot.  With ``power=1`` on the daily mean these are the plain degree days of the energy sector: cooling
+    degree days are side ``"above"`` (``max(tas - k, 0)``), heating degree days are side ``"below"`` (``max(k - tas, 0)``);
+    ``power=1`` at several knots is a linear spline; ``power=3`` gives the truncated cubes of a cubic spline
+    (:func:`tas_rcspline_aggregate` combines them into the restricted one).
+
+    knots    a non-empty sequence of distinct finite numbers, in any order, else ValueError; in degrees C when ``ds[tas]``
+             carries the Kelvin shift of ``convert_kelvin_to_celsius``, otherwise in the field's own units.  More than 64 knots
+             go in several launches.  The difference ``d = (tas + offset) - k`` is formed in the element type, so an fp32
+             Kelvin field carries up to one ulp of the Kelvin value (3e-5 K) into a hinge -- unlike the bins' exact
+             comparison; powers are products in the element type, sums over days are fp64.  NaN counts 0; a counted +-inf
+             raises ValueError.
+    power    1, 2 or 3;  side: "above" or "below" -- else ValueError.
+    tas      the variable: a plain temperature field or a Kelvin-shifted one; a power (``tas_poly``) or a degree-day variable
+             is ValueError.
+    period   "year", "month" or a label per day, as for
+             :func:`~climate_toolbox_amd.periods.weighted_aggregate_grid_to_regions_periods`; required (None is ValueError).
+    season, cells, leap_days   exactly as in :func:`tas_bins_aggregate`.
+
+    Returns one Dataset with the variable ``varname`` of dims ``("knot", "period", agglev)`` (the last two in the order the
+    period call gives them), the coordinate ``knot`` = the knots as float64 in the caller's order, ``attrs["units"]`` =
+    ``"degreedays_" + units`` for ``power == 1`` and ``units + "^" + str(power)`` otherwise, and ``attrs["side"]``;
+    ``results_on_device()`` is honoured; a (lat, lon, time) field is transposed on the device, a host-resident one uploaded
+    whole (packed for "referenced")."""
+    k = _ladder_thresholds(knots)
+    res, rdims, coords, was_xr, units = _hinge_call("tas_hinge_aggregate", ds, k, None, power, side, aggwt, agglev, weights, tas,
+                                                    backup_aggwt, period, season, cells, leap_days)
+    out = _agg._as_dataset({varname: res}, ("knot",) + tuple(rdims), dict(coords, knot=k), was_xr)
+    out[varname].attrs["units"] = "degreedays_{}".format(units) if power == 1 else "{}^{}".format(units, power)
+    out[varname].attrs["side"] = side
+    return out
+
+
+def _rcspline_knots(knots):
+    """``knots`` as a float64 vector: 3 to 66 strictly ascending finite numbers -- else ValueError"""
+    try:
+        t = np.asarray(list(knots), dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError("knots must be a sequence of numbers, got %r" % (knots,)) from None
+    if t.ndim != 1 or not 3 <= len(t) <= 66 or not np.isfinite(t).all() or not (t[1:] > t[:-1]).all():
+        raise ValueError("knots must be 3 to 66 strictly ascending finite numbers, got %r" % (knots,))
+    return t
+
+
+def tas_rcspline_aggregate(ds, knots, aggwt, agglev, weights, tas="tas", varname="tas-rcspline", normalize=False, backup_aggwt="areawt",
+                           period="year", season=None, cells="all", leap_days="keep"):
+    """The nonlinear terms of a restricted (natural) cubic spline of a cell's daily temperature, summed per period (and growing
+    season) and aggregated to regions -- the usual alternative to the fourth-order polynomial.  For knots ``t_1 < ... < t_K``
+    the ``K - 2`` terms are, with ``u+ = max(u, 0)``,
+
+        term_j = (x - t_j)+^3 - (x - t_{K-1})+^3 * (t_K - t_j) / (t_K - t_{K-1}) + (x - t_K)+^3 * (t_{K-1} - t_j) / (t_K - t_{K-1})
+
+    for ``j = 1 .. K - 2``: each is 0 below ``t_1`` and linear beyond ``t_K``.  ONE kernel call serves all terms: the cubes at
+    the last two knots are summed beside those of every ``t_j`` and combined with them in fp64 before the cast
+    (``wagg_hinge_reduce_*`` with its tail), so the cancellation beyond the last knot never happens in fp32.  The spline's
+    linear term is :func:`tas_poly` with power 1 (``tas_poly_aggregate(..., powers=[1])``): it is not repeated here.
+
+    knots      3 to 66 strictly ascending finite numbers, else ValueError; units as for :func:`tas_hinge_aggregate`.
+    normalize  True: every term is divided by ``(t_K - t_1) ** 2`` (Harrell's scaling, which puts the terms on the scale of x; applied
+               to the results as one multiplication by the reciprocal).
+    everything else as for :func:`tas_hinge_aggregate` (the differences are formed in the element type there as here).
+
+    Returns one Dataset with the variable ``varname`` of dims ``("term", "period", agglev)``, the coordinate ``term`` =
+    ``knots[:-2]`` as float64, ``attrs["units"] = units + "^3"`` and ``attrs["knots"]`` = the knots as one string
+    (``", ".join(repr(float(t)) ...)``)."""
+    t = _rcspline_knots(knots)
+    span = t[-1] - t[-2]
+    ca, cb = -(t[-1] - t[:-2]) / span, (t[-2] - t[:-2]) / span
+    res, rdims, coords, was_xr, units = _hinge_call("tas_rcspline_aggregate", ds, t[:-2], (t[-2:].copy(), ca, cb), 3, "above", aggwt,
+                                                    agglev, weights, tas, backup_aggwt, period, season, cells, leap_days)
+    if normalize:                                                    # (one multiplication: the same bits from a host array and a device tensor)
+        res = res * (1.0 / float((t[-1] - t[0]) ** 2))
+    out = _agg._as_dataset({varname: res}, ("term",) + tuple(rdims), dict(coords, term=t[:-2].copy()), was_xr)
+    out[varname].attrs["units"] = "{}^3".format(units)
+    out[varname].attrs["knots"] = ", ".join(repr(float(x)) for x in t)
     return out
 
 

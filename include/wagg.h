@@ -793,6 +793,45 @@ int wagg_bin_days_reduce_f64(const double *X_dev, int64_t T, int64_t n, int64_t 
                              int64_t out_pstride, int32_t *status_dev, void *work_dev, int64_t work_bytes, void *stream);
 int64_t wagg_bin_days_work_bytes(int64_t n, int32_t P, int64_t n_rows, int n_edges);
 
+/* ---- hinges: truncated powers of the daily value about a knot, per period and season, in one pass (0.11.0) --------------------
+ * out[j][p][i] = sum over the rows t of period p, IN LIST ORDER, on which cell i is in season, of
+ * h(X[t, i]; knots[j]),  h(x; k) = max(+-((x + offset) - k), 0)^power,  j = 0 .. n_knots - 1,  1 <= n_knots <= WAGG_HINGE_MAX --
+ * one launch, the knots taken in groups of WAGG_HINGE_GROUP.  power 1 on a daily mean: cooling (WAGG_HINGE_ABOVE) / heating
+ * (WAGG_HINGE_BELOW) degree days; power 1 at several knots: a linear spline; power 3: the terms of a restricted cubic spline.
+ * Arguments as for wagg_bin_days_reduce_*, except
+ *   knots              n_knots finite host doubles in any order, converted to the element type; in the units of X + offset
+ *   power              1..3;  side: WAGG_HINGE_ABOVE (+) or WAGG_HINGE_BELOW (-)
+ *   tail_knots, tail_a, tail_b   all NULL: no tail.  Otherwise two finite knots kA, kB and n_knots finite coefficients each: plane
+ *                      j leaves the kernel as (S_j + tail_a[j] * S_A) + tail_b[j] * S_B, S_A / S_B being the same sums at kA / kB
+ *                      -- formed in fp64, per part of a split list, before the cast to the element type (the restricted cubic
+ *                      spline's cancellation beyond its last knot then happens among fp64 sums)
+ *   flags              WAGG_PERIOD_ROWS_CHECKED only (no keep-NaN form)
+ *   out_dev            plane j (a knot) at out_dev + j * out_pstride, row p at + p * ldo (out_pstride >= P * ldo when n_knots > 1)
+ *   work_dev           wagg_hinge_work_bytes(n, P, n_rows, n_knots) bytes: what wagg_bin_days_work_bytes reports for as many planes
+ * THE ARITHMETIC: d = (X[t, i] + offset) - knot in the element type, in exactly these two roundings (offset and knot converted
+ * to the element type first; nothing is contracted), negated for WAGG_HINGE_BELOW; the term is d > 0 ? d^power : 0 with
+ * d^2 = d * d and d^3 = (d * d) * d in the element type; sums are fp64.  An fp32 Kelvin field carries up to one ulp of the
+ * Kelvin value (3e-5 K) into d -- unlike the bins' exact comparison.  NaN gives 0 (S6).  An IN-SEASON +-inf of the field sets
+ * bit 0 of status_dev, whichever side is asked for; a value out of season reaches neither a sum nor the status word; a piece
+ * none of whose cells is in season is not read.  BIT-EQUALITY: when every call gets the workspace its own wagg_hinge_work_bytes
+ * reports, plane j of a many-knot call is bit for bit the plane of the call with knots[j] (and its coefficients) alone, and an
+ * all-year window for every cell gives the bits of the call with doy_dev = win_dev = NULL.                                      */
+#define WAGG_HINGE_MAX 64
+#define WAGG_HINGE_GROUP 8
+#define WAGG_HINGE_ABOVE 0
+#define WAGG_HINGE_BELOW 1
+int wagg_hinge_reduce_f32(const float *X_dev, int64_t T, int64_t n, int64_t ldx, const int32_t *row_begin_dev,
+                          const int32_t *rows_dev, int32_t P, int64_t n_rows, const int32_t *doy_dev, const int32_t *win_dev,
+                          double offset, const double *knots, int n_knots, int power, int side, const double *tail_knots,
+                          const double *tail_a, const double *tail_b, int flags, float *out_dev, int64_t ldo, int64_t out_pstride,
+                          int32_t *status_dev, void *work_dev, int64_t work_bytes, void *stream);
+int wagg_hinge_reduce_f64(const double *X_dev, int64_t T, int64_t n, int64_t ldx, const int32_t *row_begin_dev,
+                          const int32_t *rows_dev, int32_t P, int64_t n_rows, const int32_t *doy_dev, const int32_t *win_dev,
+                          double offset, const double *knots, int n_knots, int power, int side, const double *tail_knots,
+                          const double *tail_a, const double *tail_b, int flags, double *out_dev, int64_t ldo, int64_t out_pstride,
+                          int32_t *status_dev, void *work_dev, int64_t work_bytes, void *stream);
+int64_t wagg_hinge_work_bytes(int64_t n, int32_t P, int64_t n_rows, int n_knots);
+
 /* ---- packed rows: only the quads a segment table references, as a device matrix (0.9.0) ---------------------------------------
  * A single segment-table plan with a whole-line chunking (wagg_plan_info.lines) knows the distinct aligned 4-cell QUADS of a
  * grid row that hold a referenced cell (c2-real: a third of the row).  Its compact row lays them side by side in grid order:
