@@ -126,62 +126,31 @@ bin_days_kernel(const T *__restrict__ X, RowlistShape sh, const int32_t *__restr
     if (__ballot(saw_inf) != 0ull && (threadIdx.x & 63) == 0) atomicOr(status, 1);
 }
 
-template <typename T, int VEC>
-static void launch_bins(const T *X, const RowlistShape &sh, const int32_t *row_begin, const int32_t *rows, const int32_t *doy,
-                        const int32_t *win, const BinThresholds<T> &xf, T *out, int64_t ldo, int64_t pstride, double *work, int32_t *status,
-                        hipStream_t st) {
-    const dim3 grid((unsigned)((int64_t)sh.n_colblk * sh.P * sh.split * sh.aux)), block(RL_BLOCK);
-    const bool season = doy != nullptr;
-#define WAGG_BD_LAUNCH(SEASON)                                                                                                       \
-    do {                                                                                                                             \
-        if (sh.split > 1)                                                                                                            \
-            hipLaunchKernelGGL((bin_days_kernel<T, VEC, SEASON, double>), grid, block, 0, st, X, sh, row_begin, rows, doy, win, xf, work,  \
-                               sh.n, (int64_t)sh.P * sh.n, status);                                                                  \
-        else                                                                                                                         \
-            hipLaunchKernelGGL((bin_days_kernel<T, VEC, SEASON, T>), grid, block, 0, st, X, sh, row_begin, rows, doy, win, xf, out, ldo,   \
-                               pstride, status);                                                                                     \
-    } while (0)
-    if (season) WAGG_BD_LAUNCH(true);
-    else WAGG_BD_LAUNCH(false);
-#undef WAGG_BD_LAUNCH
-}
-
 template <typename T>
-static int bin_days_reduce(const T *X, int64_t Ttot, int64_t n, int64_t ldx, const int32_t *row_begin, const int32_t *rows, int32_t P,
-                           int64_t n_rows, const int32_t *doy, const int32_t *win, double offset, const double *edges, int n_edges,
-                           int flags, T *out, int64_t ldo, int64_t pstride, int32_t *status, void *work, int64_t work_bytes, void *stream) {
-    clear_error();
-    WAGG_TRY(rowlist_require_sizes(Ttot, n, P, n_rows));
-    WAGG_REQUIRE((flags & ~WAGG_PERIOD_ROWS_CHECKED) == 0, "unknown flags 0x%x (a bin count has no keep-NaN form)", flags);
-    WAGG_REQUIRE(n_edges >= 2 && n_edges <= WAGG_BIN_EDGES_MAX, "n_edges must be 2..%d, got %d", WAGG_BIN_EDGES_MAX, n_edges);
-    WAGG_REQUIRE(edges != nullptr, "edges is NULL");
-    WAGG_REQUIRE(std::isfinite(offset), "offset must be finite");
-    for (int k = 0; k < n_edges; ++k) {
-        WAGG_REQUIRE(edges[k] == edges[k], "edge %d is NaN", k);
-        WAGG_REQUIRE(k == 0 || edges[k] > edges[k - 1], "edges must ascend strictly (edge %d does not exceed edge %d)", k, k - 1);
-    }
-    WAGG_REQUIRE((doy == nullptr) == (win == nullptr), "doy_dev and win_dev go together: both given, or both NULL (no season)");
-    const int n_bins = n_edges - 1;
-    WAGG_TRY(rowlist_require_layout(n, ldx, ldo, P, n_bins, pstride, work, work_bytes, status, row_begin, rows, n_rows));
-    if (P == 0 || n == 0) return WAGG_OK;
-    WAGG_REQUIRE(out != nullptr, "NULL pointer (out_dev)");
-    WAGG_REQUIRE(n_rows == 0 || Ttot == 0 || X != nullptr, "NULL pointer (X_dev)");
-    hipStream_t st = (hipStream_t)stream;
-    WAGG_TRY(rowlist_check_rows(row_begin, P, rows, n_rows, Ttot, flags, st));
-    RowlistShape sh;
-    sh.T = Ttot; sh.n = n; sh.ldx = ldx; sh.n_rows = n_rows; sh.P = P;
-    sh.aux = (n_bins + BD_G - 1) / BD_G;                         // bin groups
-    bool wide;
-    WAGG_REQUIRE(rowlist_geometry(sh, wide, (int)sizeof(T), X, nullptr, n_bins, work, work_bytes, sh.aux),
-                 "too many pieces x periods x groups for one launch");
-    BinThresholds<T> xf;
-    xf.n_edges = n_edges;
-    for (int k = 0; k < WAGG_BIN_EDGES_MAX; ++k) xf.c[k] = ceil_to<T>(edges[k < n_edges ? k : n_edges - 1] - offset);
-    double *w = static_cast<double *>(work);
-    if (wide) launch_bins<T, 16 / (int)sizeof(T)>(X, sh, row_begin, rows, doy, win, xf, out, ldo, pstride, w, status, st);
-    else launch_bins<T, 1>(X, sh, row_begin, rows, doy, win, xf, out, ldo, pstride, w, status, st);
-    WAGG_HIP(hipGetLastError());
-    return rowlist_finish<T>(w, sh.split, n_bins, P, n, out, ldo, pstride, st);
+static int bin_days_reduce(const GroupedArgs<T> &a, double offset, const double *edges, int n_edges) {
+    static const GroupedFamily fam = {"a bin count", "X_dev", 1, BD_G};
+    return grouped_reduce<T>(
+        fam, a, (int)((int64_t)n_edges - 1),                         // (the bins; not looked at unless n_edges passes the check)
+        [&]() -> int {
+            WAGG_REQUIRE(n_edges >= 2 && n_edges <= WAGG_BIN_EDGES_MAX, "n_edges must be 2..%d, got %d", WAGG_BIN_EDGES_MAX, n_edges);
+            WAGG_REQUIRE(edges != nullptr, "edges is NULL");
+            WAGG_REQUIRE(std::isfinite(offset), "offset must be finite");
+            for (int k = 0; k < n_edges; ++k) {
+                WAGG_REQUIRE(edges[k] == edges[k], "edge %d is NaN", k);
+                WAGG_REQUIRE(k == 0 || edges[k] > edges[k - 1], "edges must ascend strictly (edge %d does not exceed edge %d)", k, k - 1);
+            }
+            return WAGG_OK;
+        },
+        [&](const RowlistShape &sh, bool wide, hipStream_t st) {
+            BinThresholds<T> xf;
+            xf.n_edges = n_edges;
+            for (int k = 0; k < WAGG_BIN_EDGES_MAX; ++k) xf.c[k] = ceil_to<T>(edges[k < n_edges ? k : n_edges - 1] - offset);
+            grouped_launch<T>(sh, wide, a, [&](auto vec, auto season, dim3 grid, auto *out, int64_t ldo, int64_t pstride) {
+                using DST = std::remove_pointer_t<decltype(out)>;
+                hipLaunchKernelGGL((bin_days_kernel<T, decltype(vec)::value, decltype(season)::value, DST>), grid, dim3(RL_BLOCK), 0, st,
+                                   a.X, sh, a.row_begin, a.rows, a.doy, a.win, xf, out, ldo, pstride, a.status);
+            });
+        });
 }
 
 }  // namespace wagg
@@ -194,13 +163,13 @@ extern "C" int wagg_bin_days_reduce_f32(const float *X_dev, int64_t T, int64_t n
                                         const int32_t *rows_dev, int32_t P, int64_t n_rows, const int32_t *doy_dev, const int32_t *win_dev,
                                         double offset, const double *edges, int n_edges, int flags, float *out_dev, int64_t ldo,
                                         int64_t out_pstride, int32_t *status_dev, void *work_dev, int64_t work_bytes, void *stream) {
-    return wagg::bin_days_reduce<float>(X_dev, T, n, ldx, row_begin_dev, rows_dev, P, n_rows, doy_dev, win_dev, offset, edges, n_edges,
-                                        flags, out_dev, ldo, out_pstride, status_dev, work_dev, work_bytes, stream);
+    return wagg::bin_days_reduce<float>({X_dev, nullptr, T, n, ldx, row_begin_dev, rows_dev, P, n_rows, doy_dev, win_dev, flags, out_dev,
+                                         ldo, out_pstride, status_dev, work_dev, work_bytes, stream}, offset, edges, n_edges);
 }
 extern "C" int wagg_bin_days_reduce_f64(const double *X_dev, int64_t T, int64_t n, int64_t ldx, const int32_t *row_begin_dev,
                                         const int32_t *rows_dev, int32_t P, int64_t n_rows, const int32_t *doy_dev, const int32_t *win_dev,
                                         double offset, const double *edges, int n_edges, int flags, double *out_dev, int64_t ldo,
                                         int64_t out_pstride, int32_t *status_dev, void *work_dev, int64_t work_bytes, void *stream) {
-    return wagg::bin_days_reduce<double>(X_dev, T, n, ldx, row_begin_dev, rows_dev, P, n_rows, doy_dev, win_dev, offset, edges, n_edges,
-                                         flags, out_dev, ldo, out_pstride, status_dev, work_dev, work_bytes, stream);
+    return wagg::bin_days_reduce<double>({X_dev, nullptr, T, n, ldx, row_begin_dev, rows_dev, P, n_rows, doy_dev, win_dev, flags, out_dev,
+                                          ldo, out_pstride, status_dev, work_dev, work_bytes, stream}, offset, edges, n_edges);
 }

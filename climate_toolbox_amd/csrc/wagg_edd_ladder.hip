@@ -151,57 +151,26 @@ edd_ladder_kernel(const T *__restrict__ X, const T *__restrict__ X2, RowlistShap
     if (__ballot(saw_inf) != 0ull && (threadIdx.x & 63) == 0) atomicOr(status, 1);
 }
 
-template <typename T, int VEC>
-static void launch_ladder(const T *X, const T *X2, const RowlistShape &sh, const int32_t *row_begin, const int32_t *rows, const int32_t *doy,
-                          const int32_t *win, const LadderXf<T> &xf, T *out, int64_t ldo, int64_t pstride, double *work, int32_t *status,
-                          hipStream_t st) {
-    const dim3 grid((unsigned)((int64_t)sh.n_colblk * sh.P * sh.split * sh.aux)), block(RL_BLOCK);
-    const bool season = doy != nullptr;
-#define WAGG_EL_LAUNCH(SEASON)                                                                                                       \
-    do {                                                                                                                             \
-        if (sh.split > 1)                                                                                                            \
-            hipLaunchKernelGGL((edd_ladder_kernel<T, VEC, SEASON, double>), grid, block, 0, st, X, X2, sh, row_begin, rows, doy, win, xf, \
-                               work, sh.n, (int64_t)sh.P * sh.n, status);                                                            \
-        else                                                                                                                         \
-            hipLaunchKernelGGL((edd_ladder_kernel<T, VEC, SEASON, T>), grid, block, 0, st, X, X2, sh, row_begin, rows, doy, win, xf, out, \
-                               ldo, pstride, status);                                                                                \
-    } while (0)
-    if (season) WAGG_EL_LAUNCH(true);
-    else WAGG_EL_LAUNCH(false);
-#undef WAGG_EL_LAUNCH
-}
-
 template <typename T>
-static int ladder_reduce(const T *X, const T *X2, int64_t Ttot, int64_t n, int64_t ldx, const int32_t *row_begin, const int32_t *rows,
-                         int32_t P, int64_t n_rows, const int32_t *doy, const int32_t *win, double offset, const double *thresholds,
-                         int n_thr, int flags, T *out, int64_t ldo, int64_t pstride, int32_t *status, void *work, int64_t work_bytes,
-                         void *stream) {
-    clear_error();
-    WAGG_TRY(rowlist_require_sizes(Ttot, n, P, n_rows));
-    WAGG_REQUIRE((flags & ~WAGG_PERIOD_ROWS_CHECKED) == 0, "unknown flags 0x%x (a degree-day ladder has no keep-NaN form)", flags);
-    WAGG_REQUIRE(n_thr >= 1 && n_thr <= WAGG_EDD_LADDER_MAX, "n_thr must be 1..%d, got %d", WAGG_EDD_LADDER_MAX, n_thr);
-    WAGG_REQUIRE(thresholds != nullptr, "thresholds is NULL");
-    WAGG_REQUIRE((doy == nullptr) == (win == nullptr), "doy_dev and win_dev go together: both given, or both NULL (no season)");
-    WAGG_TRY(rowlist_require_layout(n, ldx, ldo, P, n_thr, pstride, work, work_bytes, status, row_begin, rows, n_rows));
-    if (P == 0 || n == 0) return WAGG_OK;
-    WAGG_REQUIRE(out != nullptr, "NULL pointer (out_dev)");
-    WAGG_REQUIRE(n_rows == 0 || Ttot == 0 || (X != nullptr && X2 != nullptr), "NULL pointer (tasmin_dev / tasmax_dev)");
-    hipStream_t st = (hipStream_t)stream;
-    WAGG_TRY(rowlist_check_rows(row_begin, P, rows, n_rows, Ttot, flags, st));
-    RowlistShape sh;
-    sh.T = Ttot; sh.n = n; sh.ldx = ldx; sh.n_rows = n_rows; sh.P = P;
-    sh.aux = (n_thr + EL_G - 1) / EL_G;                          // threshold groups
-    bool wide;
-    WAGG_REQUIRE(rowlist_geometry(sh, wide, (int)sizeof(T), X, X2, n_thr, work, work_bytes, sh.aux),
-                 "too many pieces x periods x groups for one launch");
-    LadderXf<T> xf;
-    xf.off = (T)offset; xf.n_thr = n_thr;
-    for (int k = 0; k < WAGG_EDD_LADDER_MAX; ++k) xf.thr[k] = (T)(k < n_thr ? thresholds[k] : 0.0);
-    double *w = static_cast<double *>(work);
-    if (wide) launch_ladder<T, 16 / (int)sizeof(T)>(X, X2, sh, row_begin, rows, doy, win, xf, out, ldo, pstride, w, status, st);
-    else launch_ladder<T, 1>(X, X2, sh, row_begin, rows, doy, win, xf, out, ldo, pstride, w, status, st);
-    WAGG_HIP(hipGetLastError());
-    return rowlist_finish<T>(w, sh.split, n_thr, P, n, out, ldo, pstride, st);
+static int ladder_reduce(const GroupedArgs<T> &a, double offset, const double *thresholds, int n_thr) {
+    static const GroupedFamily fam = {"a degree-day ladder", "tasmin_dev / tasmax_dev", 2, EL_G};
+    return grouped_reduce<T>(
+        fam, a, n_thr,
+        [&]() -> int {
+            WAGG_REQUIRE(n_thr >= 1 && n_thr <= WAGG_EDD_LADDER_MAX, "n_thr must be 1..%d, got %d", WAGG_EDD_LADDER_MAX, n_thr);
+            WAGG_REQUIRE(thresholds != nullptr, "thresholds is NULL");
+            return WAGG_OK;
+        },
+        [&](const RowlistShape &sh, bool wide, hipStream_t st) {
+            LadderXf<T> xf;
+            xf.off = (T)offset; xf.n_thr = n_thr;
+            for (int k = 0; k < WAGG_EDD_LADDER_MAX; ++k) xf.thr[k] = (T)(k < n_thr ? thresholds[k] : 0.0);
+            grouped_launch<T>(sh, wide, a, [&](auto vec, auto season, dim3 grid, auto *out, int64_t ldo, int64_t pstride) {
+                using DST = std::remove_pointer_t<decltype(out)>;
+                hipLaunchKernelGGL((edd_ladder_kernel<T, decltype(vec)::value, decltype(season)::value, DST>), grid, dim3(RL_BLOCK), 0, st,
+                                   a.X, a.X2, sh, a.row_begin, a.rows, a.doy, a.win, xf, out, ldo, pstride, a.status);
+            });
+        });
 }
 
 }  // namespace wagg
@@ -215,14 +184,14 @@ extern "C" int wagg_edd_ladder_reduce_f32(const float *tasmin_dev, const float *
                                           const int32_t *doy_dev, const int32_t *win_dev, double offset, const double *thresholds,
                                           int n_thr, int flags, float *out_dev, int64_t ldo, int64_t out_pstride, int32_t *status_dev,
                                           void *work_dev, int64_t work_bytes, void *stream) {
-    return wagg::ladder_reduce<float>(tasmin_dev, tasmax_dev, T, n, ldx, row_begin_dev, rows_dev, P, n_rows, doy_dev, win_dev, offset,
-                                      thresholds, n_thr, flags, out_dev, ldo, out_pstride, status_dev, work_dev, work_bytes, stream);
+    return wagg::ladder_reduce<float>({tasmin_dev, tasmax_dev, T, n, ldx, row_begin_dev, rows_dev, P, n_rows, doy_dev, win_dev, flags,
+                                       out_dev, ldo, out_pstride, status_dev, work_dev, work_bytes, stream}, offset, thresholds, n_thr);
 }
 extern "C" int wagg_edd_ladder_reduce_f64(const double *tasmin_dev, const double *tasmax_dev, int64_t T, int64_t n, int64_t ldx,
                                           const int32_t *row_begin_dev, const int32_t *rows_dev, int32_t P, int64_t n_rows,
                                           const int32_t *doy_dev, const int32_t *win_dev, double offset, const double *thresholds,
                                           int n_thr, int flags, double *out_dev, int64_t ldo, int64_t out_pstride, int32_t *status_dev,
                                           void *work_dev, int64_t work_bytes, void *stream) {
-    return wagg::ladder_reduce<double>(tasmin_dev, tasmax_dev, T, n, ldx, row_begin_dev, rows_dev, P, n_rows, doy_dev, win_dev, offset,
-                                       thresholds, n_thr, flags, out_dev, ldo, out_pstride, status_dev, work_dev, work_bytes, stream);
+    return wagg::ladder_reduce<double>({tasmin_dev, tasmax_dev, T, n, ldx, row_begin_dev, rows_dev, P, n_rows, doy_dev, win_dev, flags,
+                                        out_dev, ldo, out_pstride, status_dev, work_dev, work_bytes, stream}, offset, thresholds, n_thr);
 }

@@ -154,77 +154,49 @@ hinge_kernel(const T *__restrict__ X, RowlistShape sh, const int32_t *__restrict
     if (__ballot(saw_inf) != 0ull && (threadIdx.x & 63) == 0) atomicOr(status, 1);
 }
 
-template <typename T, int VEC>
-static void launch_hinge(const T *X, const RowlistShape &sh, const int32_t *row_begin, const int32_t *rows, const int32_t *doy,
-                         const int32_t *win, const HingeXf<T> &xf, bool tail, T *out, int64_t ldo, int64_t pstride, double *work,
-                         int32_t *status, hipStream_t st) {
-    const dim3 grid((unsigned)((int64_t)sh.n_colblk * sh.P * sh.split * sh.aux)), block(RL_BLOCK);
-    const bool season = doy != nullptr;
-#define WAGG_HG_LAUNCH(SEASON, TAIL)                                                                                                 \
-    do {                                                                                                                             \
-        if (sh.split > 1)                                                                                                            \
-            hipLaunchKernelGGL((hinge_kernel<T, VEC, SEASON, TAIL, double>), grid, block, 0, st, X, sh, row_begin, rows, doy, win, xf,     \
-                               work, sh.n, (int64_t)sh.P * sh.n, status);                                                            \
-        else                                                                                                                         \
-            hipLaunchKernelGGL((hinge_kernel<T, VEC, SEASON, TAIL, T>), grid, block, 0, st, X, sh, row_begin, rows, doy, win, xf, out,     \
-                               ldo, pstride, status);                                                                                \
-    } while (0)
-    if (season && tail) WAGG_HG_LAUNCH(true, true);
-    else if (season) WAGG_HG_LAUNCH(true, false);
-    else if (tail) WAGG_HG_LAUNCH(false, true);
-    else WAGG_HG_LAUNCH(false, false);
-#undef WAGG_HG_LAUNCH
-}
-
 template <typename T>
-static int hinge_reduce(const T *X, int64_t Ttot, int64_t n, int64_t ldx, const int32_t *row_begin, const int32_t *rows, int32_t P,
-                        int64_t n_rows, const int32_t *doy, const int32_t *win, double offset, const double *knots, int n_knots,
-                        int power, int side, const double *tail_knots, const double *tail_a, const double *tail_b, int flags, T *out,
-                        int64_t ldo, int64_t pstride, int32_t *status, void *work, int64_t work_bytes, void *stream) {
-    clear_error();
-    WAGG_TRY(rowlist_require_sizes(Ttot, n, P, n_rows));
-    WAGG_REQUIRE((flags & ~WAGG_PERIOD_ROWS_CHECKED) == 0, "unknown flags 0x%x (a hinge total has no keep-NaN form)", flags);
-    WAGG_REQUIRE(n_knots >= 1 && n_knots <= WAGG_HINGE_MAX, "n_knots must be 1..%d, got %d", WAGG_HINGE_MAX, n_knots);
-    WAGG_REQUIRE(knots != nullptr, "knots is NULL");
-    WAGG_REQUIRE(power >= 1 && power <= 3, "power must be 1..3, got %d", power);
-    WAGG_REQUIRE(side == WAGG_HINGE_ABOVE || side == WAGG_HINGE_BELOW, "side must be WAGG_HINGE_ABOVE or WAGG_HINGE_BELOW, got %d", side);
-    WAGG_REQUIRE(std::isfinite(offset), "offset must be finite");
-    for (int k = 0; k < n_knots; ++k) WAGG_REQUIRE(std::isfinite(knots[k]), "knot %d is not finite", k);
+static int hinge_reduce(const GroupedArgs<T> &a, double offset, const double *knots, int n_knots, int power, int side,
+                        const double *tail_knots, const double *tail_a, const double *tail_b) {
+    static const GroupedFamily fam = {"a hinge total", "X_dev", 1, HG_G};
     const bool tail = tail_knots != nullptr;
-    WAGG_REQUIRE(tail == (tail_a != nullptr) && tail == (tail_b != nullptr),
-                 "tail_knots, tail_a and tail_b go together: all given, or all NULL (no tail)");
-    if (tail) {
-        WAGG_REQUIRE(std::isfinite(tail_knots[0]) && std::isfinite(tail_knots[1]), "a tail knot is not finite");
-        for (int k = 0; k < n_knots; ++k)
-            WAGG_REQUIRE(std::isfinite(tail_a[k]) && std::isfinite(tail_b[k]), "tail coefficient %d is not finite", k);
-    }
-    WAGG_REQUIRE((doy == nullptr) == (win == nullptr), "doy_dev and win_dev go together: both given, or both NULL (no season)");
-    WAGG_TRY(rowlist_require_layout(n, ldx, ldo, P, n_knots, pstride, work, work_bytes, status, row_begin, rows, n_rows));
-    if (P == 0 || n == 0) return WAGG_OK;
-    WAGG_REQUIRE(out != nullptr, "NULL pointer (out_dev)");
-    WAGG_REQUIRE(n_rows == 0 || Ttot == 0 || X != nullptr, "NULL pointer (X_dev)");
-    hipStream_t st = (hipStream_t)stream;
-    WAGG_TRY(rowlist_check_rows(row_begin, P, rows, n_rows, Ttot, flags, st));
-    RowlistShape sh;
-    sh.T = Ttot; sh.n = n; sh.ldx = ldx; sh.n_rows = n_rows; sh.P = P;
-    sh.aux = (n_knots + HG_G - 1) / HG_G;                        // knot groups
-    bool wide;
-    WAGG_REQUIRE(rowlist_geometry(sh, wide, (int)sizeof(T), X, nullptr, n_knots, work, work_bytes, sh.aux),
-                 "too many pieces x periods x groups for one launch");
-    HingeXf<T> xf;
-    xf.off = (T)offset; xf.n_knots = n_knots; xf.power = power; xf.below = side == WAGG_HINGE_BELOW;
-    for (int k = 0; k < WAGG_HINGE_MAX; ++k) {
-        xf.k[k] = (T)(k < n_knots ? knots[k] : 0.0);
-        xf.ca[k] = tail && k < n_knots ? tail_a[k] : 0.0;
-        xf.cb[k] = tail && k < n_knots ? tail_b[k] : 0.0;
-    }
-    xf.tail[0] = (T)(tail ? tail_knots[0] : 0.0);
-    xf.tail[1] = (T)(tail ? tail_knots[1] : 0.0);
-    double *w = static_cast<double *>(work);
-    if (wide) launch_hinge<T, 16 / (int)sizeof(T)>(X, sh, row_begin, rows, doy, win, xf, tail, out, ldo, pstride, w, status, st);
-    else launch_hinge<T, 1>(X, sh, row_begin, rows, doy, win, xf, tail, out, ldo, pstride, w, status, st);
-    WAGG_HIP(hipGetLastError());
-    return rowlist_finish<T>(w, sh.split, n_knots, P, n, out, ldo, pstride, st);
+    return grouped_reduce<T>(
+        fam, a, n_knots,
+        [&]() -> int {
+            WAGG_REQUIRE(n_knots >= 1 && n_knots <= WAGG_HINGE_MAX, "n_knots must be 1..%d, got %d", WAGG_HINGE_MAX, n_knots);
+            WAGG_REQUIRE(knots != nullptr, "knots is NULL");
+            WAGG_REQUIRE(power >= 1 && power <= 3, "power must be 1..3, got %d", power);
+            WAGG_REQUIRE(side == WAGG_HINGE_ABOVE || side == WAGG_HINGE_BELOW, "side must be WAGG_HINGE_ABOVE or WAGG_HINGE_BELOW, got %d",
+                         side);
+            WAGG_REQUIRE(std::isfinite(offset), "offset must be finite");
+            for (int k = 0; k < n_knots; ++k) WAGG_REQUIRE(std::isfinite(knots[k]), "knot %d is not finite", k);
+            WAGG_REQUIRE(tail == (tail_a != nullptr) && tail == (tail_b != nullptr),
+                         "tail_knots, tail_a and tail_b go together: all given, or all NULL (no tail)");
+            if (tail) {
+                WAGG_REQUIRE(std::isfinite(tail_knots[0]) && std::isfinite(tail_knots[1]), "a tail knot is not finite");
+                for (int k = 0; k < n_knots; ++k)
+                    WAGG_REQUIRE(std::isfinite(tail_a[k]) && std::isfinite(tail_b[k]), "tail coefficient %d is not finite", k);
+            }
+            return WAGG_OK;
+        },
+        [&](const RowlistShape &sh, bool wide, hipStream_t st) {
+            HingeXf<T> xf;
+            xf.off = (T)offset; xf.n_knots = n_knots; xf.power = power; xf.below = side == WAGG_HINGE_BELOW;
+            for (int k = 0; k < WAGG_HINGE_MAX; ++k) {
+                xf.k[k] = (T)(k < n_knots ? knots[k] : 0.0);
+                xf.ca[k] = tail && k < n_knots ? tail_a[k] : 0.0;
+                xf.cb[k] = tail && k < n_knots ? tail_b[k] : 0.0;
+            }
+            xf.tail[0] = (T)(tail ? tail_knots[0] : 0.0);
+            xf.tail[1] = (T)(tail ? tail_knots[1] : 0.0);
+            grouped_launch<T>(sh, wide, a, [&](auto vec, auto season, dim3 grid, auto *out, int64_t ldo, int64_t pstride) {
+                constexpr int VEC = decltype(vec)::value;
+                constexpr bool SEASON = decltype(season)::value;
+                using DST = std::remove_pointer_t<decltype(out)>;
+                auto *kernel = tail ? hinge_kernel<T, VEC, SEASON, true, DST> : hinge_kernel<T, VEC, SEASON, false, DST>;
+                hipLaunchKernelGGL(kernel, grid, dim3(RL_BLOCK), 0, st, a.X, sh, a.row_begin, a.rows, a.doy, a.win, xf, out, ldo, pstride,
+                                   a.status);
+            });
+        });
 }
 
 }  // namespace wagg
@@ -238,16 +210,16 @@ extern "C" int wagg_hinge_reduce_f32(const float *X_dev, int64_t T, int64_t n, i
                                      double offset, const double *knots, int n_knots, int power, int side, const double *tail_knots,
                                      const double *tail_a, const double *tail_b, int flags, float *out_dev, int64_t ldo,
                                      int64_t out_pstride, int32_t *status_dev, void *work_dev, int64_t work_bytes, void *stream) {
-    return wagg::hinge_reduce<float>(X_dev, T, n, ldx, row_begin_dev, rows_dev, P, n_rows, doy_dev, win_dev, offset, knots, n_knots, power,
-                                     side, tail_knots, tail_a, tail_b, flags, out_dev, ldo, out_pstride, status_dev, work_dev, work_bytes,
-                                     stream);
+    return wagg::hinge_reduce<float>({X_dev, nullptr, T, n, ldx, row_begin_dev, rows_dev, P, n_rows, doy_dev, win_dev, flags, out_dev, ldo,
+                                      out_pstride, status_dev, work_dev, work_bytes, stream},
+                                     offset, knots, n_knots, power, side, tail_knots, tail_a, tail_b);
 }
 extern "C" int wagg_hinge_reduce_f64(const double *X_dev, int64_t T, int64_t n, int64_t ldx, const int32_t *row_begin_dev,
                                      const int32_t *rows_dev, int32_t P, int64_t n_rows, const int32_t *doy_dev, const int32_t *win_dev,
                                      double offset, const double *knots, int n_knots, int power, int side, const double *tail_knots,
                                      const double *tail_a, const double *tail_b, int flags, double *out_dev, int64_t ldo,
                                      int64_t out_pstride, int32_t *status_dev, void *work_dev, int64_t work_bytes, void *stream) {
-    return wagg::hinge_reduce<double>(X_dev, T, n, ldx, row_begin_dev, rows_dev, P, n_rows, doy_dev, win_dev, offset, knots, n_knots, power,
-                                      side, tail_knots, tail_a, tail_b, flags, out_dev, ldo, out_pstride, status_dev, work_dev, work_bytes,
-                                      stream);
+    return wagg::hinge_reduce<double>({X_dev, nullptr, T, n, ldx, row_begin_dev, rows_dev, P, n_rows, doy_dev, win_dev, flags, out_dev, ldo,
+                                       out_pstride, status_dev, work_dev, work_bytes, stream},
+                                      offset, knots, n_knots, power, side, tail_knots, tail_a, tail_b);
 }

@@ -1,12 +1,18 @@
-// What the row-list reductions hold in common (wagg_period.hip, wagg_season.hip, wagg_edd_ladder.hip): a lane owns one 16-byte
-// piece of a row (VEC = 1 for rows that are not 16-byte aligned) and walks its period's row list; the grid is column block x
-// period x part [x threshold group], flat; when that cannot fill the device a period's list is cut into `split` consecutive
-// parts, every part writes fp64 partial sums to the caller's workspace [s][plane][p][j] and rowlist_finish adds them in part
-// order -- no atomics on a sum.  The three families promise each other bit equality (an all-year season = the period sum,
-// every ladder plane = the four-plane kernels' plane): that rests on the split rule, the part arithmetic and the finish order
-// being the ones below for all of them.  The host pieces are defined once, in wagg_period.hip.
+// What the row-list reductions hold in common (wagg_period.hip, wagg_season.hip, wagg_edd_ladder.hip, wagg_bins.hip,
+// wagg_hinge.hip): a lane owns one 16-byte piece of a row (VEC = 1 for rows that are not 16-byte aligned) and walks its
+// period's row list; the grid is column block x period x part [x group of thresholds / bins / knots], flat; when that cannot
+// fill the device a period's list is cut into `split` consecutive parts, every part writes fp64 partial sums to the caller's
+// workspace [s][plane][p][j] and rowlist_finish adds them in part order -- no atomics on a sum.  The five families promise each
+// other bit equality (an all-year season = the period sum, every ladder plane = the four-plane kernels' plane, a one-knot hinge
+// call = the plane of the many-knot call, counts that do not depend on the split): that rests on the split rule, the part
+// arithmetic and the finish order being the ones below for all of them.  The host pieces are defined once, in wagg_period.hip;
+// the three grouped families (ladder, bins, hinge) also share their whole host sequence, grouped_reduce below.  The frame of
+// their three kernel bodies (window read, rows in flight, masks, loads, status word) deliberately stays three copies: behind
+// shared inline functions hipcc allocates other registers (docs/HISTORY.md, "one shared core").
 #pragma once
 #include "wagg_common.h"
+
+#include <type_traits>
 
 namespace wagg {
 
@@ -21,7 +27,7 @@ constexpr int32_t RL_WIN_NULL = 1 << 21, RL_WIN_INVERT = 1 << 20;  // include/wa
 struct RowlistShape {
     int64_t T, n, ldx, n_rows;
     int32_t P, n_colblk, split;
-    int32_t aux;                            // period: keep_nan; season: 0; ladder: the number of threshold groups
+    int32_t aux;                            // period: keep_nan; season: 0; grouped families: the number of groups
 };
 
 template <typename T> struct RowlistXf {    // the four-plane kernels' transform
@@ -59,7 +65,7 @@ __device__ __forceinline__ void load_piece(const T *__restrict__ row, int64_t co
 // functions: hipcc allocates the reduce kernels' registers by the order of these statements among the kernel's own (the
 // same statements behind an inlined call, or the second group ahead of `col`, renames registers and moves tens of
 // instructions in most instances), and the kernels are to stay the code whose registers and timings are on record.
-//   WAGG_ROWLIST_BLOCK: column block cb, period p, and sg = the part s of p's list (ladder: s + split * threshold group)
+//   WAGG_ROWLIST_BLOCK: column block cb, period p, and sg = the part s of p's list (grouped families: s + split * group)
 //   WAGG_ROWLIST_ROWS:  [b, e) = part s of period p's list; a malformed row_begin is confined to the list's extent
 #define WAGG_ROWLIST_BLOCK(sh, cb, p, sg)                                                     \
     const int64_t blk_ = blockIdx.x;                                                          \
@@ -124,5 +130,78 @@ bool rowlist_geometry(RowlistShape &sh, bool &wide, int elem_bytes, const void *
 // out[k][p][j] = (T) sum_s work[s][k][p][j], s ascending; nothing to do for split <= 1
 template <typename T>
 int rowlist_finish(const double *work, int split, int planes, int64_t P, int64_t n, T *out, int64_t ldo, int64_t pstride, hipStream_t st);
+
+// ---- the grouped families (wagg_edd_ladder.hip, wagg_bins.hip, wagg_hinge.hip) ---------------------------------------------
+// what their entry points take alike (X2: the ladder's tasmax; NULL in the one-field families)
+template <typename T> struct GroupedArgs {
+    const T *X, *X2;
+    int64_t Ttot, n, ldx;
+    const int32_t *row_begin, *rows;
+    int32_t P;
+    int64_t n_rows;
+    const int32_t *doy, *win;
+    int flags;
+    T *out;
+    int64_t ldo, pstride;
+    int32_t *status;
+    void *work;
+    int64_t work_bytes;
+    void *stream;
+};
+
+// what tells them apart outside their callbacks: the noun of the flags message, the field pointers a call that reads rows needs
+// and their names in the message, the planes one block of the group dimension serves
+struct GroupedFamily {
+    const char *noun, *fields;
+    int n_fields, group;
+};
+
+// The host sequence of a grouped entry point, in the one order all three have always had.  check(): the family's checks of its
+// own parameter list (WAGG_OK, or the error set and its code); planes: the planes of `out`, read only behind check();
+// launch(sh, wide, st): builds the family's transform and launches through grouped_launch.
+template <typename T, typename Check, typename Launch>
+int grouped_reduce(const GroupedFamily &fam, const GroupedArgs<T> &a, int planes, Check &&check, Launch &&launch) {
+    clear_error();
+    WAGG_TRY(rowlist_require_sizes(a.Ttot, a.n, a.P, a.n_rows));
+    WAGG_REQUIRE((a.flags & ~WAGG_PERIOD_ROWS_CHECKED) == 0, "unknown flags 0x%x (%s has no keep-NaN form)", a.flags, fam.noun);
+    WAGG_TRY(check());
+    WAGG_REQUIRE((a.doy == nullptr) == (a.win == nullptr), "doy_dev and win_dev go together: both given, or both NULL (no season)");
+    WAGG_TRY(rowlist_require_layout(a.n, a.ldx, a.ldo, a.P, planes, a.pstride, a.work, a.work_bytes, a.status, a.row_begin, a.rows,
+                                    a.n_rows));
+    if (a.P == 0 || a.n == 0) return WAGG_OK;
+    WAGG_REQUIRE(a.out != nullptr, "NULL pointer (out_dev)");
+    WAGG_REQUIRE(a.n_rows == 0 || a.Ttot == 0 || (a.X != nullptr && (fam.n_fields < 2 || a.X2 != nullptr)), "NULL pointer (%s)",
+                 fam.fields);
+    hipStream_t st = (hipStream_t)a.stream;
+    WAGG_TRY(rowlist_check_rows(a.row_begin, a.P, a.rows, a.n_rows, a.Ttot, a.flags, st));
+    RowlistShape sh;
+    sh.T = a.Ttot; sh.n = a.n; sh.ldx = a.ldx; sh.n_rows = a.n_rows; sh.P = a.P;
+    sh.aux = (planes + fam.group - 1) / fam.group;
+    bool wide;
+    WAGG_REQUIRE(rowlist_geometry(sh, wide, (int)sizeof(T), a.X, a.X2, planes, a.work, a.work_bytes, sh.aux),
+                 "too many pieces x periods x groups for one launch");
+    launch(sh, wide, st);
+    WAGG_HIP(hipGetLastError());
+    return rowlist_finish<T>(static_cast<double *>(a.work), sh.split, planes, a.P, a.n, a.out, a.ldo, a.pstride, st);
+}
+
+// The kernel instance of one grouped launch and its grid (column block x period x part x group): VEC = a 16-byte piece of the
+// row (wide) or 1, SEASON = doy given, DST = double with the workspace's strides (n, P * n) when the lists are split, else T
+// with the caller's.  go(vec, season, grid, dst, ldo, pstride) launches <T, vec.value, season.value, ..., *dst's type>; what
+// else picks an instance (the hinge's TAIL) is go's own business.
+template <typename T, typename Go>
+void grouped_launch(const RowlistShape &sh, bool wide, const GroupedArgs<T> &a, Go &&go) {
+    const dim3 grid((unsigned)((int64_t)sh.n_colblk * sh.P * sh.split * sh.aux));
+    auto with_dst = [&](auto vec, auto season) {
+        if (sh.split > 1) go(vec, season, grid, static_cast<double *>(a.work), sh.n, (int64_t)sh.P * sh.n);
+        else go(vec, season, grid, a.out, a.ldo, a.pstride);
+    };
+    auto with_season = [&](auto vec) {
+        if (a.doy != nullptr) with_dst(vec, std::true_type{});
+        else with_dst(vec, std::false_type{});
+    };
+    if (wide) with_season(std::integral_constant<int, 16 / (int)sizeof(T)>{});
+    else with_season(std::integral_constant<int, 1>{});
+}
 
 }  // namespace wagg

@@ -858,7 +858,8 @@ def _season_vector(a, length, what, device):
 
 
 class _RowlistCall:
-    """What :func:`period_reduce`, :func:`season_reduce`, :func:`edd_ladder_reduce`, :func:`bin_days_reduce` and :func:`hinge_reduce` do alike around their library call, in the
+    """What the five row-list calls -- :func:`period_reduce`, :func:`season_reduce` and, through :func:`_grouped_reduce`,
+    :func:`edd_ladder_reduce`, :func:`bin_days_reduce` and :func:`hinge_reduce` -- do alike around their library call, in the
     order they do it: the row lists (and, with ``season = (doy, windows)``, those two vectors) as int32 CUDA tensors and ``P``;
     then ``out``, ``status`` and the workspace; at the end what must outlive the kernels on the caller's stream."""
 
@@ -977,6 +978,30 @@ def season_reduce(X, row_begin, rows, doy, windows, X2=None, poly=None, edd=None
     return out, status
 
 
+def _grouped_reduce(name, fields, row_begin, rows, doy, windows, checked, offset, middle, planes, work_bytes, out, status, workspace,
+                    stream):
+    """What :func:`edd_ladder_reduce`, :func:`bin_days_reduce` and :func:`hinge_reduce` do alike behind their own validation: the
+    doy / windows pairing, the :class:`_RowlistCall`, ``out`` / ``status`` / workspace, and the library call ``name`` + ``_f32``
+    or ``_f64`` by the dtype of ``fields`` (one checked (T, n) tensor, or tasmin and tasmax) -- the fields and the arguments
+    every grouped entry point begins with (sizes, lists, season, ``offset``), the family's ``middle`` ones, and the ones every
+    one ends with (flags, ``out`` and its strides, status, workspace, stream).  ``work_bytes(L, n, P, n_rows, planes)``: the
+    family's ``*_work_bytes``.  Returns ``(out, status)``."""
+    import torch
+    if (doy is None) != (windows is None):
+        raise ValueError("doy and windows go together: both given, or both None (no season)")
+    X = fields[0]
+    c = _RowlistCall(X, row_begin, rows, checked, None if doy is None else (doy, windows))
+    L = _lib.load()
+    out, status, work, wb = c.alloc(lambda *a: work_bytes(L, *a), planes, out, status, workspace)
+    fn = getattr(L, name + ("_f32" if X.dtype == torch.float32 else "_f64"))
+    _lib.check(fn(*[C.c_void_p(f.data_ptr()) for f in fields], c.T, c.n, _ld(X), C.c_void_p(c.row_begin.data_ptr()),
+                  C.c_void_p(c.rows.data_ptr()), c.P, c.n_rows, None if doy is None else C.c_void_p(c.doy.data_ptr()),
+                  None if doy is None else C.c_void_p(c.windows.data_ptr()), float(offset), *middle, c.flags, C.c_void_p(out.data_ptr()),
+                  max(1, c.n), max(1, c.P * c.n), C.c_void_p(status.data_ptr()), work, wb, _stream_handle(stream)), name)
+    c.done(stream)
+    return out, status
+
+
 def edd_ladder_reduce(tasmin, tasmax, row_begin, rows, offset, thresholds, doy=None, windows=None, checked=False, out=None, status=None,
                       stream=None, workspace=True):
     """Snyder degree days at every threshold of a ladder, summed per period, in ONE launch (``wagg_edd_ladder_reduce_*``):
@@ -987,7 +1012,6 @@ def edd_ladder_reduce(tasmin, tasmax, row_begin, rows, offset, thresholds, doy=N
     :func:`season_reduce`; ``doy`` and ``windows`` both None: no season, every listed row counts (:func:`period_reduce`).  Plane
     ``k`` is bit for bit the plane those two give for ``thresholds[k]``.  Returns ``(out, status)``: the (n_thr, P, n) tensor and
     the status word (bit 0: an in-season value was +-inf)."""
-    import torch
     X = _check_X(tasmin, "TG")
     X2 = _check_X(tasmax, "TG")
     if X2.shape != X.shape or X2.dtype != X.dtype or _ld(X2) != _ld(X) or X2.device != X.device:
@@ -995,19 +1019,9 @@ def edd_ladder_reduce(tasmin, tasmax, row_begin, rows, offset, thresholds, doy=N
     thr = np.ascontiguousarray(np.atleast_1d(thresholds), dtype=np.float64)
     if thr.ndim != 1 or not 1 <= len(thr) <= _lib.EDD_LADDER_MAX:
         raise ValueError("1..%d thresholds per call, got %s" % (_lib.EDD_LADDER_MAX, thr.shape))
-    if (doy is None) != (windows is None):
-        raise ValueError("doy and windows go together: both given, or both None (no season)")
-    c = _RowlistCall(X, row_begin, rows, checked, None if doy is None else (doy, windows))
-    L = _lib.load()
-    out, status, work, wb = c.alloc(L.wagg_edd_ladder_work_bytes, len(thr), out, status, workspace)
-    fn = L.wagg_edd_ladder_reduce_f32 if X.dtype == torch.float32 else L.wagg_edd_ladder_reduce_f64
-    _lib.check(fn(C.c_void_p(X.data_ptr()), C.c_void_p(X2.data_ptr()), c.T, c.n, _ld(X), C.c_void_p(c.row_begin.data_ptr()),
-                  C.c_void_p(c.rows.data_ptr()), c.P, c.n_rows, None if doy is None else C.c_void_p(c.doy.data_ptr()),
-                  None if doy is None else C.c_void_p(c.windows.data_ptr()), float(offset), _np_ptr(thr, C.c_double), len(thr), c.flags,
-                  C.c_void_p(out.data_ptr()), max(1, c.n), max(1, c.P * c.n), C.c_void_p(status.data_ptr()), work, wb,
-                  _stream_handle(stream)), "wagg_edd_ladder_reduce")
-    c.done(stream)
-    return out, status
+    return _grouped_reduce("wagg_edd_ladder_reduce", (X, X2), row_begin, rows, doy, windows, checked, offset,
+                           (_np_ptr(thr, C.c_double), len(thr)), len(thr),
+                           lambda L, *a: L.wagg_edd_ladder_work_bytes(*a), out, status, workspace, stream)
 
 
 def bin_thresholds(edges, offset, dtype):
@@ -1038,26 +1052,16 @@ def bin_days_reduce(X, row_begin, rows, offset, edges, doy=None, windows=None, c
     the library gets the scratch its ``*_work_bytes`` reports; False: none) never changes a count.  Returns ``(counts,
     status)``: the (n_bins, P, n) tensor of ``X``'s dtype (exact in fp32 up to 2^24 days) and the status word (bit 0: an
     in-season value was +-inf)."""
-    import torch
     X = _check_X(X, "TG")
     e = np.ascontiguousarray(np.atleast_1d(edges), dtype=np.float64)
     if e.ndim != 1 or not 2 <= len(e) <= _lib.BIN_EDGES_MAX:
         raise ValueError("2..%d bin edges per call, got %s" % (_lib.BIN_EDGES_MAX, e.shape))
     if np.isnan(e).any() or not (e[1:] > e[:-1]).all():
         raise ValueError("bin edges must ascend strictly and hold no NaN, got %r" % (e.tolist(),))
-    if (doy is None) != (windows is None):
-        raise ValueError("doy and windows go together: both given, or both None (no season)")
-    c = _RowlistCall(X, row_begin, rows, checked, None if doy is None else (doy, windows))
-    L = _lib.load()
-    out, status, work, wb = c.alloc(lambda n, P, n_rows, planes: L.wagg_bin_days_work_bytes(n, P, n_rows, planes + 1), len(e) - 1, out,
-                                    status, True if workspace is None else workspace)
-    fn = L.wagg_bin_days_reduce_f32 if X.dtype == torch.float32 else L.wagg_bin_days_reduce_f64
-    _lib.check(fn(C.c_void_p(X.data_ptr()), c.T, c.n, _ld(X), C.c_void_p(c.row_begin.data_ptr()), C.c_void_p(c.rows.data_ptr()), c.P,
-                  c.n_rows, None if doy is None else C.c_void_p(c.doy.data_ptr()), None if doy is None else C.c_void_p(c.windows.data_ptr()),
-                  float(offset), _np_ptr(e, C.c_double), len(e), c.flags, C.c_void_p(out.data_ptr()), max(1, c.n), max(1, c.P * c.n),
-                  C.c_void_p(status.data_ptr()), work, wb, _stream_handle(stream)), "wagg_bin_days_reduce")
-    c.done(stream)
-    return out, status
+    return _grouped_reduce("wagg_bin_days_reduce", (X,), row_begin, rows, doy, windows, checked, offset,
+                           (_np_ptr(e, C.c_double), len(e)), len(e) - 1,
+                           lambda L, n, P, n_rows, planes: L.wagg_bin_days_work_bytes(n, P, n_rows, planes + 1),      # (it takes n_edges)
+                           out, status, True if workspace is None else workspace, stream)
 
 
 def hinge_reduce(X, row_begin, rows, offset, knots, power=1, side="above", tail=None, doy=None, windows=None, checked=False, out=None,
@@ -1072,7 +1076,6 @@ def hinge_reduce(X, row_begin, rows, offset, knots, power=1, side="above", tail=
     The difference is formed in ``X``'s dtype, in the two roundings written above; powers are products in that dtype; sums are
     fp64.  NaN counts 0.  Returns ``(planes, status)``: the (n_knots, P, n) tensor of ``X``'s dtype and the status word (bit 0:
     an in-season value of the field was +-inf)."""
-    import torch
     X = _check_X(X, "TG")
     k = np.ascontiguousarray(np.atleast_1d(knots), dtype=np.float64)
     if k.ndim != 1 or not 1 <= len(k) <= _lib.HINGE_MAX:
@@ -1088,20 +1091,11 @@ def hinge_reduce(X, row_begin, rows, offset, knots, power=1, side="above", tail=
         tk, ta, tb = (np.ascontiguousarray(np.atleast_1d(v), dtype=np.float64) for v in tail)
         if tk.shape != (2,) or ta.shape != k.shape or tb.shape != k.shape or not all(np.isfinite(v).all() for v in (tk, ta, tb)):
             raise ValueError("tail must be (two knots, a coefficient per knot, a coefficient per knot), all finite")
-    if (doy is None) != (windows is None):
-        raise ValueError("doy and windows go together: both given, or both None (no season)")
-    c = _RowlistCall(X, row_begin, rows, checked, None if doy is None else (doy, windows))
-    L = _lib.load()
-    out, status, work, wb = c.alloc(L.wagg_hinge_work_bytes, len(k), out, status, True if workspace is None else workspace)
-    fn = L.wagg_hinge_reduce_f32 if X.dtype == torch.float32 else L.wagg_hinge_reduce_f64
     dptr = lambda v: None if v is None else _np_ptr(v, C.c_double)
-    _lib.check(fn(C.c_void_p(X.data_ptr()), c.T, c.n, _ld(X), C.c_void_p(c.row_begin.data_ptr()), C.c_void_p(c.rows.data_ptr()), c.P,
-                  c.n_rows, None if doy is None else C.c_void_p(c.doy.data_ptr()), None if doy is None else C.c_void_p(c.windows.data_ptr()),
-                  float(offset), _np_ptr(k, C.c_double), len(k), int(power), _lib.HINGE_ABOVE if side == "above" else _lib.HINGE_BELOW,
-                  dptr(tk), dptr(ta), dptr(tb), c.flags, C.c_void_p(out.data_ptr()), max(1, c.n), max(1, c.P * c.n),
-                  C.c_void_p(status.data_ptr()), work, wb, _stream_handle(stream)), "wagg_hinge_reduce")
-    c.done(stream)
-    return out, status
+    return _grouped_reduce("wagg_hinge_reduce", (X,), row_begin, rows, doy, windows, checked, offset,
+                           (dptr(k), len(k), int(power), _lib.HINGE_ABOVE if side == "above" else _lib.HINGE_BELOW, dptr(tk),
+                            dptr(ta), dptr(tb)), len(k), lambda L, *a: L.wagg_hinge_work_bytes(*a), out, status,
+                           True if workspace is None else workspace, stream)
 
 
 def season_mask(doy, windows, stream=None):

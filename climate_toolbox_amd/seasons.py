@@ -267,6 +267,38 @@ def _result_coords(ds, rdims, agglev, uniq):
     return coords
 
 
+def _leased_rows(ds, variable, aggwt, agglev, weights, backup_aggwt, values, dims, second, season, grid, time_values, cells):
+    """The set-up every sum-first route here shares behind its own checks of the variable: the segment table, the season's
+    ``(doy, windows)`` in stored cell order (``season`` None: None, None), and the plan, LEASED, beside the field on the device --
+    whole (time, gridcell) rows, or for ``cells="referenced"`` the packed rows of :func:`_referenced_rows` (``second``: tasmax
+    or None, packed along) with the windows of those cells.  Returns ``(plan, Xd, Hd, pos, doy, win, uniq)``; ``Hd`` None: a
+    second field is still to come over whole.  The caller releases ``plan._lease``."""
+    prepared, w_eff, uniq, codes, cell_idx, G = _segment_table(ds, variable, aggwt, agglev, weights, backup_aggwt)
+    shape = dict(zip(dims, tuple(values.shape)))
+    ia, io, *_ = _spatial_layout(dims)
+    doy, win = (None, None) if season is None else _stored_season(ds, variable, season, grid, dims, shape, time_values)
+    _engine.require_gpu()
+    make_plan = lambda dtype: _plan_for(cell_idx, codes, w_eff, G, len(uniq), shape["lon"] if ia < io else shape["lat"],
+                                        is_f32=str(dtype).endswith("float32"), layout="TG", prepared=prepared)
+    Hd = pos = None
+    if cells == "referenced":
+        plan, Xd, Hd, pos = _referenced_rows(values, second, dims, make_plan)
+        if pos is not None and win is not None:
+            win = win[pos]
+    else:
+        Xd = _time_by_cell(values, dims)
+        plan = make_plan(Xd.dtype)
+    return plan, Xd, Hd, pos, doy, win, uniq
+
+
+def _second_field(Xd, Hd, second, dims):
+    """tasmax beside ``Xd``: the packed ``Hd``, else ``second`` brought over whole; ValueError unless it matches ``Xd``"""
+    Hd = _time_by_cell(second, dims) if Hd is None else Hd
+    if Hd.shape != Xd.shape or Hd.dtype != Xd.dtype:
+        raise ValueError("tasmin and tasmax must have the same shape and dtype")
+    return Hd
+
+
 def _season_totals(ds, variable, aggwt, agglev, weights, backup_aggwt, lists, P, powers, offset, season, grid, time_values,
                    cells="all"):
     """The one route of a ``season=`` call: sum first (``wagg_season_reduce_*``), then contract P rows on whatever plan serves
@@ -284,27 +316,12 @@ def _season_totals(ds, variable, aggwt, agglev, weights, backup_aggwt, lists, P,
         raise ValueError("season= takes powers within 1..16 that span at most four consecutive ones, got %r" % (powers,))
     if edd is not None and len(edd[2]) > 4:
         raise ValueError("season= takes degree-day combinations of at most four thresholds")
-    prepared, w_eff, uniq, codes, cell_idx, G = _segment_table(ds, variable, aggwt, agglev, weights, backup_aggwt)
-    shape = dict(zip(dims, tuple(values.shape)))
-    ia, io, *_ = _spatial_layout(dims)
-    doy, win = _stored_season(ds, variable, season, grid, dims, shape, time_values)
-    _engine.require_gpu()
-    make_plan = lambda dtype: _plan_for(cell_idx, codes, w_eff, G, len(uniq), shape["lon"] if ia < io else shape["lat"],
-                                        is_f32=str(dtype).endswith("float32"), layout="TG", prepared=prepared)
-    Hd = pos = None
-    if cells == "referenced":
-        plan, Xd, Hd, pos = _referenced_rows(values, None if edd is None else edd[0], dims, make_plan)
-        if pos is not None:
-            win = win[pos]
-    else:
-        Xd = _time_by_cell(values, dims)
-        plan = make_plan(Xd.dtype)
+    plan, Xd, Hd, pos, doy, win, uniq = _leased_rows(ds, variable, aggwt, agglev, weights, backup_aggwt, values, dims,
+                                                     None if edd is None else edd[0], season, grid, time_values, cells)
     try:
         rb, rw = lists(Xd.device)
         if edd is not None:
-            Hd = _time_by_cell(edd[0], dims) if Hd is None else Hd
-            if Hd.shape != Xd.shape or Hd.dtype != Xd.dtype:
-                raise ValueError("tasmin and tasmax must have the same shape and dtype")
+            Hd = _second_field(Xd, Hd, edd[0], dims)
             field, status = _engine.season_reduce(Xd, rb, rw, doy, win, X2=Hd, edd=(edd[1], [e for _, e in edd[2]]), checked=True)
         elif powers is not None:
             lo, hi = int(min(powers)), int(max(powers))
@@ -327,50 +344,53 @@ def _season_totals(ds, variable, aggwt, agglev, weights, backup_aggwt, lists, P,
     return (res[0] if single or edd is not None else res), rdims, _result_coords(ds, rdims, agglev, uniq), ds._was_xarray
 
 
-def _ladder_totals(ds, variable, aggwt, agglev, weights, backup_aggwt, lists, P, ladder, season, grid, time_values, cells="all"):
-    """Period totals of the degree days of ``variable`` (a degree-day variable; its own terms are ignored) at EVERY threshold of
-    ``ladder``: summed first (``wagg_edd_ladder_reduce_*``, up to 64 thresholds a launch), then one apply per launch contracts
-    its n_thr * P rows on whatever plan serves the table.  ``season`` None: every day counts.  Returns ``(stack, rdims, coords,
-    was_xarray)`` like :func:`_season_totals`, ``stack`` being the (n_thr, P | R, R | P) results in the ladder's order.
-    ``cells="referenced"``: all of it on the packed rows of :func:`_referenced_rows`."""
-    from . import periods as _periods
-    values, dims = _gridded_field(ds, variable, P, "a degree-day ladder")
+def _degree_day_variable(ds, variable, what):
+    """``(tasmax, offset)`` of a degree-day variable (its own terms are ignored); ValueError for any other"""
     edd = ds._edds.get(variable)
     if edd is None or ds._xforms.get(variable) is not None:
-        raise ValueError("a degree-day ladder needs a degree-day variable, got %r" % (variable,))
-    prepared, w_eff, uniq, codes, cell_idx, G = _segment_table(ds, variable, aggwt, agglev, weights, backup_aggwt)
-    shape = dict(zip(dims, tuple(values.shape)))
-    ia, io, *_ = _spatial_layout(dims)
-    doy, win = (None, None) if season is None else _stored_season(ds, variable, season, grid, dims, shape, time_values)
-    _engine.require_gpu()
-    make_plan = lambda dtype: _plan_for(cell_idx, codes, w_eff, G, len(uniq), shape["lon"] if ia < io else shape["lat"],
-                                        is_f32=str(dtype).endswith("float32"), layout="TG", prepared=prepared)
-    Hd = pos = None
-    if cells == "referenced":
-        plan, Xd, Hd, pos = _referenced_rows(values, edd[0], dims, make_plan)
-        if pos is not None and win is not None:
-            win = win[pos]
-    else:
-        Xd = _time_by_cell(values, dims)
-        plan = make_plan(Xd.dtype)
+        raise ValueError("%s needs a degree-day variable, got %r" % (what, variable))
+    return edd[0], edd[1]
+
+
+def _plain_variable(ds, variable, what):
+    """``(None, offset)`` of a plain temperature variable or one shifted by ``convert_kelvin_to_celsius`` (the offset is the
+    shift); ValueError for a power or a degree-day variable"""
+    xform = ds._xforms.get(variable)
+    if ds._edds.get(variable) is not None or (xform is not None and xform[1] != 1):
+        raise ValueError("%s needs a plain (or Kelvin-shifted) temperature variable, got %r" % (what, variable))
+    return None, 0.0 if xform is None else float(xform[0])
+
+
+def _grouped_totals(ds, variable, aggwt, agglev, weights, backup_aggwt, lists, P, season, grid, time_values, cells, name, of, rule,
+                    launches):
+    """The sum-first route of the grouped statistics (ladder, bins, hinges): every launch sums its planes per period first, then
+    one apply per launch contracts its planes * P rows on whatever plan serves the table.  ``name`` / ``of``: the statistic in
+    the messages ("bin count" / "bins"); ``rule(ds, variable, what)``: ``(second field or None, offset)`` of a variable the
+    statistic takes, ValueError for any other; ``launches``: an iterable, consumed as the launches run, of
+    ``reduce(Xd, Hd, rb, rw, offset, **season)`` -> ``(planes, status)``, each one engine call on its cut of the parameter
+    list.  ``season`` None: every day counts.  ``cells="referenced"``: all of it on the packed rows of :func:`_referenced_rows`.
+    Returns ``(stack, rdims, coords, was_xarray)`` like :func:`_season_totals`, ``stack`` being the (planes, P | R, R | P)
+    results of all launches in order."""
+    from . import periods as _periods
+    values, dims = _gridded_field(ds, variable, P, "a " + name)
+    second, offset = rule(ds, variable, "a " + name)
+    plan, Xd, Hd, pos, doy, win, uniq = _leased_rows(ds, variable, aggwt, agglev, weights, backup_aggwt, values, dims, second, season,
+                                                     grid, time_values, cells)
     try:
         rb, rw = lists(Xd.device)
-        Hd = _time_by_cell(edd[0], dims) if Hd is None else Hd
-        if Hd.shape != Xd.shape or Hd.dtype != Xd.dtype:
-            raise ValueError("tasmin and tasmax must have the same shape and dtype")
+        if second is not None:
+            Hd = _second_field(Xd, Hd, second, dims)
         rdims = _result_dims(dims, agglev)
         keep_dev = _agg._device_results_wanted() and _is_device_tensor(values) and not ds._was_xarray
         res = []
-        for k0 in range(0, len(ladder), _EDD_LADDER_MAX):
-            thr = [float(e) for e in ladder[k0:k0 + _EDD_LADDER_MAX]]
-            field, status = _engine.edd_ladder_reduce(Xd, Hd, rb, rw, edd[1], thr, doy=doy, windows=win, checked=True)
+        for reduce in launches:
+            field, status = reduce(Xd, Hd, rb, rw, offset, doy=doy, windows=win, checked=True)
             if int(status.item()) & 1:
-                raise ValueError("degree-day ladder: a counted value of %r is +-inf; period totals of a ladder have no daily "
-                                 "route that could give it the daily treatment" % (variable,))
+                raise ValueError("%s: a counted value of %r is +-inf; period totals of %s have no daily route that could give it the "
+                                 "daily treatment" % (name, variable, of))
             got = _periods._contract(plan, field, P, len(uniq), None, None, rdims, agglev, keep_dev, planes=True, compact=pos is not None)
             if got is None:
-                raise ValueError("degree-day ladder: the totals of %r overflow the element type (the dense-family plan met "
-                                 "+-inf)" % (variable,))
+                raise ValueError("%s: the totals of %r overflow the element type (the dense-family plan met +-inf)" % (name, variable))
             res.extend(got)
     except _engine.WaggError:
         _drop_plan(plan)
@@ -379,111 +399,46 @@ def _ladder_totals(ds, variable, aggwt, agglev, weights, backup_aggwt, lists, P,
         plan._lease.release()
     stack = _engine.require_gpu().stack(res) if keep_dev else np.stack(res)
     return stack, rdims, _result_coords(ds, rdims, agglev, uniq), ds._was_xarray
+
+
+def _ladder_totals(ds, variable, aggwt, agglev, weights, backup_aggwt, lists, P, ladder, season, grid, time_values, cells="all"):
+    """Period totals of the degree days of ``variable`` (a degree-day variable; its own terms are ignored) at EVERY threshold of
+    ``ladder`` (``wagg_edd_ladder_reduce_*``, up to 64 thresholds a launch) through :func:`_grouped_totals`; ``stack`` is the
+    (n_thr, P | R, R | P) results in the ladder's order."""
+    def launches():
+        for k0 in range(0, len(ladder), _EDD_LADDER_MAX):
+            thr = [float(e) for e in ladder[k0:k0 + _EDD_LADDER_MAX]]
+            yield lambda X, H, rb, rw, offset, **kw: _engine.edd_ladder_reduce(X, H, rb, rw, offset, thr, **kw)
+
+    return _grouped_totals(ds, variable, aggwt, agglev, weights, backup_aggwt, lists, P, season, grid, time_values, cells,
+                           "degree-day ladder", "a ladder", _degree_day_variable, launches())
 
 
 def _bin_totals(ds, variable, aggwt, agglev, weights, backup_aggwt, lists, P, edges, season, grid, time_values, cells="all"):
-    """Period totals of the days ``variable`` spends in every bin ``[edges[k], edges[k + 1])``: counted first
-    (``wagg_bin_days_reduce_*``, up to 64 bins a launch), then one apply per launch contracts its n_bins * P rows on whatever
-    plan serves the table.  ``variable``: a plain temperature variable, or one shifted by ``convert_kelvin_to_celsius`` (the
-    edges are then in degrees C); a power or a degree-day variable is ValueError.  ``season`` None: every day counts.  Returns
-    ``(stack, rdims, coords, was_xarray)`` like :func:`_ladder_totals`, ``stack`` being the (n_bins, P | R, R | P) results in
-    bin order.  ``cells="referenced"``: all of it on the packed rows of :func:`_referenced_rows`."""
-    from . import periods as _periods
-    values, dims = _gridded_field(ds, variable, P, "a bin count")
-    xform = ds._xforms.get(variable)
-    if ds._edds.get(variable) is not None or (xform is not None and xform[1] != 1):
-        raise ValueError("a bin count needs a plain (or Kelvin-shifted) temperature variable, got %r" % (variable,))
-    offset = 0.0 if xform is None else float(xform[0])
-    prepared, w_eff, uniq, codes, cell_idx, G = _segment_table(ds, variable, aggwt, agglev, weights, backup_aggwt)
-    shape = dict(zip(dims, tuple(values.shape)))
-    ia, io, *_ = _spatial_layout(dims)
-    doy, win = (None, None) if season is None else _stored_season(ds, variable, season, grid, dims, shape, time_values)
-    _engine.require_gpu()
-    make_plan = lambda dtype: _plan_for(cell_idx, codes, w_eff, G, len(uniq), shape["lon"] if ia < io else shape["lat"],
-                                        is_f32=str(dtype).endswith("float32"), layout="TG", prepared=prepared)
-    pos = None
-    if cells == "referenced":
-        plan, Xd, _, pos = _referenced_rows(values, None, dims, make_plan)
-        if pos is not None and win is not None:
-            win = win[pos]
-    else:
-        Xd = _time_by_cell(values, dims)
-        plan = make_plan(Xd.dtype)
-    try:
-        rb, rw = lists(Xd.device)
-        rdims = _result_dims(dims, agglev)
-        keep_dev = _agg._device_results_wanted() and _is_device_tensor(values) and not ds._was_xarray
-        res = []
+    """Period totals of the days ``variable`` spends in every bin ``[edges[k], edges[k + 1])`` (``wagg_bin_days_reduce_*``, up to
+    64 bins a launch) through :func:`_grouped_totals`.  ``variable``: a plain temperature variable, or one shifted by
+    ``convert_kelvin_to_celsius`` (the edges are then in degrees C); a power or a degree-day variable is ValueError.  ``stack``
+    is the (n_bins, P | R, R | P) results in bin order."""
+    def launches():
         for k0 in range(0, len(edges) - 1, _BIN_EDGES_MAX - 1):                  # (consecutive launches share an edge)
             part = [float(e) for e in edges[k0:k0 + _BIN_EDGES_MAX]]
-            field, status = _engine.bin_days_reduce(Xd, rb, rw, offset, part, doy=doy, windows=win, checked=True)
-            if int(status.item()) & 1:
-                raise ValueError("bin count: a counted value of %r is +-inf; period totals of bins have no daily route that could "
-                                 "give it the daily treatment" % (variable,))
-            got = _periods._contract(plan, field, P, len(uniq), None, None, rdims, agglev, keep_dev, planes=True, compact=pos is not None)
-            if got is None:
-                raise ValueError("bin count: the totals of %r overflow the element type (the dense-family plan met +-inf)" % (variable,))
-            res.extend(got)
-    except _engine.WaggError:
-        _drop_plan(plan)
-        raise
-    finally:
-        plan._lease.release()
-    stack = _engine.require_gpu().stack(res) if keep_dev else np.stack(res)
-    return stack, rdims, _result_coords(ds, rdims, agglev, uniq), ds._was_xarray
+            yield lambda X, H, rb, rw, offset, **kw: _engine.bin_days_reduce(X, rb, rw, offset, part, **kw)
+
+    return _grouped_totals(ds, variable, aggwt, agglev, weights, backup_aggwt, lists, P, season, grid, time_values, cells, "bin count",
+                           "bins", _plain_variable, launches())
 
 
 def _hinge_totals(ds, variable, aggwt, agglev, weights, backup_aggwt, lists, P, knots, power, side, tail, season, grid, time_values,
                   cells="all"):
-    """Period totals of the hinges ``max(+-(variable - knots[j]), 0) ** power`` at EVERY knot: summed first
-    (``wagg_hinge_reduce_*``, up to 64 knots a launch), then one apply per launch contracts its n_knots * P rows on whatever
-    plan serves the table.  ``variable``: a plain temperature variable, or one shifted by ``convert_kelvin_to_celsius`` (the
-    knots are then in degrees C and the shift is the kernel's offset); a power or a degree-day variable is ValueError.
-    ``tail``: None, or ``(two tail knots, a, b)`` with a coefficient per knot (``engine.hinge_reduce``).  ``season`` None: every
-    day counts.  Returns ``(stack, rdims, coords, was_xarray)`` like :func:`_bin_totals`, ``stack`` being the (n_knots, P | R,
-    R | P) results in the knots' order.  ``cells="referenced"``: all of it on the packed rows of :func:`_referenced_rows`."""
-    from . import periods as _periods
-    values, dims = _gridded_field(ds, variable, P, "a hinge total")
-    xform = ds._xforms.get(variable)
-    if ds._edds.get(variable) is not None or (xform is not None and xform[1] != 1):
-        raise ValueError("a hinge total needs a plain (or Kelvin-shifted) temperature variable, got %r" % (variable,))
-    offset = 0.0 if xform is None else float(xform[0])
-    prepared, w_eff, uniq, codes, cell_idx, G = _segment_table(ds, variable, aggwt, agglev, weights, backup_aggwt)
-    shape = dict(zip(dims, tuple(values.shape)))
-    ia, io, *_ = _spatial_layout(dims)
-    doy, win = (None, None) if season is None else _stored_season(ds, variable, season, grid, dims, shape, time_values)
-    _engine.require_gpu()
-    make_plan = lambda dtype: _plan_for(cell_idx, codes, w_eff, G, len(uniq), shape["lon"] if ia < io else shape["lat"],
-                                        is_f32=str(dtype).endswith("float32"), layout="TG", prepared=prepared)
-    pos = None
-    if cells == "referenced":
-        plan, Xd, _, pos = _referenced_rows(values, None, dims, make_plan)
-        if pos is not None and win is not None:
-            win = win[pos]
-    else:
-        Xd = _time_by_cell(values, dims)
-        plan = make_plan(Xd.dtype)
-    try:
-        rb, rw = lists(Xd.device)
-        rdims = _result_dims(dims, agglev)
-        keep_dev = _agg._device_results_wanted() and _is_device_tensor(values) and not ds._was_xarray
-        res = []
+    """Period totals of the hinges ``max(+-(variable - knots[j]), 0) ** power`` at EVERY knot (``wagg_hinge_reduce_*``, up to 64
+    knots a launch) through :func:`_grouped_totals`.  ``variable``: as for :func:`_bin_totals` (the knots are in degrees C for a
+    shifted one, and the shift is the kernel's offset).  ``tail``: None, or ``(two tail knots, a, b)`` with a coefficient per
+    knot (``engine.hinge_reduce``).  ``stack`` is the (n_knots, P | R, R | P) results in the knots' order."""
+    def launches():
         for k0 in range(0, len(knots), _HINGE_MAX):
             sl = slice(k0, k0 + _HINGE_MAX)
-            part = None if tail is None else (tail[0], tail[1][sl], tail[2][sl])
-            field, status = _engine.hinge_reduce(Xd, rb, rw, offset, [float(k) for k in knots[sl]], power=power, side=side, tail=part,
-                                                 doy=doy, windows=win, checked=True)
-            if int(status.item()) & 1:
-                raise ValueError("hinge total: a counted value of %r is +-inf; period totals of hinges have no daily route that "
-                                 "could give it the daily treatment" % (variable,))
-            got = _periods._contract(plan, field, P, len(uniq), None, None, rdims, agglev, keep_dev, planes=True, compact=pos is not None)
-            if got is None:
-                raise ValueError("hinge total: the totals of %r overflow the element type (the dense-family plan met +-inf)" % (variable,))
-            res.extend(got)
-    except _engine.WaggError:
-        _drop_plan(plan)
-        raise
-    finally:
-        plan._lease.release()
-    stack = _engine.require_gpu().stack(res) if keep_dev else np.stack(res)
-    return stack, rdims, _result_coords(ds, rdims, agglev, uniq), ds._was_xarray
+            part, cut = [float(k) for k in knots[sl]], None if tail is None else (tail[0], tail[1][sl], tail[2][sl])
+            yield lambda X, H, rb, rw, offset, **kw: _engine.hinge_reduce(X, rb, rw, offset, part, power=power, side=side, tail=cut, **kw)
+
+    return _grouped_totals(ds, variable, aggwt, agglev, weights, backup_aggwt, lists, P, season, grid, time_values, cells, "hinge total",
+                           "hinges", _plain_variable, launches())

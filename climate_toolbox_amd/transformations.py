@@ -242,6 +242,29 @@ def _ladder_thresholds(thresholds):
     return thr
 
 
+def _period_lists(ds, period, season):
+    """``(time_values, labels, grid, lists)`` of a period call on ``ds`` (which has a ``time`` coordinate): the period labels,
+    the dataset's own lat / lon labels for a ``season=`` call (else None), and ``lists(device)`` -- the periods' row lists as
+    ``engine.period_lists`` uploads them, once per device"""
+    from . import periods
+    time_values = np.asarray(ds.coords["time"].values)
+    labels, row_begin, rows = periods.period_rows(time_values, period)
+    grid = None if season is None else (np.asarray(ds.coords["lat"].values), np.asarray(ds.coords["lon"].values))
+    cache = {}
+
+    def lists(device):
+        if str(device) not in cache:
+            cache[str(device)] = periods._engine.period_lists(row_begin, rows, len(time_values), device=device)
+        return cache[str(device)]
+
+    return time_values, labels, grid, lists
+
+
+def _time_as_period(rdims, coords, labels):
+    """the dims and coords of a sum-first result with ``time`` replaced by ``period`` = ``labels``"""
+    return tuple("period" if d == "time" else d for d in rdims), dict({k: v for k, v in coords.items() if k != "time"}, period=labels)
+
+
 def snyder_edd_aggregate(ds, thresholds, aggwt, agglev, weights, tasmin="tasmin", tasmax="tasmax", varname="edd",
                          backup_aggwt="areawt", period=None, season=None, cells="all"):
     """Snyder degree days at EVERY threshold of a ladder, aggregated to regions: the reference's agricultural product (what
@@ -282,23 +305,13 @@ def snyder_edd_aggregate(ds, thresholds, aggwt, agglev, weights, tasmin="tasmin"
         return _agg._reindex_spatial_data_to_regions(minixr.Dataset({varname: var}, coords=dict(ds.coords)), weights)
 
     if period is not None:
-        from . import periods, seasons
+        from . import seasons
         if "time" not in ds.coords:
             raise ValueError("the dataset has no 'time' coordinate to form periods from")
-        time_values = np.asarray(ds.coords["time"].values)
-        labels, row_begin, rows = periods.period_rows(time_values, period)
-        grid = None if season is None else (np.asarray(ds.coords["lat"].values), np.asarray(ds.coords["lon"].values))
-        cache = {}
-
-        def lists(device):
-            if str(device) not in cache:
-                cache[str(device)] = periods._engine.period_lists(row_begin, rows, len(time_values), device=device)
-            return cache[str(device)]
-
+        time_values, labels, grid, lists = _period_lists(ds, period, season)
         res, rdims, coords, was_xr = seasons._ladder_totals(reindexed(base._values, base._edd[0]), varname, aggwt, agglev, weights,
                                                             backup_aggwt, lists, len(labels), thr, season, grid, time_values, cells=cells)
-        rdims = tuple("period" if d == "time" else d for d in rdims)
-        coords = dict({k: v for k, v in coords.items() if k != "time"}, period=labels)
+        rdims, coords = _time_as_period(rdims, coords, labels)
     else:
         # daily results: the fused daily apply takes four thresholds a pass.  The table is joined to the grid once and a
         # host-resident pair of fields uploaded once; every pass then reads the same two device buffers.
@@ -320,6 +333,33 @@ def snyder_edd_aggregate(ds, thresholds, aggwt, agglev, weights, tasmin="tasmin"
     out = _agg._as_dataset({varname: res}, ("refTemp",) + tuple(rdims), dict(coords, refTemp=thr), was_xr)
     out[varname].attrs["units"] = units
     return out
+
+
+def _period_setup(name, what, ds, tas, weights, period, season, cells, leap_days):
+    """What :func:`tas_bins_aggregate` and the hinge calls do alike behind the checks of their own parameter list, in this order:
+    the period / cells / leap_days checks (``name``: the public call, ``what``: "a bin count" / "a hinge total", for the
+    messages), weights read from a path, the ``time`` coordinate, ``remove_leap_days``, the rule that ``ds[tas]`` is a plain or
+    Kelvin-shifted temperature variable, the period lists, and the variable joined to the table.  Returns ``(reindexed dataset,
+    variable, weights, time_values, labels, grid, lists)``."""
+    if period is None:
+        raise ValueError("%s needs period=: %s is a sum over days" % (name, what) + ("" if season is None else " (season= needs period=)"))
+    from .periods import _check_cells
+    _check_cells(cells)
+    if leap_days not in ("keep", "drop"):
+        raise ValueError("leap_days must be 'keep' or 'drop', got %r" % (leap_days,))
+    if isinstance(weights, str):
+        weights = _agg.prepare_spatial_weights_data(weights)
+    if "time" not in ds.coords:
+        raise ValueError("the dataset has no 'time' coordinate to form periods from")
+    if leap_days == "drop":
+        ds = remove_leap_days(ds)
+    var = ds[tas]
+    xform = getattr(var, "_xform", None)
+    if getattr(var, "_edd", None) is not None or (xform is not None and xform[1] != 1):
+        raise ValueError("%s needs a plain (or Kelvin-shifted) temperature variable, got %r" % (what, tas))
+    time_values, labels, grid, lists = _period_lists(ds, period, season)
+    re = _agg._reindex_spatial_data_to_regions(minixr.Dataset({tas: var}, coords=dict(ds.coords)), weights)
+    return re, var, weights, time_values, labels, grid, lists
 
 
 def _bin_edges(edges):
@@ -358,40 +398,13 @@ def tas_bins_aggregate(ds, edges, aggwt, agglev, weights, tas="tas", varname="ta
     ``attrs["bin_edges"]`` = the edges as one string (``", ".join(repr(float(e)) ...)``); ``results_on_device()`` is honoured;
     a (lat, lon, time) field is transposed on the device, a host-resident one uploaded whole (packed for "referenced")."""
     e = _bin_edges(edges)
-    if period is None:
-        raise ValueError("tas_bins_aggregate needs period=: a bin count is a sum over days" +
-                         ("" if season is None else " (season= needs period=)"))
-    from .periods import _check_cells
-    _check_cells(cells)
-    if leap_days not in ("keep", "drop"):
-        raise ValueError("leap_days must be 'keep' or 'drop', got %r" % (leap_days,))
-    if isinstance(weights, str):
-        weights = _agg.prepare_spatial_weights_data(weights)
-    from . import periods, seasons
-    if "time" not in ds.coords:
-        raise ValueError("the dataset has no 'time' coordinate to form periods from")
-    if leap_days == "drop":
-        ds = remove_leap_days(ds)
-    var = ds[tas]
-    xform = getattr(var, "_xform", None)
-    if getattr(var, "_edd", None) is not None or (xform is not None and xform[1] != 1):
-        raise ValueError("a bin count needs a plain (or Kelvin-shifted) temperature variable, got %r" % (tas,))
-    time_values = np.asarray(ds.coords["time"].values)
-    labels, row_begin, rows = periods.period_rows(time_values, period)
-    grid = None if season is None else (np.asarray(ds.coords["lat"].values), np.asarray(ds.coords["lon"].values))
-    re = _agg._reindex_spatial_data_to_regions(minixr.Dataset({tas: var}, coords=dict(ds.coords)), weights)
-    cache = {}
-
-    def lists(device):
-        if str(device) not in cache:
-            cache[str(device)] = periods._engine.period_lists(row_begin, rows, len(time_values), device=device)
-        return cache[str(device)]
-
+    re, _, weights, time_values, labels, grid, lists = _period_setup("tas_bins_aggregate", "a bin count", ds, tas, weights, period, season,
+                                                                     cells, leap_days)
+    from . import seasons
     res, rdims, coords, was_xr = seasons._bin_totals(re, tas, aggwt, agglev, weights, backup_aggwt, lists, len(labels), e, season, grid,
                                                      time_values, cells=cells)
-    rdims = tuple("period" if d == "time" else d for d in rdims)
-    coords = dict({k: v for k, v in coords.items() if k != "time"}, period=labels, bin=e[:-1].copy())
-    out = _agg._as_dataset({varname: res}, ("bin",) + tuple(rdims), coords, was_xr)
+    rdims, coords = _time_as_period(rdims, coords, labels)
+    out = _agg._as_dataset({varname: res}, ("bin",) + tuple(rdims), dict(coords, bin=e[:-1].copy()), was_xr)
     out[varname].attrs["units"] = "days"
     out[varname].attrs["bin_edges"] = ", ".join(repr(float(x)) for x in e)
     return out
@@ -405,38 +418,12 @@ def _hinge_call(name, ds, knots, tail, power, side, aggwt, agglev, weights, tas,
         raise ValueError("power must be 1, 2 or 3, got %r" % (power,))
     if side not in ("above", "below"):
         raise ValueError("side must be 'above' or 'below', got %r" % (side,))
-    if period is None:
-        raise ValueError("%s needs period=: a hinge total is a sum over days" % name + ("" if season is None else " (season= needs period=)"))
-    from .periods import _check_cells
-    _check_cells(cells)
-    if leap_days not in ("keep", "drop"):
-        raise ValueError("leap_days must be 'keep' or 'drop', got %r" % (leap_days,))
-    if isinstance(weights, str):
-        weights = _agg.prepare_spatial_weights_data(weights)
-    from . import periods, seasons
-    if "time" not in ds.coords:
-        raise ValueError("the dataset has no 'time' coordinate to form periods from")
-    if leap_days == "drop":
-        ds = remove_leap_days(ds)
-    var = ds[tas]
-    xform = getattr(var, "_xform", None)
-    if getattr(var, "_edd", None) is not None or (xform is not None and xform[1] != 1):
-        raise ValueError("a hinge total needs a plain (or Kelvin-shifted) temperature variable, got %r" % (tas,))
-    time_values = np.asarray(ds.coords["time"].values)
-    labels, row_begin, rows = periods.period_rows(time_values, period)
-    grid = None if season is None else (np.asarray(ds.coords["lat"].values), np.asarray(ds.coords["lon"].values))
-    re = _agg._reindex_spatial_data_to_regions(minixr.Dataset({tas: var}, coords=dict(ds.coords)), weights)
-    cache = {}
-
-    def lists(device):
-        if str(device) not in cache:
-            cache[str(device)] = periods._engine.period_lists(row_begin, rows, len(time_values), device=device)
-        return cache[str(device)]
-
+    re, var, weights, time_values, labels, grid, lists = _period_setup(name, "a hinge total", ds, tas, weights, period, season, cells,
+                                                                       leap_days)
+    from . import seasons
     res, rdims, coords, was_xr = seasons._hinge_totals(re, tas, aggwt, agglev, weights, backup_aggwt, lists, len(labels), knots, power,
                                                        side, tail, season, grid, time_values, cells=cells)
-    rdims = tuple("period" if d == "time" else d for d in rdims)
-    coords = dict({k: v for k, v in coords.items() if k != "time"}, period=labels)
+    rdims, coords = _time_as_period(rdims, coords, labels)
     return res, rdims, coords, was_xr, _units(var)
 
 
