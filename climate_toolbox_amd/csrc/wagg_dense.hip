@@ -1138,21 +1138,29 @@ static int dense_apply(wagg_dense *d, const T *X_dev, int64_t Tn, int64_t ldx, c
     return WAGG_OK;
 }
 
+// ---- the typed apply layer (wagg_entry.h) of the dense-family plan kind: templates on the element type, instantiated at the
+// end of the file.  (wagg::dense_apply above is the launch itself, with the transform of the pack stage as an argument)
 template <typename T>
-static int apply_poly(wagg_dense *d, const T *X_dev, int64_t Tn, int64_t ldx, double offset, int power, T *out_dev,
-                      int64_t ldo, int ksplit, void *stream, bool exact = false) {
-    WAGG_REQUIRE(power >= 1 && power <= 16, "power must lie in [1, 16], got %d", power);
-    PackXfT<T> xf;
-    xf.mode = power; xf.off = (T)offset;
-    return dense_apply<T>(d, X_dev, Tn, ldx, xf, out_dev, ldo, ksplit, stream, exact);
+int entry::dense_apply(wagg_dense *d, const T *X_dev, int64_t Tn, int64_t ldx, T *out_dev, int64_t ldo, int ksplit, void *stream,
+                       bool exact) {
+    return wagg::dense_apply<T>(d, X_dev, Tn, ldx, PackXfT<T>{}, out_dev, ldo, ksplit, stream, exact);
 }
 
 template <typename T>
-static int apply_edd(wagg_dense *d, const T *tasmin, const T *tasmax, int64_t Tn, int64_t ldx, double offset,
-                     double threshold, T *out_dev, int64_t ldo, int ksplit, void *stream, bool exact = false) {
+int entry::dense_apply_poly(wagg_dense *d, const T *X_dev, int64_t Tn, int64_t ldx, double offset, int power, T *out_dev,
+                            int64_t ldo, int ksplit, void *stream, bool exact) {
+    WAGG_REQUIRE(power >= 1 && power <= 16, "power must lie in [1, 16], got %d", power);
+    PackXfT<T> xf;
+    xf.mode = power; xf.off = (T)offset;
+    return wagg::dense_apply<T>(d, X_dev, Tn, ldx, xf, out_dev, ldo, ksplit, stream, exact);
+}
+
+template <typename T>
+int entry::dense_apply_edd(wagg_dense *d, const T *tasmin, const T *tasmax, int64_t Tn, int64_t ldx, double offset,
+                           double threshold, T *out_dev, int64_t ldo, int ksplit, void *stream, bool exact) {
     PackXfT<T> xf;
     xf.mode = XF_EDD; xf.off = (T)offset; xf.thr = (T)threshold; xf.X2 = tasmax;
-    return dense_apply<T>(d, tasmin, Tn, ldx, xf, out_dev, ldo, ksplit, stream, exact);
+    return wagg::dense_apply<T>(d, tasmin, Tn, ldx, xf, out_dev, ldo, ksplit, stream, exact);
 }
 
 }  // namespace wagg
@@ -1302,33 +1310,6 @@ extern "C" int wagg_dense_get_den(const wagg_dense *d, double *den_host) {
     return WAGG_OK;
 }
 
-int wagg::entry::dense_apply_f32(wagg_dense *d, const float *X_dev, int64_t T, int64_t ldx,
-                                    float *out_dev, int64_t ldo, int ksplit, void *stream, bool exact) {
-    return wagg::dense_apply<float>(d, X_dev, T, ldx, wagg::PackXfT<float>{}, out_dev, ldo, ksplit, stream, exact);
-}
-int wagg::entry::dense_apply_f64(wagg_dense *d, const double *X_dev, int64_t T, int64_t ldx,
-                                    double *out_dev, int64_t ldo, int ksplit, void *stream) {
-    return wagg::dense_apply<double>(d, X_dev, T, ldx, wagg::PackXfT<double>{}, out_dev, ldo, ksplit, stream);
-}
-int wagg::entry::dense_apply_poly_f32(wagg_dense *d, const float *X_dev, int64_t T, int64_t ldx, double offset,
-                                         int power, float *out_dev, int64_t ldo, int ksplit, void *stream, bool exact) {
-    return wagg::apply_poly<float>(d, X_dev, T, ldx, offset, power, out_dev, ldo, ksplit, stream, exact);
-}
-int wagg::entry::dense_apply_poly_f64(wagg_dense *d, const double *X_dev, int64_t T, int64_t ldx, double offset,
-                                         int power, double *out_dev, int64_t ldo, int ksplit, void *stream) {
-    return wagg::apply_poly<double>(d, X_dev, T, ldx, offset, power, out_dev, ldo, ksplit, stream);
-}
-int wagg::entry::dense_apply_edd_f32(wagg_dense *d, const float *tasmin_dev, const float *tasmax_dev, int64_t T,
-                                        int64_t ldx, double offset, double threshold, float *out_dev, int64_t ldo,
-                                        int ksplit, void *stream, bool exact) {
-    return wagg::apply_edd<float>(d, tasmin_dev, tasmax_dev, T, ldx, offset, threshold, out_dev, ldo, ksplit, stream, exact);
-}
-int wagg::entry::dense_apply_edd_f64(wagg_dense *d, const double *tasmin_dev, const double *tasmax_dev, int64_t T,
-                                        int64_t ldx, double offset, double threshold, double *out_dev, int64_t ldo,
-                                        int ksplit, void *stream) {
-    return wagg::apply_edd<double>(d, tasmin_dev, tasmax_dev, T, ldx, offset, threshold, out_dev, ldo, ksplit, stream);
-}
-
 namespace wagg {
 static int check_dense_device(const wagg_dense *d) {
     int cur = 0;
@@ -1338,8 +1319,7 @@ static int check_dense_device(const wagg_dense *d) {
 }
 
 template <typename T>
-static int dense_apply_host(wagg_dense *d, const T *X_host, int64_t Tn, int64_t ldx, T *out_host, int64_t ldo, int flags,
-                            bool exact = false) {
+int entry::dense_apply_host(wagg_dense *d, const T *X_host, int64_t Tn, int64_t ldx, T *out_host, int64_t ldo, int flags, bool exact) {
     clear_error();
     WAGG_REQUIRE(d != nullptr, "dense plan is NULL");
     WAGG_REQUIRE(Tn >= 0, "T < 0");
@@ -1354,21 +1334,21 @@ static int dense_apply_host(wagg_dense *d, const T *X_host, int64_t Tn, int64_t 
         WAGG_HIP(dout.alloc((size_t)(Tn * ldo)));
         const bool pin = (flags & WAGG_HOST_PIN) != 0;
         if (int rc = copy_to_device(dx.p, X_host, sizeof(T) * (size_t)((Tn - 1) * ldx + d->G), pin)) return rc;
-        const int rc = dense_apply<T>(d, dx.p, Tn, ldx, PackXfT<T>{}, dout.p, ldo, 0, nullptr, exact);
+        const int rc = entry::dense_apply<T>(d, dx.p, Tn, ldx, dout.p, ldo, 0, nullptr, exact);
         if (rc != WAGG_OK) return rc;
         WAGG_HIP(hipDeviceSynchronize());
         return copy_rows_to_host(out_host, dout.p, Tn, sizeof(T) * (size_t)ldo, sizeof(T) * (size_t)d->R, pin);
     }
     return stream_host_rows<T>(X_host, Tn, ldx, d->G, out_host, ldo, d->R, flags, d->spmm ? SpT<T>::TB : DT<T>::MT_MAX * 16, 1, nullptr,
                                [&](int, const T *xd, int64_t rows, T *od, hipStream_t st) {
-                                   return dense_apply<T>(d, xd, rows, ldx, PackXfT<T>{}, od, ldo, 0, (void *)st, exact);
+                                   return entry::dense_apply<T>(d, xd, rows, ldx, od, ldo, 0, (void *)st, exact);
                                },
                                [](int, hipStream_t) {});
 }
 
 // multi-device form: one replica of the dense-family plan per device (wagg_apply_host_multi_* says how the blocks travel)
 template <typename T>
-static int dense_apply_host_multi(wagg_dense *const *plans, const int *devices, int n, const T *X_host, int64_t Tn, int64_t ldx,
+int entry::dense_apply_host_multi(wagg_dense *const *plans, const int *devices, int n, const T *X_host, int64_t Tn, int64_t ldx,
                                   T *out_host, int64_t ldo, int flags) {
     clear_error();
     WAGG_REQUIRE(plans && devices && n >= 1 && n <= 64, "need 1..64 plan replicas and their devices");
@@ -1388,7 +1368,7 @@ static int dense_apply_host_multi(wagg_dense *const *plans, const int *devices, 
     WAGG_REQUIRE(ldx >= d0->G && ldo >= d0->R, "ldx/ldo too small");
     const int rc = stream_host_rows<T>(X_host, Tn, ldx, d0->G, out_host, ldo, d0->R, flags, d0->spmm ? SpT<T>::TB : DT<T>::MT_MAX * 16, n, devices,
                                        [&](int s, const T *xd, int64_t rows, T *od, hipStream_t st) {
-                                           return dense_apply<T>(plans[s], xd, rows, ldx, PackXfT<T>{}, od, ldo, 0, (void *)st);
+                                           return entry::dense_apply<T>(plans[s], xd, rows, ldx, od, ldo, 0, (void *)st);
                                        },
                                        [](int, hipStream_t) {});
     // Every pipeline has drained.  A replica's pack stage leaves its +-inf note in the replica's own word: the caller asks
@@ -1401,23 +1381,6 @@ static int dense_apply_host_multi(wagg_dense *const *plans, const int *devices, 
 }
 }  // namespace wagg
 
-int wagg::entry::dense_apply_host_f32(wagg_dense *d, const float *X_host, int64_t T, int64_t ldx,
-                                         float *out_host, int64_t ldo, int flags, bool exact) {
-    return wagg::dense_apply_host<float>(d, X_host, T, ldx, out_host, ldo, flags, exact);
-}
-int wagg::entry::dense_apply_host_f64(wagg_dense *d, const double *X_host, int64_t T, int64_t ldx,
-                                         double *out_host, int64_t ldo, int flags) {
-    return wagg::dense_apply_host<double>(d, X_host, T, ldx, out_host, ldo, flags);
-}
-int wagg::entry::dense_apply_host_multi_f32(wagg_dense *const *plans, const int *devices, int n_devices, const float *X_host,
-                                               int64_t T, int64_t ldx, float *out_host, int64_t ldo, int flags) {
-    return wagg::dense_apply_host_multi<float>(plans, devices, n_devices, X_host, T, ldx, out_host, ldo, flags);
-}
-int wagg::entry::dense_apply_host_multi_f64(wagg_dense *const *plans, const int *devices, int n_devices, const double *X_host,
-                                               int64_t T, int64_t ldx, double *out_host, int64_t ldo, int flags) {
-    return wagg::dense_apply_host_multi<double>(plans, devices, n_devices, X_host, T, ldx, out_host, ldo, flags);
-}
-
 extern "C" int wagg_dense_saw_inf(wagg_dense *d, void *stream, int *saw) {
     using namespace wagg;
     WAGG_REQUIRE(d && saw, "NULL argument");
@@ -1426,3 +1389,17 @@ extern "C" int wagg_dense_saw_inf(wagg_dense *d, void *stream, int *saw) {
     *(volatile int *)d->inf_host = 0;
     return WAGG_OK;
 }
+
+// the typed apply layer of the dense-family plan kind, for both element types
+namespace wagg {
+#define WAGG_ENTRY_DENSE(T)                                                                                                              \
+    template int entry::dense_apply<T>(wagg_dense *, const T *, int64_t, int64_t, T *, int64_t, int, void *, bool);                      \
+    template int entry::dense_apply_poly<T>(wagg_dense *, const T *, int64_t, int64_t, double, int, T *, int64_t, int, void *, bool);    \
+    template int entry::dense_apply_edd<T>(wagg_dense *, const T *, const T *, int64_t, int64_t, double, double, T *, int64_t, int,      \
+                                           void *, bool);                                                                                \
+    template int entry::dense_apply_host<T>(wagg_dense *, const T *, int64_t, int64_t, T *, int64_t, int, bool);                         \
+    template int entry::dense_apply_host_multi<T>(wagg_dense *const *, const int *, int, const T *, int64_t, int64_t, T *, int64_t, int);
+WAGG_ENTRY_DENSE(float)
+WAGG_ENTRY_DENSE(double)
+#undef WAGG_ENTRY_DENSE
+}  // namespace wagg

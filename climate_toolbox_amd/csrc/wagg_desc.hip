@@ -40,19 +40,14 @@ int unsupported(const wagg_apply_desc &d, const char *why) {
 
 template <typename T>
 int run_segment(const wagg_apply_desc &d) {
-    constexpr bool f32 = sizeof(T) == 4;
     const T *x = static_cast<const T *>(d.x), *x2 = static_cast<const T *>(d.x2);
     T *out = static_cast<T *>(d.out);
     const wagg_plan *plan = static_cast<const wagg_plan *>(d.plan);
     // many-plans (wagg_plan_create_many): looked at only where the single-plan path would use the handle anyway
     auto many = [&]() -> int {
         if (d.transform != WAGG_XF_NONE) return unsupported(d, "a many-plan aggregates the field as it is (no fused transform)");
-        if (d.source == WAGG_SRC_DEVICE) {
-            if constexpr (f32) return entry::apply_many_f32(plan, x, d.T, d.ldx, d.layout, out, d.ldo, d.out_layout, d.stream);
-            else return entry::apply_many_f64(plan, x, d.T, d.ldx, d.layout, out, d.ldo, d.out_layout, d.stream);
-        }
-        if constexpr (f32) return entry::apply_many_host_f32(plan, x, d.T, d.ldx, d.layout, out, d.ldo, d.out_layout, d.flags);
-        else return entry::apply_many_host_f64(plan, x, d.T, d.ldx, d.layout, out, d.ldo, d.out_layout, d.flags);
+        if (d.source == WAGG_SRC_DEVICE) return entry::apply_many<T>(plan, x, d.T, d.ldx, d.layout, out, d.ldo, d.out_layout, d.stream);
+        return entry::apply_many_host<T>(plan, x, d.T, d.ldx, d.layout, out, d.ldo, d.out_layout, d.flags);
     };
     auto any_many = [&](const wagg_plan *const *plans) {
         for (int i = 0; i < d.n_plans; ++i) if (entry::is_many_plan(plans[i])) return true;
@@ -62,44 +57,32 @@ int run_segment(const wagg_apply_desc &d) {
         if (d.source != WAGG_SRC_DEVICE || d.transform != WAGG_XF_NONE || d.layout != WAGG_LAYOUT_TG || d.out_layout != WAGG_OUT_TR)
             return unsupported(d, "WAGG_APPLY_COMPACT_ROWS takes device-resident packed (time, cell) rows, no transform, and gives a (time, region) result");
         if (entry::is_many_plan(plan)) return unsupported(d, "a many-plan has no compact row");
-        if constexpr (f32) return entry::apply_compact_f32(plan, x, d.T, d.ldx, out, d.ldo, d.stream);
-        else return entry::apply_compact_f64(plan, x, d.T, d.ldx, out, d.ldo, d.stream);
+        return entry::apply_compact<T>(plan, x, d.T, d.ldx, out, d.ldo, d.stream);
     }
     switch (d.source) {
         case WAGG_SRC_DEVICE:
             if (entry::is_many_plan(plan)) return many();
-            if (d.transform == WAGG_XF_NONE) {
-                if constexpr (f32) return entry::apply_f32(plan, x, d.T, d.ldx, d.layout, out, d.ldo, d.out_layout, d.stream);
-                else return entry::apply_f64(plan, x, d.T, d.ldx, d.layout, out, d.ldo, d.out_layout, d.stream);
-            }
-            if (d.transform == WAGG_XF_POLY) {
-                if constexpr (f32) return entry::apply_poly_f32(plan, x, d.T, d.ldx, d.layout, d.offset, d.pow_first, d.n_pow, out, d.ldo, d.out_pstride, d.out_layout, d.stream);
-                else return entry::apply_poly_f64(plan, x, d.T, d.ldx, d.layout, d.offset, d.pow_first, d.n_pow, out, d.ldo, d.out_pstride, d.out_layout, d.stream);
-            }
-            if constexpr (f32) return entry::apply_edd_f32(plan, x, x2, d.T, d.ldx, d.layout, d.offset, d.thresholds, d.n_thr, out, d.ldo, d.out_pstride, d.out_layout, d.stream);
-            else return entry::apply_edd_f64(plan, x, x2, d.T, d.ldx, d.layout, d.offset, d.thresholds, d.n_thr, out, d.ldo, d.out_pstride, d.out_layout, d.stream);
+            if (d.transform == WAGG_XF_NONE) return entry::apply<T>(plan, x, d.T, d.ldx, d.layout, out, d.ldo, d.out_layout, d.stream);
+            if (d.transform == WAGG_XF_POLY)
+                return entry::apply_poly<T>(plan, x, d.T, d.ldx, d.layout, d.offset, d.pow_first, d.n_pow, out, d.ldo, d.out_pstride, d.out_layout, d.stream);
+            return entry::apply_edd<T>(plan, x, x2, d.T, d.ldx, d.layout, d.offset, d.thresholds, d.n_thr, out, d.ldo, d.out_pstride, d.out_layout, d.stream);
         case WAGG_SRC_HOST:
             if (d.transform == WAGG_XF_NONE) {
                 if (entry::is_many_plan(plan)) return many();
-                if constexpr (f32) return entry::apply_host_ex_f32(plan, x, d.T, d.ldx, d.layout, out, d.ldo, d.out_layout, d.flags);
-                else return entry::apply_host_ex_f64(plan, x, d.T, d.ldx, d.layout, out, d.ldo, d.out_layout, d.flags);
+                return entry::apply_host_ex<T>(plan, x, d.T, d.ldx, d.layout, out, d.ldo, d.out_layout, d.flags);
             }
             if (d.layout != WAGG_LAYOUT_TG || d.out_layout != WAGG_OUT_TR)
                 return unsupported(d, "fused transforms of host-resident fields take (time, gridcell) data and give (time, region) results");
             if (entry::is_many_plan(plan)) return many();
-            if (d.transform == WAGG_XF_POLY) {
-                if constexpr (f32) return entry::apply_poly_host_f32(plan, x, d.T, d.ldx, d.offset, d.pow_first, d.n_pow, out, d.ldo, d.out_pstride, d.flags);
-                else return entry::apply_poly_host_f64(plan, x, d.T, d.ldx, d.offset, d.pow_first, d.n_pow, out, d.ldo, d.out_pstride, d.flags);
-            }
-            if constexpr (f32) return entry::apply_edd_host_f32(plan, x, x2, d.T, d.ldx, d.offset, d.thresholds, d.n_thr, out, d.ldo, d.out_pstride, d.flags);
-            else return entry::apply_edd_host_f64(plan, x, x2, d.T, d.ldx, d.offset, d.thresholds, d.n_thr, out, d.ldo, d.out_pstride, d.flags);
+            if (d.transform == WAGG_XF_POLY)
+                return entry::apply_poly_host<T>(plan, x, d.T, d.ldx, d.offset, d.pow_first, d.n_pow, out, d.ldo, d.out_pstride, d.flags);
+            return entry::apply_edd_host<T>(plan, x, x2, d.T, d.ldx, d.offset, d.thresholds, d.n_thr, out, d.ldo, d.out_pstride, d.flags);
         case WAGG_SRC_HOST_MULTI: {
             if (d.transform != WAGG_XF_NONE) return unsupported(d, "the multi-device host pipeline has no fused transforms");
             if (d.layout != WAGG_LAYOUT_TG || d.out_layout != WAGG_OUT_TR) return unsupported(d, "(time, gridcell) data and (time, region) results only");
             const wagg_plan *const *plans = static_cast<const wagg_plan *const *>(d.plan);
             if (any_many(plans)) return unsupported(d, "a many-plan has no multi-device form");
-            if constexpr (f32) return entry::apply_host_multi_f32(plans, d.devices, d.n_plans, x, d.T, d.ldx, out, d.ldo, d.flags);
-            else return entry::apply_host_multi_f64(plans, d.devices, d.n_plans, x, d.T, d.ldx, out, d.ldo, d.flags);
+            return entry::apply_host_multi<T>(plans, d.devices, d.n_plans, x, d.T, d.ldx, out, d.ldo, d.flags);
         }
         default: {
             if (d.transform != WAGG_XF_NONE) return unsupported(d, "the sharded form has no fused transforms");
@@ -108,15 +91,13 @@ int run_segment(const wagg_apply_desc &d) {
             const wagg_plan *const *plans = static_cast<const wagg_plan *const *>(d.plan);
             const T *const *xs = static_cast<const T *const *>(d.x);
             if (any_many(plans)) return unsupported(d, "a many-plan has no sharded form");
-            if constexpr (f32) return entry::apply_sharded_f32(g, plans, xs, d.rows, d.ldx, out, d.ldo, d.root);
-            else return entry::apply_sharded_f64(g, plans, xs, d.rows, d.ldx, out, d.ldo, d.root);
+            return entry::apply_sharded<T>(g, plans, xs, d.rows, d.ldx, out, d.ldo, d.root);
         }
     }
 }
 
 template <typename T>
 int run_dense(const wagg_apply_desc &d) {
-    constexpr bool f32 = sizeof(T) == 4;
     if (d.layout != WAGG_LAYOUT_TG || d.out_layout != WAGG_OUT_TR)
         return unsupported(d, "dense-family plans take (time, gridcell) data and give (time, region) results");
     const T *x = static_cast<const T *>(d.x), *x2 = static_cast<const T *>(d.x2);
@@ -130,59 +111,83 @@ int run_dense(const wagg_apply_desc &d) {
     const int host_flags = d.flags & ~WAGG_APPLY_EXACT_F32;
     switch (d.source) {
         case WAGG_SRC_DEVICE:
-            if (d.transform == WAGG_XF_NONE) {
-                if constexpr (f32) return entry::dense_apply_f32(plan, x, d.T, d.ldx, out, d.ldo, d.ksplit, d.stream, exact);
-                else return entry::dense_apply_f64(plan, x, d.T, d.ldx, out, d.ldo, d.ksplit, d.stream);
-            }
+            if (d.transform == WAGG_XF_NONE) return entry::dense_apply<T>(plan, x, d.T, d.ldx, out, d.ldo, d.ksplit, d.stream, exact);
             if (d.transform == WAGG_XF_POLY) {
                 if (d.n_pow != 1) return unsupported(d, "one power per call (n_pow == 1, the power in pow_first)");
-                if constexpr (f32) return entry::dense_apply_poly_f32(plan, x, d.T, d.ldx, d.offset, d.pow_first, out, d.ldo, d.ksplit, d.stream, exact);
-                else return entry::dense_apply_poly_f64(plan, x, d.T, d.ldx, d.offset, d.pow_first, out, d.ldo, d.ksplit, d.stream);
+                return entry::dense_apply_poly<T>(plan, x, d.T, d.ldx, d.offset, d.pow_first, out, d.ldo, d.ksplit, d.stream, exact);
             }
             if (d.n_thr != 1 || d.thresholds == nullptr) return unsupported(d, "one threshold per call (n_thr == 1)");
-            if constexpr (f32) return entry::dense_apply_edd_f32(plan, x, x2, d.T, d.ldx, d.offset, d.thresholds[0], out, d.ldo, d.ksplit, d.stream, exact);
-            else return entry::dense_apply_edd_f64(plan, x, x2, d.T, d.ldx, d.offset, d.thresholds[0], out, d.ldo, d.ksplit, d.stream);
+            return entry::dense_apply_edd<T>(plan, x, x2, d.T, d.ldx, d.offset, d.thresholds[0], out, d.ldo, d.ksplit, d.stream, exact);
         case WAGG_SRC_HOST:
             if (d.transform != WAGG_XF_NONE) return unsupported(d, "host-resident fields through a dense-family plan have no fused transforms");
-            if constexpr (f32) return entry::dense_apply_host_f32(plan, x, d.T, d.ldx, out, d.ldo, host_flags, exact);
-            else return entry::dense_apply_host_f64(plan, x, d.T, d.ldx, out, d.ldo, host_flags);
+            return entry::dense_apply_host<T>(plan, x, d.T, d.ldx, out, d.ldo, host_flags, exact);
         case WAGG_SRC_HOST_MULTI: {
             if (d.transform != WAGG_XF_NONE) return unsupported(d, "the multi-device host pipeline has no fused transforms");
             wagg_dense *const *plans = static_cast<wagg_dense *const *>(d.plan);
-            if constexpr (f32) return entry::dense_apply_host_multi_f32(plans, d.devices, d.n_plans, x, d.T, d.ldx, out, d.ldo, d.flags);
-            else return entry::dense_apply_host_multi_f64(plans, d.devices, d.n_plans, x, d.T, d.ldx, out, d.ldo, d.flags);
+            return entry::dense_apply_host_multi<T>(plans, d.devices, d.n_plans, x, d.T, d.ldx, out, d.ldo, d.flags);
         }
         default: {
             if (d.transform != WAGG_XF_NONE) return unsupported(d, "the sharded form has no fused transforms");
             wagg_shard_group *g = static_cast<wagg_shard_group *>(d.group);
             wagg_dense *const *plans = static_cast<wagg_dense *const *>(d.plan);
             const T *const *xs = static_cast<const T *const *>(d.x);
-            if constexpr (f32) return entry::dense_apply_sharded_f32(g, plans, xs, d.rows, d.ldx, out, d.ldo, d.root);
-            else return entry::dense_apply_sharded_f64(g, plans, xs, d.rows, d.ldx, out, d.ldo, d.root);
+            return entry::dense_apply_sharded<T>(g, plans, xs, d.rows, d.ldx, out, d.ldo, d.root);
         }
     }
 }
 
-// descriptor of the common shape; the wrappers below set what differs
-wagg_apply_desc base(int plan_kind, int elem, int source, const void *plan, const void *x, int64_t T, int64_t ldx, void *out, int64_t ldo) {
+// ---- what the exported wrappers below are made of: one descriptor builder per source, the element code from the pointer type
+template <typename T> constexpr int elem_code = std::is_same_v<T, float> ? WAGG_T_F32 : WAGG_T_F64;
+
+// descriptor of the common shape; the builders set what differs
+template <typename T>
+wagg_apply_desc base(int plan_kind, int source, const void *plan, const void *x, int64_t Tn, int64_t ldx, T *out, int64_t ldo) {
+    static_assert(std::is_same_v<T, float> || std::is_same_v<T, double>, "float or double");
     wagg_apply_desc d;
     std::memset(&d, 0, sizeof(d));
     d.struct_size = sizeof(d);
-    d.plan_kind = plan_kind; d.elem = elem; d.source = source; d.transform = WAGG_XF_NONE;
-    d.plan = plan; d.x = x; d.T = T; d.ldx = ldx; d.out = out; d.ldo = ldo;
+    d.plan_kind = plan_kind; d.elem = elem_code<T>; d.source = source; d.transform = WAGG_XF_NONE;
+    d.plan = plan; d.x = x; d.T = Tn; d.ldx = ldx; d.out = out; d.ldo = ldo;
     d.layout = WAGG_LAYOUT_TG; d.out_layout = WAGG_OUT_TR;
     d.pow_first = 1; d.n_pow = 1;
     return d;
 }
-wagg_apply_desc &poly(wagg_apply_desc &d, double offset, int pow_first, int n_pow, int64_t pstride) {
+template <typename T>
+wagg_apply_desc on_device(int plan_kind, const void *plan, const T *x, int64_t Tn, int64_t ldx, T *out, int64_t ldo, void *stream, int ksplit = 0) {
+    wagg_apply_desc d = base(plan_kind, WAGG_SRC_DEVICE, plan, x, Tn, ldx, out, ldo);
+    d.ksplit = ksplit; d.stream = stream;
+    return d;
+}
+template <typename T>
+wagg_apply_desc on_host(int plan_kind, const void *plan, const T *x, int64_t Tn, int64_t ldx, T *out, int64_t ldo, int flags) {
+    wagg_apply_desc d = base(plan_kind, WAGG_SRC_HOST, plan, x, Tn, ldx, out, ldo);
+    d.flags = flags;
+    return d;
+}
+template <typename T>
+wagg_apply_desc on_host_multi(int plan_kind, const void *plans, const int *devices, int n_devices, const T *x, int64_t Tn, int64_t ldx, T *out,
+                              int64_t ldo, int flags) {
+    wagg_apply_desc d = base(plan_kind, WAGG_SRC_HOST_MULTI, plans, x, Tn, ldx, out, ldo);
+    d.devices = devices; d.n_plans = n_devices; d.flags = flags;
+    return d;
+}
+template <typename T>
+wagg_apply_desc on_shards(int plan_kind, wagg_shard_group *g, const void *plans, const T *const *xs, const int64_t *rows, int64_t ldx, T *out,
+                          int64_t ldo, int root) {
+    wagg_apply_desc d = base(plan_kind, WAGG_SRC_SHARDED, plans, xs, 0, ldx, out, ldo);
+    d.group = g; d.rows = rows; d.root = root;
+    return d;
+}
+wagg_apply_desc poly(wagg_apply_desc d, double offset, int pow_first, int n_pow, int64_t pstride) {
     d.transform = WAGG_XF_POLY; d.offset = offset; d.pow_first = pow_first; d.n_pow = n_pow; d.out_pstride = pstride;
     return d;
 }
-wagg_apply_desc &edd(wagg_apply_desc &d, const void *tasmax, double offset, const double *thr, int n_thr, int64_t pstride) {
+wagg_apply_desc edd(wagg_apply_desc d, const void *tasmax, double offset, const double *thr, int n_thr, int64_t pstride) {
     d.transform = WAGG_XF_EDD; d.x2 = tasmax; d.offset = offset; d.thresholds = thr; d.n_thr = n_thr; d.out_pstride = pstride;
     return d;
 }
-wagg_apply_desc &lay(wagg_apply_desc &d, int layout, int out_layout) { d.layout = layout; d.out_layout = out_layout; return d; }
+wagg_apply_desc lay(wagg_apply_desc d, int layout, int out_layout) { d.layout = layout; d.out_layout = out_layout; return d; }
+int run(const wagg_apply_desc &d) { return wagg_apply(&d); }
 
 }  // namespace
 }  // namespace wagg
@@ -207,36 +212,29 @@ extern "C" int wagg_apply(const wagg_apply_desc *desc) {
     return d.elem == WAGG_T_F32 ? run_dense<float>(d) : run_dense<double>(d);
 }
 
-// ---- the exported apply symbols of rounds 1-5: fill a descriptor, call wagg_apply ----------------------------------------
+// ---- the exported apply symbols: each fills a descriptor and calls wagg_apply ---------------------------------------------
+// Every symbol of include/wagg.h is written out under its name; the _f32 / _f64 twins have the same one-line body, and the
+// builder they call takes the element code from the type of the data pointer.
 #define SEG WAGG_PLAN_SEGMENT
 #define DEN WAGG_PLAN_DENSE
-#define F32 WAGG_T_F32
-#define F64 WAGG_T_F64
-using wagg::base; using wagg::edd; using wagg::lay; using wagg::poly;
+using wagg::edd; using wagg::lay; using wagg::on_device; using wagg::on_host; using wagg::on_host_multi; using wagg::on_shards; using wagg::poly;
+using wagg::run;
 
 extern "C" int wagg_apply_f32(const wagg_plan *plan, const float *X_dev, int64_t T, int64_t ldx, int layout, float *out_dev, int64_t ldo,
                               int out_layout, void *stream) {
-    wagg_apply_desc d = base(SEG, F32, WAGG_SRC_DEVICE, plan, X_dev, T, ldx, out_dev, ldo);
-    d.stream = stream;
-    return wagg_apply(&lay(d, layout, out_layout));
+    return run(lay(on_device(SEG, plan, X_dev, T, ldx, out_dev, ldo, stream), layout, out_layout));
 }
 extern "C" int wagg_apply_f64(const wagg_plan *plan, const double *X_dev, int64_t T, int64_t ldx, int layout, double *out_dev, int64_t ldo,
                               int out_layout, void *stream) {
-    wagg_apply_desc d = base(SEG, F64, WAGG_SRC_DEVICE, plan, X_dev, T, ldx, out_dev, ldo);
-    d.stream = stream;
-    return wagg_apply(&lay(d, layout, out_layout));
+    return run(lay(on_device(SEG, plan, X_dev, T, ldx, out_dev, ldo, stream), layout, out_layout));
 }
 extern "C" int wagg_apply_host_ex_f32(const wagg_plan *plan, const float *X_host, int64_t T, int64_t ldx, int layout, float *out_host,
                                       int64_t ldo, int out_layout, int flags) {
-    wagg_apply_desc d = base(SEG, F32, WAGG_SRC_HOST, plan, X_host, T, ldx, out_host, ldo);
-    d.flags = flags;
-    return wagg_apply(&lay(d, layout, out_layout));
+    return run(lay(on_host(SEG, plan, X_host, T, ldx, out_host, ldo, flags), layout, out_layout));
 }
 extern "C" int wagg_apply_host_ex_f64(const wagg_plan *plan, const double *X_host, int64_t T, int64_t ldx, int layout, double *out_host,
                                       int64_t ldo, int out_layout, int flags) {
-    wagg_apply_desc d = base(SEG, F64, WAGG_SRC_HOST, plan, X_host, T, ldx, out_host, ldo);
-    d.flags = flags;
-    return wagg_apply(&lay(d, layout, out_layout));
+    return run(lay(on_host(SEG, plan, X_host, T, ldx, out_host, ldo, flags), layout, out_layout));
 }
 extern "C" int wagg_apply_host_f32(const wagg_plan *plan, const float *X_host, int64_t T, int64_t ldx, int layout, float *out_host,
                                    int64_t ldo, int out_layout) {
@@ -248,151 +246,101 @@ extern "C" int wagg_apply_host_f64(const wagg_plan *plan, const double *X_host, 
 }
 extern "C" int wagg_apply_host_multi_f32(const wagg_plan *const *plans, const int *devices, int n_devices, const float *X_host, int64_t T,
                                          int64_t ldx, float *out_host, int64_t ldo, int flags) {
-    wagg_apply_desc d = base(SEG, F32, WAGG_SRC_HOST_MULTI, plans, X_host, T, ldx, out_host, ldo);
-    d.devices = devices; d.n_plans = n_devices; d.flags = flags;
-    return wagg_apply(&d);
+    return run(on_host_multi(SEG, plans, devices, n_devices, X_host, T, ldx, out_host, ldo, flags));
 }
 extern "C" int wagg_apply_host_multi_f64(const wagg_plan *const *plans, const int *devices, int n_devices, const double *X_host, int64_t T,
                                          int64_t ldx, double *out_host, int64_t ldo, int flags) {
-    wagg_apply_desc d = base(SEG, F64, WAGG_SRC_HOST_MULTI, plans, X_host, T, ldx, out_host, ldo);
-    d.devices = devices; d.n_plans = n_devices; d.flags = flags;
-    return wagg_apply(&d);
+    return run(on_host_multi(SEG, plans, devices, n_devices, X_host, T, ldx, out_host, ldo, flags));
 }
 extern "C" int wagg_apply_poly_f32(const wagg_plan *plan, const float *X_dev, int64_t T, int64_t ldx, int layout, double offset, int pow_first,
                                    int n_pow, float *out_dev, int64_t ldo, int64_t out_pstride, int out_layout, void *stream) {
-    wagg_apply_desc d = base(SEG, F32, WAGG_SRC_DEVICE, plan, X_dev, T, ldx, out_dev, ldo);
-    d.stream = stream;
-    return wagg_apply(&lay(poly(d, offset, pow_first, n_pow, out_pstride), layout, out_layout));
+    return run(lay(poly(on_device(SEG, plan, X_dev, T, ldx, out_dev, ldo, stream), offset, pow_first, n_pow, out_pstride), layout, out_layout));
 }
 extern "C" int wagg_apply_poly_f64(const wagg_plan *plan, const double *X_dev, int64_t T, int64_t ldx, int layout, double offset, int pow_first,
                                    int n_pow, double *out_dev, int64_t ldo, int64_t out_pstride, int out_layout, void *stream) {
-    wagg_apply_desc d = base(SEG, F64, WAGG_SRC_DEVICE, plan, X_dev, T, ldx, out_dev, ldo);
-    d.stream = stream;
-    return wagg_apply(&lay(poly(d, offset, pow_first, n_pow, out_pstride), layout, out_layout));
+    return run(lay(poly(on_device(SEG, plan, X_dev, T, ldx, out_dev, ldo, stream), offset, pow_first, n_pow, out_pstride), layout, out_layout));
 }
 extern "C" int wagg_apply_poly_host_f32(const wagg_plan *plan, const float *X_host, int64_t T, int64_t ldx, double offset, int pow_first, int n_pow,
                                         float *out_host, int64_t ldo, int64_t out_pstride, int flags) {
-    wagg_apply_desc d = base(SEG, F32, WAGG_SRC_HOST, plan, X_host, T, ldx, out_host, ldo);
-    d.flags = flags;
-    return wagg_apply(&poly(d, offset, pow_first, n_pow, out_pstride));
+    return run(poly(on_host(SEG, plan, X_host, T, ldx, out_host, ldo, flags), offset, pow_first, n_pow, out_pstride));
 }
 extern "C" int wagg_apply_poly_host_f64(const wagg_plan *plan, const double *X_host, int64_t T, int64_t ldx, double offset, int pow_first, int n_pow,
                                         double *out_host, int64_t ldo, int64_t out_pstride, int flags) {
-    wagg_apply_desc d = base(SEG, F64, WAGG_SRC_HOST, plan, X_host, T, ldx, out_host, ldo);
-    d.flags = flags;
-    return wagg_apply(&poly(d, offset, pow_first, n_pow, out_pstride));
+    return run(poly(on_host(SEG, plan, X_host, T, ldx, out_host, ldo, flags), offset, pow_first, n_pow, out_pstride));
 }
 extern "C" int wagg_apply_edd_f32(const wagg_plan *plan, const float *tasmin_dev, const float *tasmax_dev, int64_t T, int64_t ldx, int layout,
                                   double offset, const double *thresholds, int n_thr, float *out_dev, int64_t ldo, int64_t out_pstride,
                                   int out_layout, void *stream) {
-    wagg_apply_desc d = base(SEG, F32, WAGG_SRC_DEVICE, plan, tasmin_dev, T, ldx, out_dev, ldo);
-    d.stream = stream;
-    return wagg_apply(&lay(edd(d, tasmax_dev, offset, thresholds, n_thr, out_pstride), layout, out_layout));
+    return run(lay(edd(on_device(SEG, plan, tasmin_dev, T, ldx, out_dev, ldo, stream), tasmax_dev, offset, thresholds, n_thr, out_pstride), layout, out_layout));
 }
 extern "C" int wagg_apply_edd_f64(const wagg_plan *plan, const double *tasmin_dev, const double *tasmax_dev, int64_t T, int64_t ldx, int layout,
                                   double offset, const double *thresholds, int n_thr, double *out_dev, int64_t ldo, int64_t out_pstride,
                                   int out_layout, void *stream) {
-    wagg_apply_desc d = base(SEG, F64, WAGG_SRC_DEVICE, plan, tasmin_dev, T, ldx, out_dev, ldo);
-    d.stream = stream;
-    return wagg_apply(&lay(edd(d, tasmax_dev, offset, thresholds, n_thr, out_pstride), layout, out_layout));
+    return run(lay(edd(on_device(SEG, plan, tasmin_dev, T, ldx, out_dev, ldo, stream), tasmax_dev, offset, thresholds, n_thr, out_pstride), layout, out_layout));
 }
 extern "C" int wagg_apply_edd_host_f32(const wagg_plan *plan, const float *tasmin_host, const float *tasmax_host, int64_t T, int64_t ldx, double offset,
                                        const double *thresholds, int n_thr, float *out_host, int64_t ldo, int64_t out_pstride, int flags) {
-    wagg_apply_desc d = base(SEG, F32, WAGG_SRC_HOST, plan, tasmin_host, T, ldx, out_host, ldo);
-    d.flags = flags;
-    return wagg_apply(&edd(d, tasmax_host, offset, thresholds, n_thr, out_pstride));
+    return run(edd(on_host(SEG, plan, tasmin_host, T, ldx, out_host, ldo, flags), tasmax_host, offset, thresholds, n_thr, out_pstride));
 }
 extern "C" int wagg_apply_edd_host_f64(const wagg_plan *plan, const double *tasmin_host, const double *tasmax_host, int64_t T, int64_t ldx, double offset,
                                        const double *thresholds, int n_thr, double *out_host, int64_t ldo, int64_t out_pstride, int flags) {
-    wagg_apply_desc d = base(SEG, F64, WAGG_SRC_HOST, plan, tasmin_host, T, ldx, out_host, ldo);
-    d.flags = flags;
-    return wagg_apply(&edd(d, tasmax_host, offset, thresholds, n_thr, out_pstride));
+    return run(edd(on_host(SEG, plan, tasmin_host, T, ldx, out_host, ldo, flags), tasmax_host, offset, thresholds, n_thr, out_pstride));
 }
 extern "C" int wagg_apply_sharded_f32(wagg_shard_group *g, const wagg_plan *const *plans, const float *const *X_dev, const int64_t *rows, int64_t ldx,
                                       float *out_root, int64_t ldo, int root) {
-    wagg_apply_desc d = base(SEG, F32, WAGG_SRC_SHARDED, plans, X_dev, 0, ldx, out_root, ldo);
-    d.group = g; d.rows = rows; d.root = root;
-    return wagg_apply(&d);
+    return run(on_shards(SEG, g, plans, X_dev, rows, ldx, out_root, ldo, root));
 }
 extern "C" int wagg_apply_sharded_f64(wagg_shard_group *g, const wagg_plan *const *plans, const double *const *X_dev, const int64_t *rows, int64_t ldx,
                                       double *out_root, int64_t ldo, int root) {
-    wagg_apply_desc d = base(SEG, F64, WAGG_SRC_SHARDED, plans, X_dev, 0, ldx, out_root, ldo);
-    d.group = g; d.rows = rows; d.root = root;
-    return wagg_apply(&d);
+    return run(on_shards(SEG, g, plans, X_dev, rows, ldx, out_root, ldo, root));
 }
 
 extern "C" int wagg_dense_apply_f32(wagg_dense *p, const float *X_dev, int64_t T, int64_t ldx, float *out_dev, int64_t ldo, int ksplit, void *stream) {
-    wagg_apply_desc d = base(DEN, F32, WAGG_SRC_DEVICE, p, X_dev, T, ldx, out_dev, ldo);
-    d.ksplit = ksplit; d.stream = stream;
-    return wagg_apply(&d);
+    return run(on_device(DEN, p, X_dev, T, ldx, out_dev, ldo, stream, ksplit));
 }
 extern "C" int wagg_dense_apply_f64(wagg_dense *p, const double *X_dev, int64_t T, int64_t ldx, double *out_dev, int64_t ldo, int ksplit, void *stream) {
-    wagg_apply_desc d = base(DEN, F64, WAGG_SRC_DEVICE, p, X_dev, T, ldx, out_dev, ldo);
-    d.ksplit = ksplit; d.stream = stream;
-    return wagg_apply(&d);
+    return run(on_device(DEN, p, X_dev, T, ldx, out_dev, ldo, stream, ksplit));
 }
 extern "C" int wagg_dense_apply_poly_f32(wagg_dense *p, const float *X_dev, int64_t T, int64_t ldx, double offset, int power, float *out_dev, int64_t ldo,
                                          int ksplit, void *stream) {
-    wagg_apply_desc d = base(DEN, F32, WAGG_SRC_DEVICE, p, X_dev, T, ldx, out_dev, ldo);
-    d.ksplit = ksplit; d.stream = stream;
-    return wagg_apply(&poly(d, offset, power, 1, 0));
+    return run(poly(on_device(DEN, p, X_dev, T, ldx, out_dev, ldo, stream, ksplit), offset, power, 1, 0));
 }
 extern "C" int wagg_dense_apply_poly_f64(wagg_dense *p, const double *X_dev, int64_t T, int64_t ldx, double offset, int power, double *out_dev, int64_t ldo,
                                          int ksplit, void *stream) {
-    wagg_apply_desc d = base(DEN, F64, WAGG_SRC_DEVICE, p, X_dev, T, ldx, out_dev, ldo);
-    d.ksplit = ksplit; d.stream = stream;
-    return wagg_apply(&poly(d, offset, power, 1, 0));
+    return run(poly(on_device(DEN, p, X_dev, T, ldx, out_dev, ldo, stream, ksplit), offset, power, 1, 0));
 }
 extern "C" int wagg_dense_apply_edd_f32(wagg_dense *p, const float *tasmin_dev, const float *tasmax_dev, int64_t T, int64_t ldx, double offset,
                                         double threshold, float *out_dev, int64_t ldo, int ksplit, void *stream) {
-    wagg_apply_desc d = base(DEN, F32, WAGG_SRC_DEVICE, p, tasmin_dev, T, ldx, out_dev, ldo);
-    d.ksplit = ksplit; d.stream = stream;
-    return wagg_apply(&edd(d, tasmax_dev, offset, &threshold, 1, 0));
+    return run(edd(on_device(DEN, p, tasmin_dev, T, ldx, out_dev, ldo, stream, ksplit), tasmax_dev, offset, &threshold, 1, 0));
 }
 extern "C" int wagg_dense_apply_edd_f64(wagg_dense *p, const double *tasmin_dev, const double *tasmax_dev, int64_t T, int64_t ldx, double offset,
                                         double threshold, double *out_dev, int64_t ldo, int ksplit, void *stream) {
-    wagg_apply_desc d = base(DEN, F64, WAGG_SRC_DEVICE, p, tasmin_dev, T, ldx, out_dev, ldo);
-    d.ksplit = ksplit; d.stream = stream;
-    return wagg_apply(&edd(d, tasmax_dev, offset, &threshold, 1, 0));
+    return run(edd(on_device(DEN, p, tasmin_dev, T, ldx, out_dev, ldo, stream, ksplit), tasmax_dev, offset, &threshold, 1, 0));
 }
 extern "C" int wagg_dense_apply_host_f32(wagg_dense *p, const float *X_host, int64_t T, int64_t ldx, float *out_host, int64_t ldo, int flags) {
-    wagg_apply_desc d = base(DEN, F32, WAGG_SRC_HOST, p, X_host, T, ldx, out_host, ldo);
-    d.flags = flags;
-    return wagg_apply(&d);
+    return run(on_host(DEN, p, X_host, T, ldx, out_host, ldo, flags));
 }
 extern "C" int wagg_dense_apply_host_f64(wagg_dense *p, const double *X_host, int64_t T, int64_t ldx, double *out_host, int64_t ldo, int flags) {
-    wagg_apply_desc d = base(DEN, F64, WAGG_SRC_HOST, p, X_host, T, ldx, out_host, ldo);
-    d.flags = flags;
-    return wagg_apply(&d);
+    return run(on_host(DEN, p, X_host, T, ldx, out_host, ldo, flags));
 }
 extern "C" int wagg_dense_apply_host_multi_f32(wagg_dense *const *plans, const int *devices, int n_devices, const float *X_host, int64_t T, int64_t ldx,
                                                float *out_host, int64_t ldo, int flags) {
-    wagg_apply_desc d = base(DEN, F32, WAGG_SRC_HOST_MULTI, plans, X_host, T, ldx, out_host, ldo);
-    d.devices = devices; d.n_plans = n_devices; d.flags = flags;
-    return wagg_apply(&d);
+    return run(on_host_multi(DEN, plans, devices, n_devices, X_host, T, ldx, out_host, ldo, flags));
 }
 extern "C" int wagg_dense_apply_host_multi_f64(wagg_dense *const *plans, const int *devices, int n_devices, const double *X_host, int64_t T, int64_t ldx,
                                                double *out_host, int64_t ldo, int flags) {
-    wagg_apply_desc d = base(DEN, F64, WAGG_SRC_HOST_MULTI, plans, X_host, T, ldx, out_host, ldo);
-    d.devices = devices; d.n_plans = n_devices; d.flags = flags;
-    return wagg_apply(&d);
+    return run(on_host_multi(DEN, plans, devices, n_devices, X_host, T, ldx, out_host, ldo, flags));
 }
 extern "C" int wagg_dense_apply_sharded_f32(wagg_shard_group *g, wagg_dense *const *plans, const float *const *X_dev, const int64_t *rows, int64_t ldx,
                                             float *out_root, int64_t ldo, int root) {
-    wagg_apply_desc d = base(DEN, F32, WAGG_SRC_SHARDED, plans, X_dev, 0, ldx, out_root, ldo);
-    d.group = g; d.rows = rows; d.root = root;
-    return wagg_apply(&d);
+    return run(on_shards(DEN, g, plans, X_dev, rows, ldx, out_root, ldo, root));
 }
 extern "C" int wagg_dense_apply_sharded_f64(wagg_shard_group *g, wagg_dense *const *plans, const double *const *X_dev, const int64_t *rows, int64_t ldx,
                                             double *out_root, int64_t ldo, int root) {
-    wagg_apply_desc d = base(DEN, F64, WAGG_SRC_SHARDED, plans, X_dev, 0, ldx, out_root, ldo);
-    d.group = g; d.rows = rows; d.root = root;
-    return wagg_apply(&d);
+    return run(on_shards(DEN, g, plans, X_dev, rows, ldx, out_root, ldo, root));
 }
 #undef SEG
 #undef DEN
-#undef F32
-#undef F64
 
 // ---- the structs that cross the boundary by layout: their sizes here, and a pattern that shows their field order ----------
 namespace wagg {

@@ -1,51 +1,35 @@
-// The apply entry points by their old C names, as plain C++ functions (namespace wagg::entry): what wagg_apply()
-// (wagg_desc.hip) dispatches a descriptor to, and what code INSIDE the library calls when it needs an apply (the host
-// pipelines hand them on as per-block launchers, the shard group calls them per shard).  The exported wagg_*apply* symbols of
-// include/wagg.h are wrappers in wagg_desc.hip that fill a wagg_apply_desc and call wagg_apply(); argument meaning: wagg.h.
+// The typed apply layer (namespace wagg::entry): one function template per apply, on the element type T (float or double).
+// It is what wagg_apply() (wagg_desc.hip) dispatches a descriptor to -- run_segment<T> / run_dense<T> call entry::x<T> -- and
+// what code INSIDE the library calls when it needs an apply (the host pipelines launch entry::apply<T> per block, the shard
+// group per shard).  Each template is defined in the translation unit of its plan kind (wagg_sparse.hip, wagg_dense.hip,
+// wagg_shard.hip) and instantiated there for float and double; the `dense_` prefix marks the dense-family plan kind.
+// The exported wagg_*apply*_f32/_f64 symbols of include/wagg.h are wrappers in wagg_desc.hip that fill a wagg_apply_desc and
+// call wagg_apply(); argument meaning: wagg.h.
 #pragma once
 #include "../../include/wagg.h"
 
 namespace wagg {
 namespace entry {
-int apply_f32(const wagg_plan *plan, const float *X_dev, int64_t T, int64_t ldx, int layout, float *out_dev, int64_t ldo, int out_layout, void *stream);
-int apply_f64(const wagg_plan *plan, const double *X_dev, int64_t T, int64_t ldx, int layout, double *out_dev, int64_t ldo, int out_layout, void *stream);
+template <typename T> int apply(const wagg_plan *plan, const T *X_dev, int64_t Tn, int64_t ldx, int layout, T *out_dev, int64_t ldo, int out_layout, void *stream);
 // WAGG_APPLY_COMPACT_ROWS: X_dev holds packed rows (wagg_pack.hip), ldx >= Gq
-int apply_compact_f32(const wagg_plan *plan, const float *X_dev, int64_t T, int64_t ldx, float *out_dev, int64_t ldo, void *stream);
-int apply_compact_f64(const wagg_plan *plan, const double *X_dev, int64_t T, int64_t ldx, double *out_dev, int64_t ldo, void *stream);
-int apply_host_f32(const wagg_plan *plan, const float *X_host, int64_t T, int64_t ldx, int layout, float *out_host, int64_t ldo, int out_layout);
-int apply_host_f64(const wagg_plan *plan, const double *X_host, int64_t T, int64_t ldx, int layout, double *out_host, int64_t ldo, int out_layout);
-int apply_host_ex_f32(const wagg_plan *plan, const float *X_host, int64_t T, int64_t ldx, int layout, float *out_host, int64_t ldo, int out_layout, int flags);
-int apply_host_ex_f64(const wagg_plan *plan, const double *X_host, int64_t T, int64_t ldx, int layout, double *out_host, int64_t ldo, int out_layout, int flags);
-int apply_host_multi_f32(const wagg_plan *const *plans, const int *devices, int n_devices, const float *X_host, int64_t T, int64_t ldx, float *out_host, int64_t ldo, int flags);
-int apply_host_multi_f64(const wagg_plan *const *plans, const int *devices, int n_devices, const double *X_host, int64_t T, int64_t ldx, double *out_host, int64_t ldo, int flags);
-int apply_poly_f32(const wagg_plan *plan, const float *X_dev, int64_t T, int64_t ldx, int layout, double offset, int pow_first, int n_pow, float *out_dev, int64_t ldo, int64_t out_pstride, int out_layout, void *stream);
-int apply_poly_f64(const wagg_plan *plan, const double *X_dev, int64_t T, int64_t ldx, int layout, double offset, int pow_first, int n_pow, double *out_dev, int64_t ldo, int64_t out_pstride, int out_layout, void *stream);
-int apply_poly_host_f32(const wagg_plan *plan, const float *X_host, int64_t T, int64_t ldx, double offset, int pow_first, int n_pow, float *out_host, int64_t ldo, int64_t out_pstride, int flags);
-int apply_poly_host_f64(const wagg_plan *plan, const double *X_host, int64_t T, int64_t ldx, double offset, int pow_first, int n_pow, double *out_host, int64_t ldo, int64_t out_pstride, int flags);
-int apply_edd_f32(const wagg_plan *plan, const float *tasmin_dev, const float *tasmax_dev, int64_t T, int64_t ldx, int layout, double offset, const double *thresholds, int n_thr, float *out_dev, int64_t ldo, int64_t out_pstride, int out_layout, void *stream);
-int apply_edd_f64(const wagg_plan *plan, const double *tasmin_dev, const double *tasmax_dev, int64_t T, int64_t ldx, int layout, double offset, const double *thresholds, int n_thr, double *out_dev, int64_t ldo, int64_t out_pstride, int out_layout, void *stream);
-int apply_edd_host_f32(const wagg_plan *plan, const float *tasmin_host, const float *tasmax_host, int64_t T, int64_t ldx, double offset, const double *thresholds, int n_thr, float *out_host, int64_t ldo, int64_t out_pstride, int flags);
-int apply_edd_host_f64(const wagg_plan *plan, const double *tasmin_host, const double *tasmax_host, int64_t T, int64_t ldx, double offset, const double *thresholds, int n_thr, double *out_host, int64_t ldo, int64_t out_pstride, int flags);
-int apply_sharded_f32(wagg_shard_group *g, const wagg_plan *const *plans, const float *const *X_dev, const int64_t *rows, int64_t ldx, float *out_root, int64_t ldo, int root);
-int apply_sharded_f64(wagg_shard_group *g, const wagg_plan *const *plans, const double *const *X_dev, const int64_t *rows, int64_t ldx, double *out_root, int64_t ldo, int root);
-// (fp32 dense applies: exact = WAGG_APPLY_EXACT_F32, today's fp32-pipe kernel instead of the split form)
-int dense_apply_f32(wagg_dense *d, const float *X_dev, int64_t T, int64_t ldx, float *out_dev, int64_t ldo, int ksplit, void *stream, bool exact = false);
-int dense_apply_f64(wagg_dense *d, const double *X_dev, int64_t T, int64_t ldx, double *out_dev, int64_t ldo, int ksplit, void *stream);
-int dense_apply_poly_f32(wagg_dense *d, const float *X_dev, int64_t T, int64_t ldx, double offset, int power, float *out_dev, int64_t ldo, int ksplit, void *stream, bool exact = false);
-int dense_apply_poly_f64(wagg_dense *d, const double *X_dev, int64_t T, int64_t ldx, double offset, int power, double *out_dev, int64_t ldo, int ksplit, void *stream);
-int dense_apply_edd_f32(wagg_dense *d, const float *tasmin_dev, const float *tasmax_dev, int64_t T, int64_t ldx, double offset, double threshold, float *out_dev, int64_t ldo, int ksplit, void *stream, bool exact = false);
-int dense_apply_edd_f64(wagg_dense *d, const double *tasmin_dev, const double *tasmax_dev, int64_t T, int64_t ldx, double offset, double threshold, double *out_dev, int64_t ldo, int ksplit, void *stream);
-int dense_apply_host_f32(wagg_dense *d, const float *X_host, int64_t T, int64_t ldx, float *out_host, int64_t ldo, int flags, bool exact = false);
-int dense_apply_host_f64(wagg_dense *d, const double *X_host, int64_t T, int64_t ldx, double *out_host, int64_t ldo, int flags);
-int dense_apply_host_multi_f32(wagg_dense *const *plans, const int *devices, int n_devices, const float *X_host, int64_t T, int64_t ldx, float *out_host, int64_t ldo, int flags);
-int dense_apply_host_multi_f64(wagg_dense *const *plans, const int *devices, int n_devices, const double *X_host, int64_t T, int64_t ldx, double *out_host, int64_t ldo, int flags);
-int dense_apply_sharded_f32(wagg_shard_group *g, wagg_dense *const *plans, const float *const *X_dev, const int64_t *rows, int64_t ldx, float *out_root, int64_t ldo, int root);
-int dense_apply_sharded_f64(wagg_shard_group *g, wagg_dense *const *plans, const double *const *X_dev, const int64_t *rows, int64_t ldx, double *out_root, int64_t ldo, int root);
+template <typename T> int apply_compact(const wagg_plan *plan, const T *X_dev, int64_t Tn, int64_t ldx, T *out_dev, int64_t ldo, void *stream);
+template <typename T> int apply_host_ex(const wagg_plan *plan, const T *X_host, int64_t Tn, int64_t ldx, int layout, T *out_host, int64_t ldo, int out_layout, int flags);
+template <typename T> int apply_host_multi(const wagg_plan *const *plans, const int *devices, int n_devices, const T *X_host, int64_t Tn, int64_t ldx, T *out_host, int64_t ldo, int flags);
+template <typename T> int apply_poly(const wagg_plan *plan, const T *X_dev, int64_t Tn, int64_t ldx, int layout, double offset, int pow_first, int n_pow, T *out_dev, int64_t ldo, int64_t out_pstride, int out_layout, void *stream);
+template <typename T> int apply_poly_host(const wagg_plan *plan, const T *X_host, int64_t Tn, int64_t ldx, double offset, int pow_first, int n_pow, T *out_host, int64_t ldo, int64_t out_pstride, int flags);
+template <typename T> int apply_edd(const wagg_plan *plan, const T *tasmin_dev, const T *tasmax_dev, int64_t Tn, int64_t ldx, int layout, double offset, const double *thresholds, int n_thr, T *out_dev, int64_t ldo, int64_t out_pstride, int out_layout, void *stream);
+template <typename T> int apply_edd_host(const wagg_plan *plan, const T *tasmin_host, const T *tasmax_host, int64_t Tn, int64_t ldx, double offset, const double *thresholds, int n_thr, T *out_host, int64_t ldo, int64_t out_pstride, int flags);
+template <typename T> int apply_sharded(wagg_shard_group *g, const wagg_plan *const *plans, const T *const *X_dev, const int64_t *rows, int64_t ldx, T *out_root, int64_t ldo, int root);
+// (dense applies: exact = WAGG_APPLY_EXACT_F32, the fp32-pipe kernel instead of the split form; fp64 plans ignore it)
+template <typename T> int dense_apply(wagg_dense *d, const T *X_dev, int64_t Tn, int64_t ldx, T *out_dev, int64_t ldo, int ksplit, void *stream, bool exact = false);
+template <typename T> int dense_apply_poly(wagg_dense *d, const T *X_dev, int64_t Tn, int64_t ldx, double offset, int power, T *out_dev, int64_t ldo, int ksplit, void *stream, bool exact = false);
+template <typename T> int dense_apply_edd(wagg_dense *d, const T *tasmin_dev, const T *tasmax_dev, int64_t Tn, int64_t ldx, double offset, double threshold, T *out_dev, int64_t ldo, int ksplit, void *stream, bool exact = false);
+template <typename T> int dense_apply_host(wagg_dense *d, const T *X_host, int64_t Tn, int64_t ldx, T *out_host, int64_t ldo, int flags, bool exact = false);
+template <typename T> int dense_apply_host_multi(wagg_dense *const *plans, const int *devices, int n_devices, const T *X_host, int64_t Tn, int64_t ldx, T *out_host, int64_t ldo, int flags);
+template <typename T> int dense_apply_sharded(wagg_shard_group *g, wagg_dense *const *plans, const T *const *X_dev, const int64_t *rows, int64_t ldx, T *out_root, int64_t ldo, int root);
 // many-plans (wagg_plan_create_many): the concatenated result of every (level, weighting) plane, from one pass over X
-int apply_many_f32(const wagg_plan *plan, const float *X_dev, int64_t T, int64_t ldx, int layout, float *out_dev, int64_t ldo, int out_layout, void *stream);
-int apply_many_f64(const wagg_plan *plan, const double *X_dev, int64_t T, int64_t ldx, int layout, double *out_dev, int64_t ldo, int out_layout, void *stream);
-int apply_many_host_f32(const wagg_plan *plan, const float *X_host, int64_t T, int64_t ldx, int layout, float *out_host, int64_t ldo, int out_layout, int flags);
-int apply_many_host_f64(const wagg_plan *plan, const double *X_host, int64_t T, int64_t ldx, int layout, double *out_host, int64_t ldo, int out_layout, int flags);
+template <typename T> int apply_many(const wagg_plan *plan, const T *X_dev, int64_t Tn, int64_t ldx, int layout, T *out_dev, int64_t ldo, int out_layout, void *stream);
+template <typename T> int apply_many_host(const wagg_plan *plan, const T *X_host, int64_t Tn, int64_t ldx, int layout, T *out_host, int64_t ldo, int out_layout, int flags);
 bool is_many_plan(const wagg_plan *plan);
 }  // namespace entry
 }  // namespace wagg

@@ -283,9 +283,11 @@ static int apply_sharded(wagg_shard_group *g, const int *plan_devices, int32_t R
     return WAGG_OK;
 }
 
+// ---- the typed apply layer (wagg_entry.h) of the sharded source, one per plan kind.  (wagg::apply_sharded above is the
+// orchestration they share; it is named with its namespace because entry::apply_sharded hides it here)
 template <typename T>
-static int sparse_sharded(wagg_shard_group *g, const wagg_plan *const *plans, const T *const *X_dev, const int64_t *rows, int64_t ldx,
-                          T *out_root, int64_t ldo, int root) {
+int entry::apply_sharded(wagg_shard_group *g, const wagg_plan *const *plans, const T *const *X_dev, const int64_t *rows, int64_t ldx,
+                         T *out_root, int64_t ldo, int root) {
     WAGG_REQUIRE(g != nullptr && plans != nullptr, "NULL argument");
     std::vector<int> devs((size_t)g->n);
     for (int i = 0; i < g->n; ++i) {
@@ -294,16 +296,15 @@ static int sparse_sharded(wagg_shard_group *g, const wagg_plan *const *plans, co
         devs[(size_t)i] = plans[i]->device;
     }
     WAGG_REQUIRE(ldx >= plans[0]->info.G, "ldx too small");
-    return apply_sharded<T>(g, devs.data(), plans[0]->info.R, X_dev, rows, out_root, ldo, root,
-                            [&](int i, const T *x, int64_t r, T *o, int64_t ld, hipStream_t st) {
-                                if constexpr (sizeof(T) == 4) return entry::apply_f32(plans[i], x, r, ldx, WAGG_LAYOUT_TG, o, ld, WAGG_OUT_TR, st);
-                                else return entry::apply_f64(plans[i], x, r, ldx, WAGG_LAYOUT_TG, o, ld, WAGG_OUT_TR, st);
-                            });
+    return wagg::apply_sharded<T>(g, devs.data(), plans[0]->info.R, X_dev, rows, out_root, ldo, root,
+                                  [&](int i, const T *x, int64_t r, T *o, int64_t ld, hipStream_t st) {
+                                      return entry::apply<T>(plans[i], x, r, ldx, WAGG_LAYOUT_TG, o, ld, WAGG_OUT_TR, st);
+                                  });
 }
 
 template <typename T>
-static int dense_sharded(wagg_shard_group *g, wagg_dense *const *plans, const T *const *X_dev, const int64_t *rows, int64_t ldx, T *out_root,
-                         int64_t ldo, int root) {
+int entry::dense_apply_sharded(wagg_shard_group *g, wagg_dense *const *plans, const T *const *X_dev, const int64_t *rows, int64_t ldx,
+                               T *out_root, int64_t ldo, int root) {
     WAGG_REQUIRE(g != nullptr && plans != nullptr, "NULL argument");
     std::vector<int> devs((size_t)g->n);
     for (int i = 0; i < g->n; ++i) {
@@ -313,28 +314,18 @@ static int dense_sharded(wagg_shard_group *g, wagg_dense *const *plans, const T 
         devs[(size_t)i] = plans[i]->device;
     }
     WAGG_REQUIRE(ldx >= plans[0]->G, "ldx too small");
-    return apply_sharded<T>(g, devs.data(), plans[0]->R, X_dev, rows, out_root, ldo, root,
-                            [&](int i, const T *x, int64_t r, T *o, int64_t ld, hipStream_t st) {
-                                if constexpr (sizeof(T) == 4) return entry::dense_apply_f32(plans[i], x, r, ldx, o, ld, 0, st);
-                                else return entry::dense_apply_f64(plans[i], x, r, ldx, o, ld, 0, st);
-                            });
+    return wagg::apply_sharded<T>(g, devs.data(), plans[0]->R, X_dev, rows, out_root, ldo, root,
+                                  [&](int i, const T *x, int64_t r, T *o, int64_t ld, hipStream_t st) {
+                                      return entry::dense_apply<T>(plans[i], x, r, ldx, o, ld, 0, st);
+                                  });
 }
 
+#define WAGG_ENTRY_SHARDED(T)                                                                                                            \
+    template int entry::apply_sharded<T>(wagg_shard_group *, const wagg_plan *const *, const T *const *, const int64_t *, int64_t, T *,   \
+                                         int64_t, int);                                                                                  \
+    template int entry::dense_apply_sharded<T>(wagg_shard_group *, wagg_dense *const *, const T *const *, const int64_t *, int64_t, T *, \
+                                               int64_t, int);
+WAGG_ENTRY_SHARDED(float)
+WAGG_ENTRY_SHARDED(double)
+#undef WAGG_ENTRY_SHARDED
 }  // namespace wagg
-
-int wagg::entry::apply_sharded_f32(wagg_shard_group *g, const wagg_plan *const *plans, const float *const *X_dev, const int64_t *rows,
-                                      int64_t ldx, float *out_root, int64_t ldo, int root) {
-    return wagg::sparse_sharded<float>(g, plans, X_dev, rows, ldx, out_root, ldo, root);
-}
-int wagg::entry::apply_sharded_f64(wagg_shard_group *g, const wagg_plan *const *plans, const double *const *X_dev, const int64_t *rows,
-                                      int64_t ldx, double *out_root, int64_t ldo, int root) {
-    return wagg::sparse_sharded<double>(g, plans, X_dev, rows, ldx, out_root, ldo, root);
-}
-int wagg::entry::dense_apply_sharded_f32(wagg_shard_group *g, wagg_dense *const *plans, const float *const *X_dev, const int64_t *rows,
-                                            int64_t ldx, float *out_root, int64_t ldo, int root) {
-    return wagg::dense_sharded<float>(g, plans, X_dev, rows, ldx, out_root, ldo, root);
-}
-int wagg::entry::dense_apply_sharded_f64(wagg_shard_group *g, wagg_dense *const *plans, const double *const *X_dev, const int64_t *rows,
-                                            int64_t ldx, double *out_root, int64_t ldo, int root) {
-    return wagg::dense_sharded<double>(g, plans, X_dev, rows, ldx, out_root, ldo, root);
-}

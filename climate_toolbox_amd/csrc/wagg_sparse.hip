@@ -1244,6 +1244,9 @@ template <typename T> static const LcvEntry<T> &lcv_pick(bool vec, bool edd, boo
     return table[vec ? 1 : 0][edd ? 1 : 0][gt ? 1 : 0][planes - 1];
 }
 
+// the timesteps of one tile of the segment-table kernels (their TB), by element type: what every apply launches with
+template <typename T> constexpr int SEG_TB = sizeof(T) == 4 ? 64 : 32;
+
 template <typename T, int TB>
 static int launch_sparse(const wagg_plan *plan, const T *X, int64_t Ttot, int64_t ldx, int layout,
                          T *out, int64_t ldo, int out_layout, hipStream_t stream, T xoff = T(0), int xpow = 0,
@@ -2295,27 +2298,20 @@ extern "C" int wagg_plan_get_den(const wagg_plan *plan, double *den_host) {
     return WAGG_OK;
 }
 
-int wagg::entry::apply_f32(const wagg_plan *plan, const float *X_dev, int64_t T, int64_t ldx,
-                              int layout, float *out_dev, int64_t ldo, int out_layout, void *stream) {
-    int rc = wagg::check_apply_args(plan, X_dev, T, ldx, layout, out_dev, ldo, out_layout);
-    if (rc != WAGG_OK) return rc;
-    return wagg::launch_sparse<float, 64>(plan, X_dev, T, ldx, layout, out_dev, ldo, out_layout,
-                                          (hipStream_t)stream);
-}
-
-int wagg::entry::apply_f64(const wagg_plan *plan, const double *X_dev, int64_t T, int64_t ldx,
-                              int layout, double *out_dev, int64_t ldo, int out_layout, void *stream) {
-    int rc = wagg::check_apply_args(plan, X_dev, T, ldx, layout, out_dev, ldo, out_layout);
-    if (rc != WAGG_OK) return rc;
-    return wagg::launch_sparse<double, 32>(plan, X_dev, T, ldx, layout, out_dev, ldo, out_layout,
-                                           (hipStream_t)stream);
-}
-
+// ---- the typed apply layer (wagg_entry.h): defined here as templates on the element type, instantiated at the end of the file
 namespace wagg {
+template <typename T>
+int entry::apply(const wagg_plan *plan, const T *X, int64_t Tn, int64_t ldx, int layout, T *out, int64_t ldo, int out_layout,
+                 void *stream) {
+    int rc = check_apply_args(plan, X, Tn, ldx, layout, out, ldo, out_layout);
+    if (rc != WAGG_OK) return rc;
+    return launch_sparse<T, SEG_TB<T>>(plan, X, Tn, ldx, layout, out, ldo, out_layout, (hipStream_t)stream);
+}
+
 // WAGG_APPLY_COMPACT_ROWS: device-resident PACKED rows (wagg_pack.hip; ldx >= Gq) through the kernel of the lines-only host
 // path -- what host_rows_pipeline below does with every block it has shipped
 template <typename T>
-static int apply_compact(const wagg_plan *plan, const T *X, int64_t Tn, int64_t ldx, T *out, int64_t ldo, hipStream_t st) {
+int entry::apply_compact(const wagg_plan *plan, const T *X, int64_t Tn, int64_t ldx, T *out, int64_t ldo, void *stream) {
     WAGG_REQUIRE(plan != nullptr, "plan is NULL");
     WAGG_REQUIRE(Tn >= 0, "T < 0");
     const SparsePlanDev &d = sizeof(T) == 4 ? plan->dl : plan->dl64;
@@ -2328,24 +2324,17 @@ static int apply_compact(const wagg_plan *plan, const T *X, int64_t Tn, int64_t 
     WAGG_REQUIRE(X != nullptr && out != nullptr, "X/out is NULL");
     WAGG_REQUIRE(ldx >= d.Gq, "ldx %lld too small for packed rows of %lld cells", (long long)ldx, (long long)d.Gq);
     WAGG_REQUIRE(ldo >= (int64_t)plan->info.R, "ldo %lld too small", (long long)ldo);
-    return launch_sparse<T, (sizeof(T) == 4 ? 64 : 32)>(plan, X, Tn, ldx, WAGG_LAYOUT_TG, out, ldo, WAGG_OUT_TR, st, T(0), 0, 1, 0, nullptr,
-                                                        nullptr, 0, COMPACT_QUADS);
-}
-}  // namespace wagg
-int wagg::entry::apply_compact_f32(const wagg_plan *plan, const float *X_dev, int64_t T, int64_t ldx, float *out_dev, int64_t ldo, void *stream) {
-    return wagg::apply_compact<float>(plan, X_dev, T, ldx, out_dev, ldo, (hipStream_t)stream);
-}
-int wagg::entry::apply_compact_f64(const wagg_plan *plan, const double *X_dev, int64_t T, int64_t ldx, double *out_dev, int64_t ldo, void *stream) {
-    return wagg::apply_compact<double>(plan, X_dev, T, ldx, out_dev, ldo, (hipStream_t)stream);
+    return launch_sparse<T, SEG_TB<T>>(plan, X, Tn, ldx, WAGG_LAYOUT_TG, out, ldo, WAGG_OUT_TR, (hipStream_t)stream, T(0), 0, 1, 0, nullptr,
+                                       nullptr, 0, COMPACT_QUADS);
 }
 
-namespace wagg {
 // (x + offset)^p for p = 1..n_pow, each aggregated like wagg_apply.  Power p lands at
 // out + (p - 1) * out_pstride.
-template <typename T, int TB>
-static int apply_poly(const wagg_plan *plan, const T *X, int64_t Tn, int64_t ldx, int layout, double offset,
-                      int pow_first, int n_pow, T *out, int64_t ldo, int64_t out_pstride, int out_layout,
-                      hipStream_t st) {
+template <typename T>
+int entry::apply_poly(const wagg_plan *plan, const T *X, int64_t Tn, int64_t ldx, int layout, double offset, int pow_first,
+                      int n_pow, T *out, int64_t ldo, int64_t out_pstride, int out_layout, void *stream) {
+    constexpr int TB = SEG_TB<T>;
+    const hipStream_t st = (hipStream_t)stream;
     int rc = check_apply_args(plan, X, Tn, ldx, layout, out, ldo, out_layout);
     if (rc != WAGG_OK) return rc;
     WAGG_REQUIRE(pow_first >= 1 && n_pow >= 1 && pow_first + n_pow - 1 <= 16,
@@ -2421,9 +2410,32 @@ static int host_rows_pipeline(const wagg_plan *plan, const T *X, int64_t Tn, int
     return stream_host_rows_any(a);
 }
 
-template <typename T, typename F>
-static int apply_host(const wagg_plan *plan, const T *X, int64_t Tn, int64_t ldx, int layout, T *out,
-                      int64_t ldo, int out_layout, int flags, F fn) {
+// The whole-field fallback of a host-resident field (WAGG_HOST_WHOLE, or a layout the row-block pipeline does not take): the
+// field goes into one scratch block, `launch(x_dev, out_dev)` queues the apply on the null stream into a zeroed result block,
+// the device is drained and the rows of the result come back.  timeout_check: ask the plan (check_timeout) between the drain
+// and the copy back.
+template <typename T, typename LaunchFn>
+static int host_whole_field(const wagg_plan *plan, const T *X, int64_t Tn, int64_t ldx, int layout, T *out, int64_t ldo, int out_layout,
+                            int flags, bool timeout_check, LaunchFn launch) {
+    const int64_t xrows = layout == WAGG_LAYOUT_TG ? Tn : plan->info.G;
+    const int64_t orows = out_layout == WAGG_OUT_TR ? Tn : plan->info.R;
+    ScratchBuf<T> dx, dout;                      // (call-lifetime blocks: from the pool, wagg_scratch.hip; the device is drained below)
+    WAGG_HIP(dx.alloc((size_t)(xrows * ldx)));
+    WAGG_HIP(dout.alloc((size_t)(orows * ldo)));
+    const int64_t xcols = layout == WAGG_LAYOUT_TG ? plan->info.G : Tn, ocols = out_layout == WAGG_OUT_TR ? plan->info.R : Tn;
+    const bool pin = (flags & WAGG_HOST_PIN) != 0;
+    if (int rc = copy_to_device(dx.p, X, sizeof(T) * (size_t)((xrows - 1) * ldx + xcols), pin)) return rc;
+    WAGG_HIP(hipMemset(dout.p, 0, sizeof(T) * (size_t)(orows * ldo)));
+    if (int rc = launch(dx.p, dout.p)) return rc;
+    WAGG_HIP(hipDeviceSynchronize());
+    if (timeout_check)
+        if (int rc = check_timeout(plan)) return rc;
+    return copy_rows_to_host(out, dout.p, orows, sizeof(T) * (size_t)ldo, sizeof(T) * (size_t)ocols, pin);
+}
+
+template <typename T>
+int entry::apply_host_ex(const wagg_plan *plan, const T *X, int64_t Tn, int64_t ldx, int layout, T *out, int64_t ldo, int out_layout,
+                         int flags) {
     clear_error();
     int rc = check_apply_args(plan, X, Tn, ldx, layout, out, ldo, out_layout);
     if (rc != WAGG_OK || Tn == 0) return rc;
@@ -2432,33 +2444,22 @@ static int apply_host(const wagg_plan *plan, const T *X, int64_t Tn, int64_t ldx
     if (layout == WAGG_LAYOUT_TG && out_layout == WAGG_OUT_TR && !(flags & WAGG_HOST_WHOLE)) {
         rc = host_rows_pipeline<T>(plan, X, Tn, ldx, out, ldo, flags, 1, 0,
                                    [&](const T *xd, int64_t rows, int64_t ldx_dev, T *od, hipStream_t st, int compact) {
-                                       if (!compact) return fn(plan, xd, rows, ldx_dev, WAGG_LAYOUT_TG, od, ldo, WAGG_OUT_TR, (void *)st);
-                                       return launch_sparse<T, (sizeof(T) == 4 ? 64 : 32)>(plan, xd, rows, ldx_dev, WAGG_LAYOUT_TG, od, ldo, WAGG_OUT_TR, st,
-                                                                                           T(0), 0, 1, 0, nullptr, nullptr, 0, compact);
+                                       if (!compact) return entry::apply<T>(plan, xd, rows, ldx_dev, WAGG_LAYOUT_TG, od, ldo, WAGG_OUT_TR, (void *)st);
+                                       return launch_sparse<T, SEG_TB<T>>(plan, xd, rows, ldx_dev, WAGG_LAYOUT_TG, od, ldo, WAGG_OUT_TR, st, T(0), 0, 1, 0,
+                                                                          nullptr, nullptr, 0, compact);
                                    });
         if (rc != WAGG_OK) return rc;
         return check_timeout(plan);
     }
-    const int64_t xrows = layout == WAGG_LAYOUT_TG ? Tn : plan->info.G;
-    const int64_t orows = out_layout == WAGG_OUT_TR ? Tn : plan->info.R;
-    ScratchBuf<T> dx, dout;                      // (call-lifetime blocks: from the pool, wagg_scratch.hip; the device is drained below)
-    WAGG_HIP(dx.alloc((size_t)(xrows * ldx)));
-    WAGG_HIP(dout.alloc((size_t)(orows * ldo)));
-    const int64_t xcols = layout == WAGG_LAYOUT_TG ? plan->info.G : Tn, ocols = out_layout == WAGG_OUT_TR ? plan->info.R : Tn;
-    const bool pin = (flags & WAGG_HOST_PIN) != 0;
-    if ((rc = copy_to_device(dx.p, X, sizeof(T) * (size_t)((xrows - 1) * ldx + xcols), pin)) != WAGG_OK) return rc;
-    WAGG_HIP(hipMemset(dout.p, 0, sizeof(T) * (size_t)(orows * ldo)));
-    rc = fn(plan, dx.p, Tn, ldx, layout, dout.p, ldo, out_layout, nullptr);
-    if (rc != WAGG_OK) return rc;
-    WAGG_HIP(hipDeviceSynchronize());
-    if (int rc2 = check_timeout(plan)) return rc2;
-    return copy_rows_to_host(out, dout.p, orows, sizeof(T) * (size_t)ldo, sizeof(T) * (size_t)ocols, pin);
+    return host_whole_field<T>(plan, X, Tn, ldx, layout, out, ldo, out_layout, flags, true, [&](const T *xd, T *od) {
+        return entry::apply<T>(plan, xd, Tn, ldx, layout, od, ldo, out_layout, nullptr);
+    });
 }
 
 // The fused powers of a host-resident field (wagg_apply_poly_host_*): the same pipeline, n_pow result planes per block.
 template <typename T>
-static int apply_poly_host(const wagg_plan *plan, const T *X, int64_t Tn, int64_t ldx, double offset, int pow_first, int n_pow,
-                           T *out, int64_t ldo, int64_t out_pstride, int flags) {
+int entry::apply_poly_host(const wagg_plan *plan, const T *X, int64_t Tn, int64_t ldx, double offset, int pow_first, int n_pow, T *out,
+                           int64_t ldo, int64_t out_pstride, int flags) {
     clear_error();
     int rc = check_apply_args(plan, X, Tn, ldx, WAGG_LAYOUT_TG, out, ldo, WAGG_OUT_TR);
     if (rc != WAGG_OK) return rc;
@@ -2468,7 +2469,7 @@ static int apply_poly_host(const wagg_plan *plan, const T *X, int64_t Tn, int64_
     WAGG_REQUIRE((flags & ~(WAGG_HOST_PIN | WAGG_HOST_LINES | WAGG_HOST_LINES_WHOLE)) == 0, "unknown host flags 0x%x", flags);
     if (Tn == 0) return WAGG_OK;
     if ((rc = check_plan_device(plan)) != WAGG_OK) return rc;
-    constexpr int TB = sizeof(T) == 4 ? 64 : 32;
+    constexpr int TB = SEG_TB<T>;
     rc = host_rows_pipeline<T>(plan, X, Tn, ldx, out, ldo, flags, n_pow, out_pstride,
                                [&](const T *xd, int64_t rows, int64_t ldx_dev, T *od, hipStream_t st, int compact) {
                                    int r2 = WAGG_OK;
@@ -2486,7 +2487,7 @@ static int apply_poly_host(const wagg_plan *plan, const T *X, int64_t Tn, int64_
 // n_thr result planes per block.  Lines only: the chunking the degree-day kernel reads (128-cell chunks of 16-cell lines for
 // fp32, the 64-cell chunks for fp64), one packed row = tasmin's lines then tasmax's.
 template <typename T>
-static int apply_edd_host(const wagg_plan *plan, const T *tmin, const T *tmax, int64_t Tn, int64_t ldx, double offset,
+int entry::apply_edd_host(const wagg_plan *plan, const T *tmin, const T *tmax, int64_t Tn, int64_t ldx, double offset,
                           const double *thr, int n_thr, T *out, int64_t ldo, int64_t out_pstride, int flags) {
     clear_error();
     int rc = check_apply_args(plan, tmin, Tn, ldx, WAGG_LAYOUT_TG, out, ldo, WAGG_OUT_TR);
@@ -2497,7 +2498,7 @@ static int apply_edd_host(const wagg_plan *plan, const T *tmin, const T *tmax, i
     WAGG_REQUIRE((flags & ~(WAGG_HOST_PIN | WAGG_HOST_LINES | WAGG_HOST_LINES_WHOLE)) == 0, "unknown host flags 0x%x", flags);
     if (Tn == 0) return WAGG_OK;
     if ((rc = check_plan_device(plan)) != WAGG_OK) return rc;
-    constexpr int TB = sizeof(T) == 4 ? 64 : 32;
+    constexpr int TB = SEG_TB<T>;
     const bool lcv_off = (plan->flags & (WAGG_PLAN_NO_LC | WAGG_PLAN_NO_STREAM | WAGG_PLAN_LC_MFMA)) != 0;
     const bool edd_lcv = (sizeof(T) == 4 ? plan->has_lines64 : plan->has_lines64e) && !lcv_off;
     const SparsePlanDev *dc = edd_lcv ? (sizeof(T) == 4 ? &plan->dl64 : &plan->dl64e) : nullptr;
@@ -2524,9 +2525,9 @@ static int apply_edd_host(const wagg_plan *plan, const T *tmin, const T *tmax, i
 // kernels / D2H pipeline on its own PCIe link from its own host thread, and every block's result lands directly in
 // the caller's rows -- no exchange between devices, no collective.  The same device may appear more than once (two
 // replicas on one GPU: how the path is exercised on a one-GPU box).
-template <typename T, typename F>
-static int apply_host_multi(const wagg_plan *const *plans, const int *devices, int n, const T *X, int64_t Tn, int64_t ldx,
-                            T *out, int64_t ldo, int flags, F fn) {
+template <typename T>
+int entry::apply_host_multi(const wagg_plan *const *plans, const int *devices, int n, const T *X, int64_t Tn, int64_t ldx, T *out,
+                            int64_t ldo, int flags) {
     clear_error();
     WAGG_REQUIRE(plans && devices && n >= 1 && n <= 64, "need 1..64 plan replicas and their devices");
     WAGG_REQUIRE((flags & ~WAGG_HOST_PIN) == 0, "unknown host flags 0x%x", flags);
@@ -2541,79 +2542,20 @@ static int apply_host_multi(const wagg_plan *const *plans, const int *devices, i
     if (Tn == 0) return WAGG_OK;
     int rc = stream_host_rows<T>(X, Tn, ldx, plans[0]->info.G, out, ldo, plans[0]->info.R, flags, 64, n, devices,
                                  [&](int s, const T *xd, int64_t rows, T *od, hipStream_t st) {
-                                     return fn(plans[s], xd, rows, ldx, WAGG_LAYOUT_TG, od, ldo, WAGG_OUT_TR, (void *)st);
+                                     return entry::apply<T>(plans[s], xd, rows, ldx, WAGG_LAYOUT_TG, od, ldo, WAGG_OUT_TR, (void *)st);
                                  },
                                  [&](int s, hipStream_t st) { plans[s]->drop_staging(st); });
     for (int s = 0; s < n && rc == WAGG_OK; ++s) rc = check_timeout(plans[s]);
     return rc;
 }
-}  // namespace wagg
 
-int wagg::entry::apply_host_f32(const wagg_plan *plan, const float *X_host, int64_t T, int64_t ldx,
-                                   int layout, float *out_host, int64_t ldo, int out_layout) {
-    return wagg::apply_host<float>(plan, X_host, T, ldx, layout, out_host, ldo, out_layout, WAGG_HOST_PIN | WAGG_HOST_LINES, entry::apply_f32);
-}
-int wagg::entry::apply_host_ex_f32(const wagg_plan *plan, const float *X_host, int64_t T, int64_t ldx,
-                                      int layout, float *out_host, int64_t ldo, int out_layout, int flags) {
-    return wagg::apply_host<float>(plan, X_host, T, ldx, layout, out_host, ldo, out_layout, flags, entry::apply_f32);
-}
-int wagg::entry::apply_host_f64(const wagg_plan *plan, const double *X_host, int64_t T, int64_t ldx,
-                                   int layout, double *out_host, int64_t ldo, int out_layout) {
-    return wagg::apply_host<double>(plan, X_host, T, ldx, layout, out_host, ldo, out_layout, WAGG_HOST_PIN | WAGG_HOST_LINES, entry::apply_f64);
-}
-int wagg::entry::apply_host_ex_f64(const wagg_plan *plan, const double *X_host, int64_t T, int64_t ldx,
-                                      int layout, double *out_host, int64_t ldo, int out_layout, int flags) {
-    return wagg::apply_host<double>(plan, X_host, T, ldx, layout, out_host, ldo, out_layout, flags, entry::apply_f64);
-}
-int wagg::entry::apply_host_multi_f32(const wagg_plan *const *plans, const int *devices, int n_devices, const float *X_host,
-                                         int64_t T, int64_t ldx, float *out_host, int64_t ldo, int flags) {
-    return wagg::apply_host_multi<float>(plans, devices, n_devices, X_host, T, ldx, out_host, ldo, flags, entry::apply_f32);
-}
-int wagg::entry::apply_host_multi_f64(const wagg_plan *const *plans, const int *devices, int n_devices, const double *X_host,
-                                         int64_t T, int64_t ldx, double *out_host, int64_t ldo, int flags) {
-    return wagg::apply_host_multi<double>(plans, devices, n_devices, X_host, T, ldx, out_host, ldo, flags, entry::apply_f64);
-}
-
-int wagg::entry::apply_poly_host_f32(const wagg_plan *plan, const float *X_host, int64_t T, int64_t ldx, double offset, int pow_first,
-                                        int n_pow, float *out_host, int64_t ldo, int64_t out_pstride, int flags) {
-    return wagg::apply_poly_host<float>(plan, X_host, T, ldx, offset, pow_first, n_pow, out_host, ldo, out_pstride, flags);
-}
-int wagg::entry::apply_poly_host_f64(const wagg_plan *plan, const double *X_host, int64_t T, int64_t ldx, double offset, int pow_first,
-                                        int n_pow, double *out_host, int64_t ldo, int64_t out_pstride, int flags) {
-    return wagg::apply_poly_host<double>(plan, X_host, T, ldx, offset, pow_first, n_pow, out_host, ldo, out_pstride, flags);
-}
-
-int wagg::entry::apply_edd_host_f32(const wagg_plan *plan, const float *tasmin_host, const float *tasmax_host, int64_t T, int64_t ldx,
-                                       double offset, const double *thresholds, int n_thr, float *out_host, int64_t ldo,
-                                       int64_t out_pstride, int flags) {
-    return wagg::apply_edd_host<float>(plan, tasmin_host, tasmax_host, T, ldx, offset, thresholds, n_thr, out_host, ldo, out_pstride, flags);
-}
-int wagg::entry::apply_edd_host_f64(const wagg_plan *plan, const double *tasmin_host, const double *tasmax_host, int64_t T, int64_t ldx,
-                                       double offset, const double *thresholds, int n_thr, double *out_host, int64_t ldo,
-                                       int64_t out_pstride, int flags) {
-    return wagg::apply_edd_host<double>(plan, tasmin_host, tasmax_host, T, ldx, offset, thresholds, n_thr, out_host, ldo, out_pstride, flags);
-}
-
-int wagg::entry::apply_poly_f32(const wagg_plan *plan, const float *X_dev, int64_t T, int64_t ldx, int layout,
-                                   double offset, int pow_first, int n_pow, float *out_dev, int64_t ldo,
-                                   int64_t out_pstride, int out_layout, void *stream) {
-    return wagg::apply_poly<float, 64>(plan, X_dev, T, ldx, layout, offset, pow_first, n_pow, out_dev, ldo, out_pstride,
-                                       out_layout, (hipStream_t)stream);
-}
-int wagg::entry::apply_poly_f64(const wagg_plan *plan, const double *X_dev, int64_t T, int64_t ldx, int layout,
-                                   double offset, int pow_first, int n_pow, double *out_dev, int64_t ldo,
-                                   int64_t out_pstride, int out_layout, void *stream) {
-    return wagg::apply_poly<double, 32>(plan, X_dev, T, ldx, layout, offset, pow_first, n_pow, out_dev, ldo, out_pstride,
-                                        out_layout, (hipStream_t)stream);
-}
-
-namespace wagg {
 // Snyder exceedance degree days (transformations.py:7-93) of (tasmin, tasmax) + offset at each of
 // n_thr thresholds, aggregated like wagg_apply; threshold i lands at out + i * out_pstride.
-template <typename T, int TB>
-static int apply_edd(const wagg_plan *plan, const T *tmin, const T *tmax, int64_t Tn, int64_t ldx, int layout,
-                     double offset, const double *thr, int n_thr, T *out, int64_t ldo, int64_t out_pstride,
-                     int out_layout, hipStream_t st) {
+template <typename T>
+int entry::apply_edd(const wagg_plan *plan, const T *tmin, const T *tmax, int64_t Tn, int64_t ldx, int layout, double offset,
+                     const double *thr, int n_thr, T *out, int64_t ldo, int64_t out_pstride, int out_layout, void *stream) {
+    constexpr int TB = SEG_TB<T>;
+    const hipStream_t st = (hipStream_t)stream;
     int rc = check_apply_args(plan, tmin, Tn, ldx, layout, out, ldo, out_layout);
     if (rc != WAGG_OK) return rc;
     WAGG_REQUIRE(Tn == 0 || tmax != nullptr, "tasmax is NULL");
@@ -2627,19 +2569,6 @@ static int apply_edd(const wagg_plan *plan, const T *tmin, const T *tmax, int64_
     return rc;
 }
 }  // namespace wagg
-
-int wagg::entry::apply_edd_f32(const wagg_plan *plan, const float *tasmin_dev, const float *tasmax_dev, int64_t T,
-                                  int64_t ldx, int layout, double offset, const double *thresholds, int n_thr,
-                                  float *out_dev, int64_t ldo, int64_t out_pstride, int out_layout, void *stream) {
-    return wagg::apply_edd<float, 64>(plan, tasmin_dev, tasmax_dev, T, ldx, layout, offset, thresholds, n_thr, out_dev,
-                                      ldo, out_pstride, out_layout, (hipStream_t)stream);
-}
-int wagg::entry::apply_edd_f64(const wagg_plan *plan, const double *tasmin_dev, const double *tasmax_dev, int64_t T,
-                                  int64_t ldx, int layout, double offset, const double *thresholds, int n_thr,
-                                  double *out_dev, int64_t ldo, int64_t out_pstride, int out_layout, void *stream) {
-    return wagg::apply_edd<double, 32>(plan, tasmin_dev, tasmax_dev, T, ldx, layout, offset, thresholds, n_thr, out_dev,
-                                       ldo, out_pstride, out_layout, (hipStream_t)stream);
-}
 
 // ---------------------------------------------------------------------------------------------
 // many-plans: K weightings x (fine level + derived coarse levels) of one table (include/wagg.h)
@@ -2807,24 +2736,24 @@ extern "C" int wagg_plan_get_den_many(const wagg_plan *plan, int weighting, int 
 
 namespace wagg {
 template <typename T>
-static int apply_many_dev(const wagg_plan *plan, const T *X, int64_t Tn, int64_t ldx, int layout, T *out, int64_t ldo,
-                          int out_layout, void *stream) {
+int entry::apply_many(const wagg_plan *plan, const T *X, int64_t Tn, int64_t ldx, int layout, T *out, int64_t ldo, int out_layout,
+                      void *stream) {
     int rc = check_apply_args(plan, X, Tn, ldx, layout, out, ldo, out_layout);
     if (rc != WAGG_OK) return rc;
-    return launch_many<T, (sizeof(T) == 4 ? 64 : 32)>(plan, X, Tn, ldx, layout, out, ldo, out_layout, (hipStream_t)stream);
+    return launch_many<T, SEG_TB<T>>(plan, X, Tn, ldx, layout, out, ldo, out_layout, (hipStream_t)stream);
 }
 
 // host-resident field through a many-plan: the row-block pipeline of a single plan with one output block per row block that is
 // out_cols wide, so the field crosses PCIe once (lines-only / quads-only packing: the structure is the same for all planes)
 template <typename T>
-static int apply_many_host(const wagg_plan *plan, const T *X, int64_t Tn, int64_t ldx, int layout, T *out, int64_t ldo,
-                           int out_layout, int flags) {
+int entry::apply_many_host(const wagg_plan *plan, const T *X, int64_t Tn, int64_t ldx, int layout, T *out, int64_t ldo, int out_layout,
+                           int flags) {
     clear_error();
     int rc = check_apply_args(plan, X, Tn, ldx, layout, out, ldo, out_layout);
     if (rc != WAGG_OK || Tn == 0) return rc;
     WAGG_REQUIRE((flags & ~(WAGG_HOST_PIN | WAGG_HOST_WHOLE | WAGG_HOST_LINES | WAGG_HOST_LINES_WHOLE)) == 0, "unknown host flags 0x%x", flags);
     if ((rc = check_plan_device(plan)) != WAGG_OK) return rc;
-    constexpr int TB = sizeof(T) == 4 ? 64 : 32;
+    constexpr int TB = SEG_TB<T>;
     if (layout == WAGG_LAYOUT_TG && out_layout == WAGG_OUT_TR && !(flags & WAGG_HOST_WHOLE)) {
         const wagg_plan *p0 = plan->many_w[0];
         const bool fused = many_fused<T>(plan, layout);
@@ -2834,35 +2763,29 @@ static int apply_many_host(const wagg_plan *plan, const T *X, int64_t Tn, int64_
                                          return launch_many<T, TB>(plan, xd, rows, ldx_dev, WAGG_LAYOUT_TG, od, ldo, WAGG_OUT_TR, st, compact);
                                      }, dc, true);
     }
-    const int64_t xrows = layout == WAGG_LAYOUT_TG ? Tn : plan->info.G;
-    const int64_t orows = out_layout == WAGG_OUT_TR ? Tn : plan->info.R;
-    ScratchBuf<T> dx, dout;
-    WAGG_HIP(dx.alloc((size_t)(xrows * ldx)));
-    WAGG_HIP(dout.alloc((size_t)(orows * ldo)));
-    const int64_t xcols = layout == WAGG_LAYOUT_TG ? plan->info.G : Tn, ocols = out_layout == WAGG_OUT_TR ? plan->info.R : Tn;
-    const bool pin = (flags & WAGG_HOST_PIN) != 0;
-    if ((rc = copy_to_device(dx.p, X, sizeof(T) * (size_t)((xrows - 1) * ldx + xcols), pin)) != WAGG_OK) return rc;
-    WAGG_HIP(hipMemset(dout.p, 0, sizeof(T) * (size_t)(orows * ldo)));
-    if ((rc = launch_many<T, TB>(plan, dx.p, Tn, ldx, layout, dout.p, ldo, out_layout, nullptr)) != WAGG_OK) return rc;
-    WAGG_HIP(hipDeviceSynchronize());
-    return copy_rows_to_host(out, dout.p, orows, sizeof(T) * (size_t)ldo, sizeof(T) * (size_t)ocols, pin);
+    // (no check_timeout after the drain here, unlike apply_host_ex)
+    return host_whole_field<T>(plan, X, Tn, ldx, layout, out, ldo, out_layout, flags, false, [&](const T *xd, T *od) {
+        return launch_many<T, TB>(plan, xd, Tn, ldx, layout, od, ldo, out_layout, nullptr);
+    });
 }
-}  // namespace wagg
 
-int wagg::entry::apply_many_f32(const wagg_plan *plan, const float *X, int64_t T, int64_t ldx, int layout, float *out, int64_t ldo,
-                                int out_layout, void *stream) {
-    return wagg::apply_many_dev<float>(plan, X, T, ldx, layout, out, ldo, out_layout, stream);
-}
-int wagg::entry::apply_many_f64(const wagg_plan *plan, const double *X, int64_t T, int64_t ldx, int layout, double *out, int64_t ldo,
-                                int out_layout, void *stream) {
-    return wagg::apply_many_dev<double>(plan, X, T, ldx, layout, out, ldo, out_layout, stream);
-}
-int wagg::entry::apply_many_host_f32(const wagg_plan *plan, const float *X, int64_t T, int64_t ldx, int layout, float *out, int64_t ldo,
-                                     int out_layout, int flags) {
-    return wagg::apply_many_host<float>(plan, X, T, ldx, layout, out, ldo, out_layout, flags);
-}
-int wagg::entry::apply_many_host_f64(const wagg_plan *plan, const double *X, int64_t T, int64_t ldx, int layout, double *out, int64_t ldo,
-                                     int out_layout, int flags) {
-    return wagg::apply_many_host<double>(plan, X, T, ldx, layout, out, ldo, out_layout, flags);
-}
-bool wagg::entry::is_many_plan(const wagg_plan *plan) { return plan != nullptr && plan->is_many(); }
+bool entry::is_many_plan(const wagg_plan *plan) { return plan != nullptr && plan->is_many(); }
+
+// the typed apply layer of the segment-table plan kind, for both element types
+#define WAGG_ENTRY_SPARSE(T)                                                                                                                          \
+    template int entry::apply<T>(const wagg_plan *, const T *, int64_t, int64_t, int, T *, int64_t, int, void *);                                     \
+    template int entry::apply_compact<T>(const wagg_plan *, const T *, int64_t, int64_t, T *, int64_t, void *);                                       \
+    template int entry::apply_host_ex<T>(const wagg_plan *, const T *, int64_t, int64_t, int, T *, int64_t, int, int);                                \
+    template int entry::apply_host_multi<T>(const wagg_plan *const *, const int *, int, const T *, int64_t, int64_t, T *, int64_t, int);              \
+    template int entry::apply_poly<T>(const wagg_plan *, const T *, int64_t, int64_t, int, double, int, int, T *, int64_t, int64_t, int, void *);     \
+    template int entry::apply_poly_host<T>(const wagg_plan *, const T *, int64_t, int64_t, double, int, int, T *, int64_t, int64_t, int);             \
+    template int entry::apply_edd<T>(const wagg_plan *, const T *, const T *, int64_t, int64_t, int, double, const double *, int, T *, int64_t,       \
+                                     int64_t, int, void *);                                                                                           \
+    template int entry::apply_edd_host<T>(const wagg_plan *, const T *, const T *, int64_t, int64_t, double, const double *, int, T *, int64_t,       \
+                                          int64_t, int);                                                                                              \
+    template int entry::apply_many<T>(const wagg_plan *, const T *, int64_t, int64_t, int, T *, int64_t, int, void *);                                \
+    template int entry::apply_many_host<T>(const wagg_plan *, const T *, int64_t, int64_t, int, T *, int64_t, int, int);
+WAGG_ENTRY_SPARSE(float)
+WAGG_ENTRY_SPARSE(double)
+#undef WAGG_ENTRY_SPARSE
+}  // namespace wagg
