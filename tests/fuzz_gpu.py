@@ -3,7 +3,8 @@
 usage: python tests/fuzz_gpu.py [n_cases] [seed]      -- prints one line per failing case, exit 1 on any
 FUZZ_LINES=1: lines_case (the lines-only host path); FUZZ_MANY=1: many_case (many-plans, wagg_plan_create_many);
 FUZZ_FLAGS=1: flags_case (the kernels behind the WAGG_PLAN_NO_* flags and plans without a row length);
-FUZZ_FORMS=1: forms_case (dense-family plans with a forced form: full, tile-sparse, entry lists)"""
+FUZZ_FORMS=1: forms_case (dense-family plans with a forced form: full, tile-sparse, entry lists);
+FUZZ_BUILD=1: build_case (the device plan builder: every stored weight against the table-order pair sum)"""
 import os, sys, traceback
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -506,6 +507,59 @@ def forms_case(i, rng, run=True):
     return tag, fails
 
 
+def build_case(i, rng, run=True):
+    """FUZZ_BUILD=1: the device plan builder (csrc/wagg_build.hip) on a random table of up to 40,000 rows with a random share
+    of repeated rows (order-sensitive runs, tests/build_tables.py), of dropped rows, scattered or clustered, as COO, as CSR
+    with shuffled columns or as CSR with sorted columns.  An fp64 plan of a random form is read back with the impulse probe:
+    every stored weight within 2^-51 of the table-order pair sum, exact zeros, nnz, den within its fsum bound
+    (tests/build_tables.py: check_readback); a second build, the other routes of the same table and the general-sort twin of
+    a CSR route give the same bits.  The tag names the route -- [route coo] / [route csr] / [route csr_sorted]."""
+    from tests import build_tables as B
+    G = int(rng.choice([1, 127, 129, 300, 1000]))
+    R = int(rng.choice([3, 37, 100, 689]))
+    n_valid = int(min(rng.integers(1, 40001), 0.8 * G * (R - 1)))
+    p_run = float(rng.choice([0.0, 0.1, 0.5]))
+    n_drop = int(n_valid * float(rng.choice([0.0, 0.0, 0.02, 0.3])))
+    order = "scattered" if rng.random() < 0.7 else "csr"
+    route = ["coo", "csr", "csr_sorted"][int(rng.integers(0, 3))]
+    form = ["full", "tiles", "entries"][int(rng.integers(0, 3))]
+    seed = int(rng.integers(0, 2 ** 31))
+    tag = "build case %d: G=%d R=%d n_valid=%d n_drop=%d p_run=%.1f %s %s [route %s]" % (i, G, R, n_valid, n_drop, p_run, order, form, route)
+    if not run:
+        return tag, None
+    t = B.random_table("fuzz", n_valid, n_drop, G, R, seed, p_run=p_run, order=order)
+    ref, cells = t.ref(), B.probe_cells(t)
+    X = torch.zeros((len(cells), G), dtype=torch.float64, device="cuda")
+    X[torch.arange(len(cells), device="cuda"), torch.from_numpy(cells).cuda()] = torch.from_numpy(B.amplitudes(cells)).cuda()
+    field = torch.from_numpy(np.random.default_rng(seed).standard_normal((17, G))).cuda()
+
+    def read(rt, general_sort=False):
+        if rt == "coo":
+            plan = DensePlan.from_segments(*t.coo(), G, R, dtype=np.float64, form=form)
+        else:
+            arrays = t.csr(sort_columns=rt == "csr_sorted")
+            plan = DensePlan.from_csr(*arrays, G, R, dtype=np.float64, form=form, general_sort=general_sort)
+            if plan.info["one_pass_sort"] != t.expect_one_pass(arrays[0], arrays[1], general_sort):
+                fails.append("%s: one_pass_sort %d" % (rt, plan.info["one_pass_sort"]))
+        out = (plan.info["nnz"], plan.den.copy(), plan.apply(X).cpu().numpy(), plan.apply(field).cpu().numpy())
+        plan.close()
+        return out
+
+    fails = []
+    first = read(route)
+    try:
+        B.check_readback(ref, cells, B.Readback(*first[:3]))
+    except AssertionError as e:
+        fails.append(str(e).splitlines()[0])
+    others = [("second build", route, False)] + [(rt, rt, False) for rt in ("coo", "csr", "csr_sorted") if rt != route]
+    others += [("general sort of " + rt, rt, True) for rt in ("csr", "csr_sorted")]
+    for what, rt, gs in others:
+        got = read(rt, gs)
+        if got[0] != first[0] or not all(np.array_equal(a, b, equal_nan=True) for a, b in zip(got[1:], first[1:])):
+            fails.append("%s differs from %s" % (what, route))
+    return tag, fails
+
+
 def main():
     global one_case
     if os.environ.get("FUZZ_LINES"):
@@ -516,6 +570,8 @@ def main():
         one_case = flags_case
     if os.environ.get("FUZZ_FORMS"):
         one_case = forms_case
+    if os.environ.get("FUZZ_BUILD"):
+        one_case = build_case
     rng = np.random.default_rng(SEED)
     bad = 0
     for i in range(N):
