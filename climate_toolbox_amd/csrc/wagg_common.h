@@ -62,7 +62,9 @@ template <typename T> __device__ __forceinline__ T snyder_edd1(T tmin, T tmax, T
     T theta, c;
     if constexpr (sizeof(T) == 4) { theta = asinf(z); c = sqrtf((T(1) - z) * (T(1) + z)); }
     else { theta = asin(z); c = sqrt((T(1) - z) * (T(1) + z)); }
-    return ((M - e) * (pi / T(2) - theta) + w * c) / pi;
+    // (for z -> 1 the two terms cancel and the sum can round a hair below 0 where the band value is positive: never negative)
+    const T r = ((M - e) * (pi / T(2) - theta) + w * c) / pi;
+    return r < T(0) ? T(0) : r;                                      // (a NaN, from +-inf data, stays)
 }
 
 // fp32: the same function in a cheaper form.  With z = (e - M) / w in (-1, 1), theta = asin z and d = M - e = -z w the
@@ -70,16 +72,21 @@ template <typename T> __device__ __forceinline__ T snyder_edd1(T tmin, T tmax, T
 //   f(x) = (1 - x)^(3/2) P(x),  P smooth between 1/pi (x = 0) and 2 sqrt(2) / (3 pi) (x = 1):
 // a degree-6 minimax fit of P (|error| <= 5e-9, tools/fit_edd_poly.py) leaves ONE v_sqrt_f32, v_rcp_f32 and ~15 vector
 // instructions per value (round 2: Abramowitz & Stegun 4.4.46 for the arcsine, two square roots, ~27).  With |z| clamped to 1
-// the expression  w s t P(|z|) + max(d, 0)  (t = 1 - |z|, s = sqrt t) also gives the two outer cases by itself for finite
-// data: M - e where tasmin >= e (z <= -1) and 0 where tasmax <= e (z >= 1); w = 0 is covered by the clamp (v_min returns
-// the number when z is 0 * inf).  snyder_edd1_finite is that expression alone; snyder_edd1<float> adds the reference's two
-// selections, which also decide what a NaN in either field gives (a NaN tasmin NaN, a NaN tasmax below the threshold 0).
+// the expression  w s t P(|z|) + max(d, 0)  (t = 1 - |z|, s = sqrt t) gives the two outer cases for finite data only up to
+// rounding: d and w round separately, so |d * rcp(w)| can come out just below 1 where the exact quotient is >= 1 and the clamp
+// does not fire (tasmax == e then gave ~1e-8 where the reference selects 0).  snyder_edd1_finite therefore forces |z| = 1 by the
+// reference's own comparisons -- !(tasmin < e) or !(tasmax > e), on the rounded values -- so that t = 0 and the product vanishes,
+// and takes d itself instead of max(d, 0) where tasmin >= e (the same number for tasmin <= tasmax, where d >= 0 because rounding
+// is monotone; M - e also for inverted data): M - e and 0 exactly as the reference selects them, for finite data, without the
+// selections at the end; w = 0 falls under the same comparisons.  snyder_edd1<float> adds the reference's two selections,
+// which decide what a NaN in either field gives (a NaN tasmin NaN, a NaN tasmax below the threshold 0).
 // The degree days differ from the fp64 libm evaluation by <= 2e-6 absolute (tolerance of the fp32 path: 1e-4 relative).
 __device__ __forceinline__ float snyder_edd1_finite(float tmin, float tmax, float e) {
     const float M = 0.5f * (tmax + tmin), w = 0.5f * (tmax - tmin);
     const float d = M - e;
     const float z = -d * __builtin_amdgcn_rcpf(w);                     // (e - M) / w
-    const float az = __builtin_fminf(__builtin_fabsf(z), 1.0f);
+    const bool below = tmin < e;
+    const float az = (below && tmax > e) ? __builtin_fminf(__builtin_fabsf(z), 1.0f) : 1.0f;   // the outer cases: t = 0 exactly
     const float t = 1.0f - az;
     float p = 7.577220821985975e-05f;
     p = __builtin_fmaf(p, az, -0.0003951705584768206f);
@@ -89,7 +96,7 @@ __device__ __forceinline__ float snyder_edd1_finite(float tmin, float tmax, floa
     p = __builtin_fmaf(p, az, -0.022534651681780815f);
     p = __builtin_fmaf(p, az, 0.31830987334251404f);
     const float q = __builtin_amdgcn_sqrtf(t) * t;                     // (1 - |z|)^(3/2)
-    return __builtin_fmaf(w, q * p, __builtin_fmaxf(d, 0.0f));
+    return __builtin_fmaf(w, q * p, below ? __builtin_fmaxf(d, 0.0f) : d);
 }
 // fp64: the same expression with a degree-13 fit of P (|error| <= 4.4e-15, tools/fit_edd_poly.py): a reciprocal, a reciprocal
 // square root and 13 fused multiply-adds where asin + sqrt of libm take several hundred instructions; used by the
@@ -101,7 +108,9 @@ __device__ __forceinline__ double snyder_edd1_finite(double tmin, double tmax, d
     // square-root sequences are a third of this function's instructions)
     double rw = __builtin_amdgcn_rcp(w);
     rw = __builtin_fma(rw, __builtin_fma(-w, rw, 1.0), rw);
-    const double az = __builtin_fmin(__builtin_fabs(d * rw), 1.0);     // |z|, z = (e - M) / w (w = 0: inf or NaN -> 1)
+    const bool below = tmin < e;
+    // |z|, z = (e - M) / w; the outer cases take 1 by the reference's comparisons (see the fp32 form), w = 0 among them
+    const double az = (below && tmax > e) ? __builtin_fmin(__builtin_fabs(d * rw), 1.0) : 1.0;
     const double t = 1.0 - az;
     const double ty = __builtin_amdgcn_rsq(__builtin_fmax(t, 1e-300));  // (t = 0: 0 * 1e150 = 0 below)
     double st = t * ty;                                                 // sqrt(t) to ~2^-26 ...
@@ -120,7 +129,7 @@ __device__ __forceinline__ double snyder_edd1_finite(double tmin, double tmax, d
     p = __builtin_fma(p, az, 0.005985979570242935);
     p = __builtin_fma(p, az, -0.0225351707225776);
     p = __builtin_fma(p, az, 0.3183098861837864);
-    return __builtin_fma(w, st * t * p, __builtin_fmax(d, 0.0));
+    return __builtin_fma(w, st * t * p, below ? __builtin_fmax(d, 0.0) : d);
 }
 template <> __device__ __forceinline__ float snyder_edd1<float>(float tmin, float tmax, float e) {
     const float d = 0.5f * (tmax + tmin) - e;

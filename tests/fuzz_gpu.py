@@ -37,6 +37,25 @@ def rel_bad(got, ref, rtol, scale):
     return None
 
 
+def edge_thresholds(thr, lo, hi, cell, off, dtype):
+    """``thr`` and, in about a third of the cases, one or two more thresholds that EQUAL ``dtype(tasmin + off)`` or
+    ``dtype(tasmax + off)`` of a cell the table references: the band edges, where the reference selects M - e or 0.  The draw
+    comes from a generator of its own (seeded by the case's first threshold), and the thresholds are appended: a seed's case is
+    what it was, with at most two planes more."""
+    if not len(cell) or not lo.size:
+        return thr
+    side = np.random.default_rng(int(abs(thr[0]) * 1e9) % (1 << 32))
+    if side.random() >= 0.35:
+        return thr
+    more = []
+    for _ in range(int(side.integers(1, 3))):
+        t, c = int(side.integers(0, lo.shape[0])), int(cell[int(side.integers(0, len(cell)))])
+        v = float(dtype((lo if side.random() < 0.5 else hi)[t, c] + dtype(off)))
+        if np.isfinite(v):
+            more.append(v)
+    return thr + more
+
+
 def one_case(i, rng):
     dtype = np.float32 if rng.random() < 0.6 else np.float64
     rtol = 1e-4 if dtype == np.float32 else 1e-6
@@ -122,6 +141,7 @@ def one_case(i, rng):
         half = rng.uniform(0, 8, X.shape).astype(dtype)
         lo, hi = X - half, X + half
         thr = [float(rng.uniform(5, 35)) for _ in range(int(rng.integers(1, 7)))]        # 1..6: passes of four + a rest
+        thr = edge_thresholds(thr, lo, hi, cell, -273.15, dtype)
         ge = plan.apply_edd(dev(lo), dev(hi), thr, offset=-273.15, layout=layout, out_layout=out_layout).cpu().numpy()
         ft = dtype
         for k, e in enumerate(thr):
@@ -208,6 +228,7 @@ def lines_case(i, rng):
         half = rng.uniform(0, 8, X.shape).astype(dtype)
         lo, hi = X - half, X + half
         thr = [float(rng.uniform(5, 35)) for _ in range(int(rng.integers(1, 6)))]
+        thr = edge_thresholds(thr, lo, hi, cell, -273.15, dtype)
         ge = plan.apply_edd_host(lo, hi, thr, offset=-273.15, flags=flags)
         gd = plan.apply_edd(torch.from_numpy(lo).cuda(), torch.from_numpy(hi).cuda(), thr, offset=-273.15).cpu().numpy()
         if not np.array_equal(ge, gd, equal_nan=True): fails.append("apply_edd_host differs from the device form")
@@ -406,6 +427,7 @@ def flags_case(i, rng, run=True):
             if b: fails.append("poly p=%d: %s" % (p0 + k, b))
     elif kind == "edd":
         lo, hi = X - half, X + half
+        thr = edge_thresholds(thr, lo, hi, cell, -273.15, dtype)
         ge = tr(plan.apply_edd(dev(lo), dev(hi), thr, offset=-273.15, layout=layout, out_layout=out_layout).cpu().numpy())
         for k, e in enumerate(thr):
             b = rel_bad(ge[k], O.agg_coded(O.snyder_edd_values(lo + dtype(-273.15), hi + dtype(-273.15), e), cell, code, w, R), rtol, 0.05)
