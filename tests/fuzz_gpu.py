@@ -4,7 +4,8 @@ usage: python tests/fuzz_gpu.py [n_cases] [seed]      -- prints one line per fai
 FUZZ_LINES=1: lines_case (the lines-only host path); FUZZ_MANY=1: many_case (many-plans, wagg_plan_create_many);
 FUZZ_FLAGS=1: flags_case (the kernels behind the WAGG_PLAN_NO_* flags and plans without a row length);
 FUZZ_FORMS=1: forms_case (dense-family plans with a forced form: full, tile-sparse, entry lists);
-FUZZ_BUILD=1: build_case (the device plan builder: every stored weight against the table-order pair sum)"""
+FUZZ_BUILD=1: build_case (the device plan builder: every stored weight against the table-order pair sum);
+FUZZ_ELEMENTS=1: elements_case (relayout, to_float64, take_axis, gather: bits against tests/element_ops.py)"""
 import os, sys, traceback
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -582,8 +583,82 @@ def build_case(i, rng, run=True):
     return tag, fails
 
 
+def elements_case(i, rng, run=True):
+    """FUZZ_ELEMENTS=1: one of the data-movement kernels of csrc/wagg_util.hip -- engine.relayout, to_float64, take_axis or
+    gather -- on a random element type, 1 to 6 dims of extents 1 to 9, a view with random steps and starts inside a larger
+    buffer (relayout, to_float64), a random order of the dims, a random axis and index list (take_axis), random cells, layouts
+    and a pitched field (gather).  Random 32- / 64-bit words with NaNs, infinities, -0 and subnormals planted; results compared
+    as bits with the restatements of tests/element_ops.py.  The tag names the kernel -- [kernel relayout] / [kernel to_float64]
+    / [kernel take_axis] / [kernel gather].  run=False: the tag alone, from the same random stream."""
+    from tests import element_ops as E
+    kernel = ["relayout", "to_float64", "take_axis", "gather"][int(rng.integers(0, 4))]
+    dtype = np.float32 if rng.random() < 0.5 else np.float64
+    kind = E.TO_F64_KINDS[int(rng.integers(0, len(E.TO_F64_KINDS)))]
+    nd = int(rng.integers(1, 7))
+    shape = [int(rng.integers(1, 10)) for _ in range(nd)]
+    steps = [int(rng.integers(1, 4)) for _ in range(nd)]
+    starts = [int(rng.integers(0, 2)) for _ in range(nd)]
+    order = [int(k) for k in rng.permutation(nd)]
+    axis = int(rng.integers(-nd, nd))
+    idx = rng.integers(0, shape[axis], int(rng.integers(0, 2 * shape[axis] + 2)))
+    nseg = int(rng.choice([0, 1, 7, 255, 256, 257, 600]))
+    layout, out_layout = ("TG" if rng.random() < 0.5 else "GT"), ("TR" if rng.random() < 0.5 else "RT")
+    seed = int(rng.integers(0, 2 ** 31))
+    what = {"relayout": "%s steps=%r starts=%r order=%r" % (dtype.__name__, steps, starts, order),
+            "to_float64": "%s steps=%r starts=%r order=%r" % (kind, steps, starts, order),
+            "take_axis": "%s axis=%d n_idx=%d" % (dtype.__name__, axis, len(idx)),
+            "gather": "%s nseg=%d %s->%s pitch+%d" % (dtype.__name__, nseg, layout, out_layout, steps[0] - 1)}[kernel]
+    tag = "elements case %d: shape=%r %s [kernel %s]" % (i, shape, what, kernel)
+    if not run:
+        return tag, None
+    from climate_toolbox_amd import engine
+    fails = []
+    big = [b + s * st for b, s, st in zip(starts, shape, steps)]
+    cut = tuple(slice(b, b + s * st, st) for b, s, st in zip(starts, shape, steps))
+    n = int(np.prod(big))
+
+    def typed(kind, values):
+        if kind == "float16":
+            return torch.from_numpy(values.view(np.float16).copy()).cuda()
+        if kind == "bfloat16":
+            return torch.from_numpy(values.view(np.int16).copy()).cuda().view(torch.bfloat16)
+        return torch.from_numpy(values.copy()).cuda()
+
+    if kernel in ("relayout", "to_float64"):
+        pos = np.arange(n, dtype=np.int64)
+        v = E._describe(tag, pos, pos.reshape(big)[cut], order)
+        if kernel == "relayout":
+            data = E.random_words(n, dtype, seed)
+            got = engine.relayout(torch.as_strided(torch.from_numpy(data).cuda(), v.shape, v.strides, v.base), v.order).cpu().numpy()
+            why = E.same_f64(got, E.relayout_ref(data, v), exact_nan=True)
+        else:
+            pool = E.to_f64_values(kind, seed % 1000)
+            values = pool[np.random.default_rng(seed).integers(0, len(pool), n)]
+            got = engine.to_float64(torch.as_strided(typed(kind, values), v.shape, v.strides, v.base), v.order).cpu().numpy()
+            why = E.same_f64(got, E.relayout_ref(E.to_f64_ref(kind, values), v), exact_nan=kind == "float64")
+        if why: fails.append("%s: %s" % (kernel, why))
+    elif kernel == "take_axis":
+        a = E.random_words(int(np.prod(shape)), dtype, seed).reshape(shape)
+        got = engine.take_axis(torch.from_numpy(a).cuda(), axis, idx).cpu().numpy()
+        why = E.same_f64(got, np.take(a, idx, axis=axis), exact_nan=True)
+        if why: fails.append("take_axis: " + why)
+    else:
+        T, G = shape[0], int(np.prod(shape[1:]))
+        X = E.random_words(T * G, dtype, seed).reshape(T, G)
+        a = X if layout == "TG" else np.ascontiguousarray(X.T)
+        wide = torch.full((a.shape[0], a.shape[1] + steps[0] - 1), float("nan"), dtype=torch.from_numpy(a).dtype, device="cuda")
+        wide[:, :a.shape[1]] = torch.from_numpy(a).cuda()
+        cells = E.gather_cells(G, nseg, seed)
+        got = engine.gather(wide[:, :a.shape[1]], torch.from_numpy(cells).cuda(), layout=layout, out_layout=out_layout).cpu().numpy()
+        why = E.same_f64(got, E.gather_ref(X, cells, out_layout), exact_nan=True)
+        if why: fails.append("gather: " + why)
+    return tag, fails
+
+
 def main():
     global one_case
+    if os.environ.get("FUZZ_ELEMENTS"):
+        one_case = elements_case
     if os.environ.get("FUZZ_LINES"):
         one_case = lines_case
     if os.environ.get("FUZZ_MANY"):
