@@ -5,7 +5,8 @@ FUZZ_LINES=1: lines_case (the lines-only host path); FUZZ_MANY=1: many_case (man
 FUZZ_FLAGS=1: flags_case (the kernels behind the WAGG_PLAN_NO_* flags and plans without a row length);
 FUZZ_FORMS=1: forms_case (dense-family plans with a forced form: full, tile-sparse, entry lists);
 FUZZ_BUILD=1: build_case (the device plan builder: every stored weight against the table-order pair sum);
-FUZZ_ELEMENTS=1: elements_case (relayout, to_float64, take_axis, gather: bits against tests/element_ops.py)"""
+FUZZ_ELEMENTS=1: elements_case (relayout, to_float64, take_axis, gather: bits against tests/element_ops.py);
+FUZZ_SPLIT=1: split_case (the split form of fp32 full-form plans under power-of-two row and column scales)"""
 import os, sys, traceback
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -655,8 +656,64 @@ def elements_case(i, rng, run=True):
     return tag, fails
 
 
+def split_case(i, rng, run=True):
+    """FUZZ_SPLIT=1: the split form of an fp32 full-form plan (DensePlan.from_host; csrc/wagg_dense_split.inc) with G in
+    [33, 700], R in [1, 700], T in [1, 400]: weights uniform(0.1, 1) with a random share of zeros, column r scaled by 2^j[r],
+    j in [-60, 60]; rows N(0, 1) scaled by 2^k[t], k in [-100, 100], a random share of the values with a 22-bit significand
+    whose f16 low part is large (tests/split_parts.py: two_part), 1 % NaN; aligned or unaligned rows.  Against the fp64
+    quotient within the documented bound (4e-6 of sum |x| |w| / |den| plus the 2^-36 floors) wherever sum |x| |w| and the
+    result's scale lie in [2^-110, 2^126] (a sum outside fp32's range overflows or flushes by design, as in the exact
+    kernel), and against the unscaled plan bit for bit (column scales are powers of two) wherever they lie in [2^-60, 2^120]
+    and the result itself is above 2^-120.  run=False: the tag alone, from the same random stream."""
+    G, R, T = int(rng.integers(33, 701)), int(rng.integers(1, 701)), int(rng.integers(1, 401))
+    W = rng.uniform(0.1, 1.0, (G, R)).astype(np.float32)
+    W[rng.random((G, R)) < rng.uniform(0.0, 0.7)] = 0.0
+    W[int(rng.integers(0, G)), :] = np.float32(0.5)                                  # (no all-zero column)
+    j = rng.integers(-60, 61, R).astype(np.int32)
+    k = rng.integers(-100, 101, T).astype(np.int32)
+    X = rng.standard_normal((T, G))
+    share = float(rng.uniform(0.0, 1.0))
+    two = rng.random((T, G)) < share
+    m, e = np.frexp(X)
+    sig = np.sign(m) * (2 ** 21 + rng.integers(0, 1024, (T, G)) * 2 ** 11 + 513 + 2 * rng.integers(0, 512, (T, G))) * 2.0 ** -22
+    X = np.ldexp(np.where(two, np.ldexp(sig, e), X).astype(np.float32), k[:, None])
+    X[rng.random((T, G)) < 0.01] = np.nan
+    unaligned = bool(rng.random() < 0.5)
+    tag = "split case %d: T=%d G=%d R=%d two-part %.2f %s [split]" % (i, T, G, R, share, "unaligned" if unaligned else "contiguous")
+    if not run:
+        return tag, None
+    fails = []
+    Wj = np.ldexp(W, j[None, :])
+    Xd = torch.from_numpy(X).cuda()
+    if unaligned:
+        wide = torch.full((T, (G + 8) // 4 * 4), float("nan"), dtype=Xd.dtype, device="cuda")
+        wide[:, 1:1 + G] = Xd
+        Xd = wide[:, 1:1 + G]
+    ax, aw = np.abs(np.where(np.isnan(X), 0.0, X).astype(np.float64)), np.abs(Wj.astype(np.float64))
+    den = Wj.astype(np.float64).sum(0)
+    num = ax @ aw
+    ref = (np.where(np.isnan(X), 0.0, X).astype(np.float64) @ Wj.astype(np.float64)) / den[None, :]
+    tol = (4e-6 * num + 2.0 ** -36 * ax.max(1, keepdims=True) * aw.sum(0)[None, :] + 2.0 ** -36 * aw.max(0)[None, :] * ax.sum(1, keepdims=True)) / den[None, :]
+    scale = num / den[None, :]
+    ok = (num >= 2.0 ** -110) & (num <= 2.0 ** 126) & (scale >= 2.0 ** -110) & (scale <= 2.0 ** 126)
+    law = (num >= 2.0 ** -60) & (num <= 2.0 ** 120) & (scale >= 2.0 ** -60) & (scale <= 2.0 ** 120) & (np.abs(ref) >= 2.0 ** -120)
+    plan, base = DensePlan.from_host(Wj), DensePlan.from_host(W)
+    got, plain = plan.apply(Xd).cpu().numpy(), base.apply(Xd).cpu().numpy()
+    if plan.saw_inf(): fails.append("a note of +-inf that nothing explains")
+    if not np.isfinite(got[ok]).all(): fails.append("non-finite results in range")
+    elif not (np.abs(got[ok] - ref[ok]) <= tol[ok]).all():
+        fails.append("max err/tol %.3g" % (np.abs(got[ok] - ref[ok]) / tol[ok]).max())
+    if not np.array_equal(got[law], plain[law]): fails.append("the column scales change %d results" % (got[law] != plain[law]).sum())
+    if ok.mean() < 0.3: fails.append("only %.2f of the results compared" % ok.mean())
+    plan.close()
+    base.close()
+    return tag, fails
+
+
 def main():
     global one_case
+    if os.environ.get("FUZZ_SPLIT"):
+        one_case = split_case
     if os.environ.get("FUZZ_ELEMENTS"):
         one_case = elements_case
     if os.environ.get("FUZZ_LINES"):
