@@ -33,7 +33,7 @@ EXPORTS = (
     "wagg_any_less_f32", "wagg_any_less_f64",
     "wagg_dense_create_synth", "wagg_dense_create_host", "wagg_dense_create_from_segments", "wagg_dense_create_synth_blocklocal", "wagg_dense_create_synth_sparse", "wagg_dense_get_info",
     "wagg_dense_destroy", "wagg_dense_clone", "wagg_release_scratch", "wagg_scratch_bytes", "wagg_dense_get_den", "wagg_dense_apply_f32", "wagg_dense_apply_poly_f32",
-    "wagg_dense_apply_edd_f32", "wagg_dense_saw_inf",
+    "wagg_dense_apply_edd_f32", "wagg_dense_saw_inf", "wagg_dense_read_w",
     "wagg_dense_create_synth_f64", "wagg_dense_create_host_f64", "wagg_dense_create_from_segments_f64",
     "wagg_dense_create_synth_blocklocal_f64", "wagg_dense_apply_f64", "wagg_dense_apply_poly_f64", "wagg_dense_apply_edd_f64",
     "wagg_synth_field_f32", "wagg_synth_field_f64",
@@ -100,7 +100,7 @@ class DenseInfo(C.Structure):
                 ("form", C.c_int32), ("elem_bytes", C.c_int32), ("nnz", C.c_int64),
                 ("build_s", C.c_double), ("build_upload_s", C.c_double),
                 ("est_full_s", C.c_double), ("est_tiles_s", C.c_double), ("est_entries_s", C.c_double), ("walked_entries", C.c_int64),
-                ("one_pass_sort", C.c_int32), ("reserved0", C.c_int32)]
+                ("one_pass_sort", C.c_int32), ("reserved0", C.c_int32), ("w_image_bytes", C.c_int64)]
 
 
 class WaggError(RuntimeError):
@@ -308,7 +308,11 @@ def load():
         getattr(L, name).argtypes = [vp, vp, vp, C.c_int64, C.c_int64, vp, C.c_int64, vp]
     for name in ("wagg_pack_rows_host_f32", "wagg_pack_rows_host_f64"):
         getattr(L, name).argtypes = [vp, vp, vp, C.c_int64, C.c_int64, vp, C.c_int64, C.c_int]
+    if hasattr(L, "wagg_dense_read_w"):     # (a diagnostic entry: a library built from an older header lacks it)
+        L.wagg_dense_read_w.argtypes = [vp, C.c_int, vp, C.c_uint64]
     for name in EXPORTS:
+        if name == "wagg_dense_read_w" and not hasattr(L, name):
+            continue
         fn = getattr(L, name)
         if name not in ("wagg_last_error", "wagg_scratch_bytes", "wagg_period_reduce_work_bytes", "wagg_season_reduce_work_bytes",
                         "wagg_edd_ladder_work_bytes", "wagg_bin_days_work_bytes", "wagg_hinge_work_bytes"):

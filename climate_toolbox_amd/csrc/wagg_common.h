@@ -216,6 +216,7 @@ struct DevBuf {  // owning device buffer, freed in the destructor (plan lifetime
     DevBuf(const DevBuf &) = delete;
     DevBuf &operator=(const DevBuf &) = delete;
     ~DevBuf() { if (p) (void)hipFree(p); }
+    void reset() { if (p) (void)hipFree(p); p = nullptr; n = 0; }
     hipError_t alloc(size_t count) {
         if (p) { (void)hipFree(p); p = nullptr; }
         n = count;

@@ -425,7 +425,9 @@ static int dense_finish_den(wagg_dense *d) {
     return dense_den_to_host(d);
 }
 
-// column maxima of a full-form fp32 plan (the split form's column scales), whichever builder made it; other plans have none
+static void dense_build_image(wagg_dense *d, hipStream_t st);
+// column maxima of a full-form fp32 plan (the split form's column scales), whichever builder made it, and the f16 image of W
+// they scale (when memory allows); other plans have neither
 static int dense_finish_scales(wagg_dense *d, hipStream_t st = nullptr) {
     if (d->f64 || d->tiled || d->spmm) return WAGG_OK;
     const int kt_per_block = 128;
@@ -435,6 +437,7 @@ static int dense_finish_scales(wagg_dense *d, hipStream_t st = nullptr) {
     hipLaunchKernelGGL(dense_colmax_kernel, dim3((unsigned)d->n_nt, (unsigned)n_strips), dim3(512), 0, st,
                        reinterpret_cast<const f32x4 *>(d->W.p), d->n_kt, kt_per_block, reinterpret_cast<unsigned *>(d->wmax.p));
     WAGG_HIP(hipGetLastError());
+    dense_build_image(d, st);
     return WAGG_OK;
 }
 
@@ -586,6 +589,29 @@ static int pick_ksplit(int64_t items, int n_kt) {
         if (eff >= 0.985) break;
     }
     return best;
+}
+
+// The f16 hi/lo image of a full-form fp32 W (wagg_dense_split.inc: dense_split_image_kernel), built in stream order behind the
+// column maxima: the split apply then loads its W operands instead of splitting every element on every apply.  A second
+// copy of W's size, so it is optional and never an error: built only while the device has room for it AND the workspaces
+// of the plan's largest launch group (one row block of MT_MAX x 16 rows: packed X, slabs at pick_ksplit's S, row maxima);
+// without it the apply splits in registers as before.  WAGG_DENSE_NO_W_IMAGE=1 turns it off (parity tests, A/B runs).
+static void dense_build_image(wagg_dense *d, hipStream_t st) {
+    if (d->f64 || d->tiled || d->spmm || !d->wmax.p || d->n_tiles <= 0) return;
+    const char *off = getenv("WAGG_DENSE_NO_W_IMAGE");
+    if (off && off[0] && off[0] != '0') return;
+    constexpr size_t bm = (size_t)DT<float>::MT_MAX * 16;
+    const size_t S = (size_t)pick_ksplit(d->n_nt, d->n_kt);
+    const size_t workspace = (size_t)d->n_kt * bm * D_ROWB + (size_t)d->n_nt * S * bm * D_BN * sizeof(float) + bm * sizeof(float);
+    const size_t bytes = (size_t)d->w_slots() * 16;
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); return; }
+    if (free_b < bytes || free_b - bytes < workspace) return;
+    if (d->wimg.alloc(bytes / sizeof(float)) != hipSuccess) { (void)hipGetLastError(); d->wimg.reset(); return; }
+    const int64_t grid = d->n_tiles < (int64_t)d->ncu * 8 ? d->n_tiles : (int64_t)d->ncu * 8;
+    hipLaunchKernelGGL(dense_split_image_kernel, dim3((unsigned)grid), dim3(D_THREADS), 0, st, (const float *)d->W.p,
+                       (const float *)d->wmax.p, d->n_kt, d->n_tiles, d->wimg.p);
+    if (hipGetLastError() != hipSuccess) d->wimg.reset();
 }
 
 template <typename T>
@@ -918,9 +944,9 @@ static const void *pick_mfma_kernel(int MT, bool tiled, bool rm = false) {
 #undef WAGG_PICK
 }
 
-// split form (fp32 full-form plans, the default): MT from the same set as the fp32 kernel
-static const void *pick_split_kernel(int MT) {
-#define WAGG_PICK(M) case M: return (const void *)dense_split_kernel<M>
+// split form (fp32 full-form plans, the default): MT from the same set as the fp32 kernel; img = W comes from the plan's image
+static const void *pick_split_kernel(int MT, bool img) {
+#define WAGG_PICK(M) case M: return img ? (const void *)dense_split_kernel<M, 0, true> : (const void *)dense_split_kernel<M>
     switch (MT) {
         WAGG_PICK(1); WAGG_PICK(2); WAGG_PICK(3); WAGG_PICK(4); WAGG_PICK(5); WAGG_PICK(6); WAGG_PICK(8);
         WAGG_PICK(10); WAGG_PICK(12); WAGG_PICK(14); WAGG_PICK(16); WAGG_PICK(18); WAGG_PICK(20);
@@ -938,23 +964,30 @@ static int dense_apply_split(wagg_dense *d, const float *X_dev, int64_t Tn, int6
     const int kt_per_slice = (n_kt + S - 1) / S;
     const int64_t nblk = (int64_t)n_nt * n_mb * S;
     WAGG_REQUIRE(nblk < (int64_t)0x7fffffff, "grid too large");
-    const void *kern = pick_split_kernel(MT);
-    if (!kern) { set_error("no split kernel for MT=%d", MT); return WAGG_EINVAL; }
     const size_t need = (size_t)nblk * bm * D_BN;
     if (d->slabs.n < need) WAGG_HIP(d->slabs.alloc(need));
     const int64_t x_slots = (int64_t)n_mb * n_kt * bm * 8;
     if (d->xp.n < (size_t)x_slots * 4) WAGG_HIP(d->xp.alloc((size_t)x_slots * 4));
     if (d->xmax.n < (size_t)Tn) WAGG_HIP(d->xmax.alloc((size_t)Tn));
+    // the image serves launches of ONE row block.  With several, every W tile is contracted once per row block and all but
+    // the first read are L2 hits; there the image measured no gain (c4's share, four row blocks: 0.6 % slower in every
+    // alternation, profiles/split_image_ab.txt), so those launches split in registers as before.
+    bool img = d->wimg.p != nullptr && n_mb == 1;
+#ifdef WAGG_DIAG      // WAGG_SPLIT_IMG=0: split in registers although the plan holds an image (A/B in one process)
+    if (const char *e = getenv("WAGG_SPLIT_IMG")) img = img && e[0] != '0';
+#endif
+    const void *kern = pick_split_kernel(MT, img);
+    if (!kern) { set_error("no split kernel for MT=%d", MT); return WAGG_EINVAL; }
     const int aligned = ((ldx * sizeof(float)) % 16 == 0) && ((reinterpret_cast<uintptr_t>(X_dev) & 15) == 0) &&
                         (xf.mode != XF_EDD || (reinterpret_cast<uintptr_t>(xf.X2) & 15) == 0);
 #ifdef WAGG_DIAG      // ablation variants (timing only; results are wrong with any bit set): tools/split_ablate.sh
     if (const char *dbg = MT == D_MT ? getenv("WAGG_SPLIT_DBG") : nullptr) {
-        switch (atoi(dbg)) {
-            case 1: kern = (const void *)dense_split_kernel<D_MT, 1>; break;
-            case 4: kern = (const void *)dense_split_kernel<D_MT, 4>; break;
-            case 5: kern = (const void *)dense_split_kernel<D_MT, 5>; break;
-            case 8: kern = (const void *)dense_split_kernel<D_MT, 8>; break;
-            case 9: kern = (const void *)dense_split_kernel<D_MT, 9>; break;
+        switch (atoi(dbg)) {     // (bit3 is the split's own knob: those variants read the fp32 W)
+            case 1: kern = img ? (const void *)dense_split_kernel<D_MT, 1, true> : (const void *)dense_split_kernel<D_MT, 1>; break;
+            case 4: kern = img ? (const void *)dense_split_kernel<D_MT, 4, true> : (const void *)dense_split_kernel<D_MT, 4>; break;
+            case 5: kern = img ? (const void *)dense_split_kernel<D_MT, 5, true> : (const void *)dense_split_kernel<D_MT, 5>; break;
+            case 8: kern = (const void *)dense_split_kernel<D_MT, 8>; img = false; break;
+            case 9: kern = (const void *)dense_split_kernel<D_MT, 9>; img = false; break;
             default: break;
         }
     }
@@ -969,7 +1002,7 @@ static int dense_apply_split(wagg_dense *d, const float *X_dev, int64_t Tn, int6
                        (const unsigned *)xmax, reinterpret_cast<f16x8 *>(d->xp.p), xf, d->inf_dev);
     WAGG_HIP(hipGetLastError());
     const f16x8 *xp = reinterpret_cast<const f16x8 *>(d->xp.p);
-    const float *wp = d->W.p, *wmax = d->wmax.p;
+    const float *wp = img ? d->wimg.p : d->W.p, *wmax = d->wmax.p;
     float *slabs = d->slabs.p;
     int n_kt_a = n_kt, n_nt_a = n_nt, n_mb_a = n_mb, S_a = S, kps = kt_per_slice;
     void *args[] = {&xp, &wp, &wmax, &n_kt_a, &n_nt_a, &n_mb_a, &S_a, &kps, &slabs};
@@ -1228,6 +1261,7 @@ extern "C" int wagg_dense_get_info_sized(const wagg_dense *d, void *info_buf, ui
     info->walked_entries = d->walked_entries;
     info->one_pass_sort = d->one_pass_sort ? 1 : 0;
     info->reserved0 = 0;
+    info->w_image_bytes = d->wimg.p ? d->w_slots() * 16 : 0;
     copy_sized(info_buf, size, &st, sizeof(st));
     return WAGG_OK;
 }
@@ -1280,6 +1314,7 @@ extern "C" int wagg_dense_clone(const wagg_dense *src, int device, wagg_dense **
         if (e == hipSuccess) e = clone_buf(d->tile_kt, device, src->tile_kt, src->device);
         if (e == hipSuccess) e = clone_buf(d->sp.ent, device, src->sp.ent, src->device);
         if (e == hipSuccess) e = clone_buf(d->sp.grp_off, device, src->sp.grp_off, src->device);
+        if (e == hipSuccess) dense_build_image(d, nullptr);       // (from the copy, under the rule of a first build, on this device)
         if (e == hipSuccess) e = hipStreamSynchronize(nullptr);   // (the copies are complete before anyone applies the clone)
         d->build.total_s = d->build.device_s = wall_s() - t0;
     } catch (const std::bad_alloc &) {
@@ -1300,6 +1335,21 @@ extern "C" int wagg_dense_clone(const wagg_dense *src, int device, wagg_dense **
 
 extern "C" int wagg_dense_destroy(wagg_dense *d) {
     delete d;
+    return WAGG_OK;
+}
+
+// Diagnostic entry (include/wagg.h): the stored tiles as they lie on the device; tests/test_gpu_split_image.py pins the image's
+// layout with it.
+extern "C" int wagg_dense_read_w(const wagg_dense *d, int image, void *host, uint64_t bytes) {
+    using namespace wagg;
+    clear_error();
+    WAGG_REQUIRE(d && host, "NULL argument");
+    WAGG_REQUIRE(!d->spmm, "an entry-list plan holds no W matrix");
+    const float *src = image ? d->wimg.p : d->W.p;
+    WAGG_REQUIRE(src != nullptr, "the plan holds no image of W");
+    WAGG_REQUIRE(bytes == (uint64_t)d->w_slots() * 16, "W is %lld bytes, the buffer %llu", (long long)d->w_slots() * 16,
+                 (unsigned long long)bytes);
+    WAGG_HIP(hipMemcpy(host, src, bytes, hipMemcpyDeviceToHost));
     return WAGG_OK;
 }
 

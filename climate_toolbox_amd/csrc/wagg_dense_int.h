@@ -77,6 +77,9 @@ struct wagg_dense {
     // full-form fp32 plans: max |w| of every column (n_nt * 256, zero-padded), from which the split form takes its
     // power-of-two column scales (wagg_dense_split.inc); xmax: the row maxima of the apply in flight (workspace)
     wagg::DevBuf<float> wmax, xmax;
+    // ... and, when the device had room for it at plan time, the f16 high / low parts of the scaled W in the packed tile
+    // layout (W's size again): what the split kernel would make of every tile on every apply (dense_split_image_kernel)
+    wagg::DevBuf<float> wimg;
     std::vector<double> den_host;
     // tile-sparse form: only the non-empty (32-cell x 256-region) tiles of W are stored, grouped by
     // column tile; tile_kt[i] = k tile of stored tile i (+2 padding entries)

@@ -70,6 +70,13 @@ __device__ __forceinline__ void split_w8(f32x4 a, f32x4 b, int e, f16x8 &hi, f16
 // DBG is a diagnostic knob (WAGG_SPLIT_DBG env, read by the -DWAGG_DIAG build only; tools/split_ablate.sh): bit0 = no W loads
 // and no X DMA in the k-loop, bit2 = no per-tile wait or barrier, bit3 = no split arithmetic (the raw register pairs go to
 // the MFMAs as they are: same loads, same waits).  Results are wrong with any bit set.
+//
+// IMG: Wp is the plan's f16 image of W (dense_split_image_kernel below): the tile layout of the packed fp32 W, but the four
+// 16-byte slots a lane loads hold wh0, wl0, wh1, wl1 -- the bits split_w8 makes of them -- so the loaded registers ARE the
+// operands and the split (and the column scales) leave the k-loop.  The operands are then live for the whole tile while
+// the loads of tile t + 1 are in flight, so the loads go into a second set of four registers and the tile loop is written
+// out twice with the sets exchanged (no copies).  Same loads at the same place, same waits, same MFMA order: the result is
+// that of the IMG = false kernel, bit for bit.
 
 // buffer descriptor of `bytes` bytes at a wave-uniform address (read back from lane 0, so that the compiler keeps the
 // descriptor in SGPRs instead of looping over the lanes' copies)
@@ -81,7 +88,11 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t split_tile_rsrc(const char *ba
     return __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void *>(u), (short)0, bytes, 0x00020000);
 }
 
-template <int MT, int DBG = 0>
+// byte offsets of lane (lr, kq)'s two fragments inside a 2-KiB block of sixteen tile rows
+__device__ __forceinline__ unsigned split_frag0(int lr, int kq) { return (lr * 8 + (kq ^ (lr >> 1))) * 16; }        // piece kq
+__device__ __forceinline__ unsigned split_frag1(int lr, int kq) { return (lr * 8 + ((kq ^ (lr >> 1)) ^ 4)) * 16; }  // piece kq + 4
+
+template <int MT, int DBG = 0, bool IMG = false>
 __global__ __launch_bounds__(D_THREADS, 2) void dense_split_kernel(
     const f16x8 *__restrict__ Xp, const float *__restrict__ Wp, const float *__restrict__ wmax, int n_kt, int n_nt, int n_mb,
     int S, int kt_per_slice, float *__restrict__ slabs) {
@@ -109,13 +120,12 @@ __global__ __launch_bounds__(D_THREADS, 2) void dense_split_kernel(
     const int kt1 = kt0 + kt_per_slice < n_kt ? kt0 + kt_per_slice : n_kt;
     const int ntiles = kt1 > kt0 ? kt1 - kt0 : 0;
     const int64_t w_first = (int64_t)nt * n_kt + kt0;
-    // scales of this lane's two columns (the plan pads wmax to whole column tiles with zeros)
-    const int ew0 = split_exp(wmax[nt * D_BN + wave * 32 + lr]);
-    const int ew1 = split_exp(wmax[nt * D_BN + wave * 32 + 16 + lr]);
+    // scales of this lane's two columns (the plan pads wmax to whole column tiles with zeros); the image holds scaled parts
+    const int ew0 = IMG ? 0 : split_exp(wmax[nt * D_BN + wave * 32 + lr]);
+    const int ew1 = IMG ? 0 : split_exp(wmax[nt * D_BN + wave * 32 + 16 + lr]);
 
-    const int f = lr >> 1;
-    const unsigned frag0 = (lr * 8 + (kq ^ f)) * 16;       // piece kq: W k = 4 kq + c, X high parts
-    const unsigned frag1 = (lr * 8 + ((kq ^ f) ^ 4)) * 16; // piece kq + 4: W k = 16 + 4 kq + c, X low parts
+    const unsigned frag0 = split_frag0(lr, kq);            // piece kq: W k = 4 kq + c, X high parts
+    const unsigned frag1 = split_frag1(lr, kq);            // piece kq + 4: W k = 16 + 4 kq + c, X low parts
     // buffer descriptors of one tile (wave-uniform: the tile's X image, the tile's W image) and 32-bit per-lane offsets; the
     // range check holds every W load (and the lane part of every X piece) inside its tile
     const char *xslice = reinterpret_cast<const char *>(Xp) + ((int64_t)mb * n_kt + kt0) * XT4;
@@ -139,13 +149,13 @@ __global__ __launch_bounds__(D_THREADS, 2) void dense_split_kernel(
         if constexpr (NXP > 4) WAGG_DMA_X(NXP > 4 ? 4 : 0, xr_, buf);                             \
         if constexpr (NXP > 5) WAGG_DMA_X(NXP > 5 ? 5 : 0, xr_, buf);                             \
     } while (0)
-#define WAGG_LOAD_W(tile)                                                                         \
+#define WAGG_LOAD_W(tile, D00, D01, D10, D11)                                                     \
     do {                                                                                          \
         const auto wr_ = WAGG_RSRC(wslice + (int64_t)(tile) * D_WTB, D_WTB);                      \
-        b00 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(wr_, wfrag0, 0, 0));        \
-        b01 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(wr_, wfrag1, 0, 0));        \
-        b10 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(wr_, wfrag0 + 2048, 0, 0)); \
-        b11 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(wr_, wfrag1 + 2048, 0, 0)); \
+        D00 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(wr_, wfrag0, 0, 0));        \
+        D01 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(wr_, wfrag1, 0, 0));        \
+        D10 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(wr_, wfrag0 + 2048, 0, 0)); \
+        D11 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(wr_, wfrag1 + 2048, 0, 0)); \
     } while (0)
 
     f32x4 acc[MT][2];
@@ -155,17 +165,18 @@ __global__ __launch_bounds__(D_THREADS, 2) void dense_split_kernel(
     f32x4 b00, b01, b10, b11;
     if (ntiles > 0) {
         const int t1 = ntiles > 1 ? 1 : 0;
-        WAGG_LOAD_W(0);
+        WAGG_LOAD_W(0, b00, b01, b10, b11);
         WAGG_DMA_XALL(0, 0);
         WAGG_DMA_XALL(t1, 1);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
     }
 
-    // DBG bit3: no split arithmetic, the raw register pairs go to the MFMAs as they are (same loads, same waits)
+    // DBG bit3: no split arithmetic, the raw register pairs go to the MFMAs as they are (same loads, same waits); IMG: the
+    // registers hold the parts already
 #define WAGG_SPLIT(A, B, E, HI, LO)                                                               \
     do {                                                                                          \
-        if constexpr (DBG & 8) { HI = __builtin_bit_cast(f16x8, A); LO = __builtin_bit_cast(f16x8, B); } \
+        if constexpr (IMG || (DBG & 8)) { HI = __builtin_bit_cast(f16x8, A); LO = __builtin_bit_cast(f16x8, B); } \
         else split_w8(A, B, E, HI, LO);                                                           \
     } while (0)
 #define WAGG_MFMA16(RB, CB, A, B) acc[RB][CB] = __builtin_amdgcn_mfma_f32_16x16x32_f16(A, B, acc[RB][CB], 0, 0, 0)
@@ -211,55 +222,67 @@ __global__ __launch_bounds__(D_THREADS, 2) void dense_split_kernel(
         }                                                                                         \
     } while (0)
 
+    // One tile: C00 C01 C10 C11 hold its W pieces (IMG: its operands), N00 ... N11 take those of tile t + 1 (IMG = false: the
+    // same registers, free once the pieces have been split)
+#define WAGG_TILE(tile, C00, C01, C10, C11, N00, N01, N10, N11)                                                               \
+    do {                                                                                                                      \
+        const char *img = lds + bcur * XT4;                                                                                   \
+        const int bfar = bcur == 0 ? 2 : bcur - 1; /* buffer of tile t + 2 (read by tile t - 1) */                            \
+        const int tnext = (tile) + 1 < ntiles ? (tile) + 1 : ntiles - 1; /* last tiles: harmless re-loads inside the slice */ \
+        const int tfar = (tile) + 2 < ntiles ? (tile) + 2 : ntiles - 1;                                                       \
+        const auto xfar = WAGG_RSRC(xslice + (int64_t)tfar * XT4, XT4);                                                       \
+        f16x8 wh0, wl0, wh1, wl1, aAh, aAl, aBh, aBl;                                                                         \
+        /* row blocks 0 and 1, column block 0, with column block 1's split between the MFMAs; then W of tile t + 1 */         \
+        WAGG_READ_A(aAh, aAl, 0);                                                                                             \
+        WAGG_SPLIT(C00, C01, ew0, wh0, wl0);                                                                                  \
+        if constexpr (MT > 1) WAGG_READ_A(aBh, aBl, MT > 1 ? 1 : 0);                                                          \
+        __builtin_amdgcn_sched_barrier(0);                                                                                    \
+        WAGG_MFMA16(0, 0, aAh, wl0);                                                                                          \
+        WAGG_MFMA16(0, 0, aAl, wh0);                                                                                          \
+        WAGG_MFMA16(0, 0, aAh, wh0);                                                                                          \
+        if constexpr (MT > 1) {                                                                                               \
+            WAGG_MFMA16(MT > 1 ? 1 : 0, 0, aBh, wl0);                                                                         \
+            WAGG_MFMA16(MT > 1 ? 1 : 0, 0, aBl, wh0);                                                                         \
+            WAGG_MFMA16(MT > 1 ? 1 : 0, 0, aBh, wh0);                                                                         \
+        }                                                                                                                     \
+        WAGG_SPLIT(C10, C11, ew1, wh1, wl1);                                                                                  \
+        __builtin_amdgcn_sched_barrier(0);                                                                                    \
+        if constexpr (!(DBG & 1)) WAGG_LOAD_W(tnext, N00, N01, N10, N11);                                                     \
+        __builtin_amdgcn_sched_barrier(0);                                                                                    \
+        WAGG_MFMA16(0, 1, aAh, wl1);                                                                                          \
+        WAGG_MFMA16(0, 1, aAl, wh1);                                                                                          \
+        WAGG_MFMA16(0, 1, aAh, wh1);                                                                                          \
+        __builtin_amdgcn_sched_barrier(0);                                                                                    \
+        if constexpr (MT > 2) WAGG_READ_A(aAh, aAl, MT > 2 ? 2 : 0);                                                          \
+        __builtin_amdgcn_sched_barrier(0);                                                                                    \
+        if constexpr (MT > 1) {                                                                                               \
+            WAGG_MFMA16(MT > 1 ? 1 : 0, 1, aBh, wl1);                                                                         \
+            WAGG_MFMA16(MT > 1 ? 1 : 0, 1, aBl, wh1);                                                                         \
+            WAGG_MFMA16(MT > 1 ? 1 : 0, 1, aBh, wh1);                                                                         \
+        }                                                                                                                     \
+        __builtin_amdgcn_sched_barrier(0);                                                                                    \
+        WAGG_DMA_BLOCK(0); WAGG_DMA_BLOCK(1);                                                                                 \
+        WAGG_BLOCK(2); WAGG_BLOCK(3); WAGG_BLOCK(4); WAGG_BLOCK(5);                                                           \
+        WAGG_BLOCK(6); WAGG_BLOCK(7); WAGG_BLOCK(8); WAGG_BLOCK(9); WAGG_BLOCK(10); WAGG_BLOCK(11);                           \
+        WAGG_BLOCK(12); WAGG_BLOCK(13); WAGG_BLOCK(14); WAGG_BLOCK(15); WAGG_BLOCK(16); WAGG_BLOCK(17);                       \
+        WAGG_BLOCK(18); WAGG_BLOCK(19); WAGG_BLOCK(20); WAGG_BLOCK(21); WAGG_BLOCK(22);                                       \
+        static_assert(MT <= 23, "row blocks are written out up to 22");                                                       \
+        __builtin_amdgcn_sched_barrier(0);                                                                                    \
+        if constexpr (!(DBG & 4)) {                                                                                           \
+            __builtin_amdgcn_s_waitcnt(WAIT_TILE);                                                                            \
+            __builtin_amdgcn_s_barrier();                                                                                     \
+        }                                                                                                                     \
+        bcur = bcur == 2 ? 0 : bcur + 1;                                                                                      \
+    } while (0)
     int bcur = 0;                                              // ring buffer of tile t
-    for (int tile = 0; tile < ntiles; ++tile) {
-        const char *img = lds + bcur * XT4;
-        const int bfar = bcur == 0 ? 2 : bcur - 1;                // buffer of tile t + 2 (read by tile t - 1)
-        const int tnext = tile + 1 < ntiles ? tile + 1 : ntiles - 1;   // last tiles: harmless re-loads inside the slice
-        const int tfar = tile + 2 < ntiles ? tile + 2 : ntiles - 1;
-        const auto xfar = WAGG_RSRC(xslice + (int64_t)tfar * XT4, XT4);
-        f16x8 wh0, wl0, wh1, wl1, aAh, aAl, aBh, aBl;
-        // row blocks 0 and 1, column block 0, with column block 1's split between the MFMAs; then W of tile t + 1
-        WAGG_READ_A(aAh, aAl, 0);
-        WAGG_SPLIT(b00, b01, ew0, wh0, wl0);
-        if constexpr (MT > 1) WAGG_READ_A(aBh, aBl, MT > 1 ? 1 : 0);
-        __builtin_amdgcn_sched_barrier(0);
-        WAGG_MFMA16(0, 0, aAh, wl0);
-        WAGG_MFMA16(0, 0, aAl, wh0);
-        WAGG_MFMA16(0, 0, aAh, wh0);
-        if constexpr (MT > 1) {
-            WAGG_MFMA16(MT > 1 ? 1 : 0, 0, aBh, wl0);
-            WAGG_MFMA16(MT > 1 ? 1 : 0, 0, aBl, wh0);
-            WAGG_MFMA16(MT > 1 ? 1 : 0, 0, aBh, wh0);
+    if constexpr (IMG) {
+        f32x4 d00, d01, d10, d11;                                 // the second operand set
+        for (int tile = 0; tile < ntiles; tile += 2) {
+            WAGG_TILE(tile, b00, b01, b10, b11, d00, d01, d10, d11);
+            if (tile + 1 < ntiles) WAGG_TILE(tile + 1, d00, d01, d10, d11, b00, b01, b10, b11);
         }
-        WAGG_SPLIT(b10, b11, ew1, wh1, wl1);
-        __builtin_amdgcn_sched_barrier(0);
-        if constexpr (!(DBG & 1)) WAGG_LOAD_W(tnext);
-        __builtin_amdgcn_sched_barrier(0);
-        WAGG_MFMA16(0, 1, aAh, wl1);
-        WAGG_MFMA16(0, 1, aAl, wh1);
-        WAGG_MFMA16(0, 1, aAh, wh1);
-        __builtin_amdgcn_sched_barrier(0);
-        if constexpr (MT > 2) WAGG_READ_A(aAh, aAl, MT > 2 ? 2 : 0);
-        __builtin_amdgcn_sched_barrier(0);
-        if constexpr (MT > 1) {
-            WAGG_MFMA16(MT > 1 ? 1 : 0, 1, aBh, wl1);
-            WAGG_MFMA16(MT > 1 ? 1 : 0, 1, aBl, wh1);
-            WAGG_MFMA16(MT > 1 ? 1 : 0, 1, aBh, wh1);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        WAGG_DMA_BLOCK(0); WAGG_DMA_BLOCK(1);
-        WAGG_BLOCK(2); WAGG_BLOCK(3); WAGG_BLOCK(4); WAGG_BLOCK(5);
-        WAGG_BLOCK(6); WAGG_BLOCK(7); WAGG_BLOCK(8); WAGG_BLOCK(9); WAGG_BLOCK(10); WAGG_BLOCK(11);
-        WAGG_BLOCK(12); WAGG_BLOCK(13); WAGG_BLOCK(14); WAGG_BLOCK(15); WAGG_BLOCK(16); WAGG_BLOCK(17);
-        WAGG_BLOCK(18); WAGG_BLOCK(19); WAGG_BLOCK(20); WAGG_BLOCK(21); WAGG_BLOCK(22);
-        static_assert(MT <= 23, "row blocks are written out up to 22");
-        __builtin_amdgcn_sched_barrier(0);
-        if constexpr (!(DBG & 4)) {
-            __builtin_amdgcn_s_waitcnt(WAIT_TILE);
-            __builtin_amdgcn_s_barrier();
-        }
-        bcur = bcur == 2 ? 0 : bcur + 1;
+    } else {
+        for (int tile = 0; tile < ntiles; ++tile) WAGG_TILE(tile, b00, b01, b10, b11, b00, b01, b10, b11);
     }
     // the re-loads behind the last tile land before the wave ends
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -284,6 +307,34 @@ __global__ __launch_bounds__(D_THREADS, 2) void dense_split_kernel(
 #undef WAGG_READ_A
 #undef WAGG_BLOCK_
 #undef WAGG_BLOCK
+#undef WAGG_TILE
+}
+
+// The f16 image of a packed fp32 W (plan time; what dense_split_kernel<MT, DBG, true> loads): a workgroup takes a tile as
+// the split kernel's does -- lane (lr, kq) of wave w reads its four pieces at the kernel's offsets, splits them with
+// split_w8 at the scales of its two columns and stores wh0, wl0, wh1, wl1 at the same four offsets of the image tile.  The
+// eight waves' offsets cover every 16-byte slot of a tile once.
+__global__ __launch_bounds__(D_THREADS) void dense_split_image_kernel(const float *__restrict__ Wp, const float *__restrict__ wmax,
+                                                                      int n_kt, int64_t n_tiles, float *__restrict__ image) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int lr = lane & 15, kq = lane >> 4;
+    const unsigned wfrag0 = wave * 4096 + split_frag0(lr, kq), wfrag1 = wave * 4096 + split_frag1(lr, kq);
+    for (int64_t t = blockIdx.x; t < n_tiles; t += gridDim.x) {
+        const int64_t nt = t / n_kt;
+        const int ew0 = split_exp(wmax[nt * D_BN + wave * 32 + lr]);
+        const int ew1 = split_exp(wmax[nt * D_BN + wave * 32 + 16 + lr]);
+        const char *src = reinterpret_cast<const char *>(Wp) + t * D_WTB;
+        char *dst = reinterpret_cast<char *>(image) + t * D_WTB;
+        const f32x4 b00 = *reinterpret_cast<const f32x4 *>(src + wfrag0), b01 = *reinterpret_cast<const f32x4 *>(src + wfrag1);
+        const f32x4 b10 = *reinterpret_cast<const f32x4 *>(src + wfrag0 + 2048), b11 = *reinterpret_cast<const f32x4 *>(src + wfrag1 + 2048);
+        f16x8 wh0, wl0, wh1, wl1;
+        split_w8(b00, b01, ew0, wh0, wl0);
+        split_w8(b10, b11, ew1, wh1, wl1);
+        *reinterpret_cast<f16x8 *>(dst + wfrag0) = wh0;
+        *reinterpret_cast<f16x8 *>(dst + wfrag1) = wl0;
+        *reinterpret_cast<f16x8 *>(dst + wfrag0 + 2048) = wh1;
+        *reinterpret_cast<f16x8 *>(dst + wfrag1 + 2048) = wl1;
+    }
 }
 
 // row maxima of the transformed X (NaN counts as 0, +-inf is left out): rowmax[t] (zeroed by the caller) as float bits,

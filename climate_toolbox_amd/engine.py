@@ -537,6 +537,14 @@ class DensePlan:
         _lib.check(_lib.load().wagg_dense_clone(self._h, int(device), C.byref(h)), "wagg_dense_clone")
         return type(self)(h, self.G, self.R, int(device))
 
+    def read_w(self, image=False):
+        """The stored tiles as bytes, as they lie on the device (``wagg_dense_read_w``): the packed W, or with ``image`` the f16
+        high / low image of a full-form fp32 plan (``info["w_image_bytes"]`` says whether one is held).  For layout tests."""
+        fn = _lib.load().wagg_dense_read_w
+        buf = np.empty(self.info["w_bytes"], dtype=np.uint8)
+        _lib.check(fn(self._h, 1 if image else 0, buf.ctypes.data_as(C.c_void_p), buf.nbytes), "wagg_dense_read_w")
+        return buf
+
     def close(self):
         for r in getattr(self, "_replicas", {}).values():
             r.close()

@@ -460,6 +460,10 @@ typedef struct wagg_dense_info {
                                       every (region block, chunk) item): = nnz for evenly spread weights */
     int32_t one_pass_sort, reserved0; /* 1 = the table was put in key order by the one-pass chunk partition (CSR, ascending
                                       columns, nothing dropped), 0 = by the general radix sort */
+    int64_t w_image_bytes;         /* full-form fp32 plans: bytes of the f16 high / low image of W that the split apply reads
+                                      (= w_bytes, held while the device had room for it at plan time; a clone decides anew on
+                                      its own device); 0 = no image: the apply splits W in registers -- same results, bit for
+                                      bit.  Applies of more than one row block (T > 368) split in registers either way */
 } wagg_dense_info;
 int wagg_dense_get_info(const wagg_dense *d, wagg_dense_info *info);
 int wagg_dense_get_info_sized(const wagg_dense *d, void *info, uint64_t size);   /* see "structs that cross the boundary by layout" */
@@ -479,6 +483,10 @@ int64_t wagg_scratch_bytes(void);  /* device bytes kept right now, all devices *
 int wagg_dense_clone(const wagg_dense *src, int device, wagg_dense **out);
 int wagg_dense_destroy(wagg_dense *d);
 int wagg_dense_get_den(const wagg_dense *d, double *den_host /* R values */);
+/* Diagnostic entry (layout tests; a library built from an older header lacks it): the stored tiles as they lie on the device, to
+ * a host buffer of exactly w_bytes -- image = 0 the packed W, 1 the f16 high / low image of a full-form fp32 plan (WAGG_EINVAL
+ * when the plan holds none).  Not for entry-list plans. */
+int wagg_dense_read_w(const wagg_dense *d, int image, void *host, uint64_t bytes);
 /* out[t, r] = sum_g nan0(X[t,g]) * W[g,r] / den[r], fp32 MFMA (v_mfma_f32_16x16x4_f32).
  * ksplit = 0 picks the k-slice count; otherwise a multiple of 8.  The plan owns the packed copy of
  * X and the partial-sum slabs of an apply (hence the non-const handle): applies on ONE dense plan
