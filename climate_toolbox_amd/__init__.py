@@ -1,7 +1,7 @@
 """MI355X-native weighted grid->region aggregation engine: a drop-in for the aggregation path of
 ClimateImpactLab/climate_toolbox (``climate_toolbox.aggregations``).  See DESIGN.md."""
 
-__version__ = "0.11.0"
+__version__ = "0.12.0"
 
 from .aggregations import (  # noqa: F401
     weighted_aggregate_grid_to_regions,
@@ -35,6 +35,7 @@ from .transformations import (  # noqa: F401  (tas_poly fused into 
     snyder_edd,
     snyder_gdd,
     snyder_edd_aggregate,
+    snyder_exposure_aggregate,
     tas_bins_aggregate,
     tas_hinge_aggregate,
     tas_rcspline_aggregate,

@@ -1,14 +1,15 @@
 // What the row-list reductions hold in common (wagg_period.hip, wagg_season.hip, wagg_edd_ladder.hip, wagg_bins.hip,
-// wagg_hinge.hip): a lane owns one 16-byte piece of a row (VEC = 1 for rows that are not 16-byte aligned) and walks its
-// period's row list; the grid is column block x period x part [x group of thresholds / bins / knots], flat; when that cannot
-// fill the device a period's list is cut into `split` consecutive parts, every part writes fp64 partial sums to the caller's
-// workspace [s][plane][p][j] and rowlist_finish adds them in part order -- no atomics on a sum.  The five families promise each
-// other bit equality (an all-year season = the period sum, every ladder plane = the four-plane kernels' plane, a one-knot hinge
-// call = the plane of the many-knot call, counts that do not depend on the split): that rests on the split rule, the part
-// arithmetic and the finish order being the ones below for all of them.  The host pieces are defined once, in wagg_period.hip;
-// the three grouped families (ladder, bins, hinge) also share their whole host sequence, grouped_reduce below.  The frame of
-// their three kernel bodies (window read, rows in flight, masks, loads, status word) deliberately stays three copies: behind
-// shared inline functions hipcc allocates other registers (docs/HISTORY.md, "one shared core").
+// wagg_hinge.hip, wagg_exposure.hip): a lane owns one 16-byte piece of a row (VEC = 1 for rows that are not 16-byte aligned)
+// and walks its period's row list; the grid is column block x period x part [x group of thresholds / bins / knots], flat; when
+// that cannot fill the device a period's list is cut into `split` consecutive parts, every part writes fp64 partial sums to the
+// caller's workspace [s][plane][p][j] and rowlist_finish adds them in part order -- no atomics on a sum. The five families
+// before the exposure bins promise each other bit equality (an all-year season = the period sum, every ladder plane = the
+// four-plane kernels' plane, a one-knot hinge call = the plane of the many-knot call, counts that do not depend on the split):
+// that rests on the split rule, the part arithmetic and the finish order being the ones below for all of them.  The host pieces
+// are defined once, in wagg_period.hip; the four grouped families (ladder, bins, hinge, exposure) also share their whole host
+// sequence, grouped_reduce below.  The frame of their kernel bodies (window read, rows in flight, masks, loads, status word)
+// deliberately stays a copy in each: behind shared inline functions hipcc allocates other registers (docs/HISTORY.md, "one
+// shared core").
 #pragma once
 #include "wagg_common.h"
 
@@ -120,7 +121,7 @@ int rowlist_check_rows(const int32_t *row_begin, int32_t P, const int32_t *rows,
 // how many consecutive parts a period's row list is cut into so that the grid fills the device.  Threshold groups do not
 // enter: they multiply the blocks, but the parts decide the order of the fp64 additions.
 int rowlist_split(int64_t n, int64_t P, int64_t n_rows, int vec);
-int64_t rowlist_work_bytes(int64_t n, int64_t P, int64_t n_rows, int planes);       // behind the three *_work_bytes
+int64_t rowlist_work_bytes(int64_t n, int64_t P, int64_t n_rows, int planes);       // behind the grouped families' *_work_bytes
 
 // sh.T .. sh.P and sh.aux are the caller's; fills sh.n_colblk and sh.split (the rule's, cut to what `work` holds) and says
 // whether rows are read in 16-byte pieces (X2 = NULL: one field).  False: n_colblk x P x split x n_grp is too many blocks.
@@ -131,8 +132,8 @@ bool rowlist_geometry(RowlistShape &sh, bool &wide, int elem_bytes, const void *
 template <typename T>
 int rowlist_finish(const double *work, int split, int planes, int64_t P, int64_t n, T *out, int64_t ldo, int64_t pstride, hipStream_t st);
 
-// ---- the grouped families (wagg_edd_ladder.hip, wagg_bins.hip, wagg_hinge.hip) ---------------------------------------------
-// what their entry points take alike (X2: the ladder's tasmax; NULL in the one-field families)
+// ---- the grouped families (wagg_edd_ladder.hip, wagg_bins.hip, wagg_hinge.hip, wagg_exposure.hip) ---------------------------
+// what their entry points take alike (X2: the ladder's and the exposure bins' tasmax; NULL in the one-field families)
 template <typename T> struct GroupedArgs {
     const T *X, *X2;
     int64_t Ttot, n, ldx;
@@ -156,7 +157,7 @@ struct GroupedFamily {
     int n_fields, group;
 };
 
-// The host sequence of a grouped entry point, in the one order all three have always had.  check(): the family's checks of its
+// The host sequence of a grouped entry point, in the one order all of them have always had.  check(): the family's checks of its
 // own parameter list (WAGG_OK, or the error set and its code); planes: the planes of `out`, read only behind check();
 // launch(sh, wide, st): builds the family's transform and launches through grouped_launch.
 template <typename T, typename Check, typename Launch>

@@ -866,9 +866,9 @@ def _season_vector(a, length, what, device):
 
 
 class _RowlistCall:
-    """What the five row-list calls -- :func:`period_reduce`, :func:`season_reduce` and, through :func:`_grouped_reduce`,
-    :func:`edd_ladder_reduce`, :func:`bin_days_reduce` and :func:`hinge_reduce` -- do alike around their library call, in the
-    order they do it: the row lists (and, with ``season = (doy, windows)``, those two vectors) as int32 CUDA tensors and ``P``;
+    """What the six row-list calls -- :func:`period_reduce`, :func:`season_reduce` and, through :func:`_grouped_reduce`,
+    :func:`edd_ladder_reduce`, :func:`exposure_reduce`, :func:`bin_days_reduce` and :func:`hinge_reduce` -- do alike around
+    their library call, in the order they do it: the row lists (and, with ``season = (doy, windows)``, those two vectors) as int32 CUDA tensors and ``P``;
     then ``out``, ``status`` and the workspace; at the end what must outlive the kernels on the caller's stream."""
 
     def __init__(self, X, row_begin, rows, checked, season=None):
@@ -988,8 +988,8 @@ def season_reduce(X, row_begin, rows, doy, windows, X2=None, poly=None, edd=None
 
 def _grouped_reduce(name, fields, row_begin, rows, doy, windows, checked, offset, middle, planes, work_bytes, out, status, workspace,
                     stream):
-    """What :func:`edd_ladder_reduce`, :func:`bin_days_reduce` and :func:`hinge_reduce` do alike behind their own validation: the
-    doy / windows pairing, the :class:`_RowlistCall`, ``out`` / ``status`` / workspace, and the library call ``name`` + ``_f32``
+    """What :func:`edd_ladder_reduce`, :func:`exposure_reduce`, :func:`bin_days_reduce` and :func:`hinge_reduce` do alike behind
+    their own validation: the doy / windows pairing, the :class:`_RowlistCall`, ``out`` / ``status`` / workspace, and the library call ``name`` + ``_f32``
     or ``_f64`` by the dtype of ``fields`` (one checked (T, n) tensor, or tasmin and tasmax) -- the fields and the arguments
     every grouped entry point begins with (sizes, lists, season, ``offset``), the family's ``middle`` ones, and the ones every
     one ends with (flags, ``out`` and its strides, status, workspace, stream).  ``work_bytes(L, n, P, n_rows, planes)``: the
@@ -1030,6 +1030,32 @@ def edd_ladder_reduce(tasmin, tasmax, row_begin, rows, offset, thresholds, doy=N
     return _grouped_reduce("wagg_edd_ladder_reduce", (X, X2), row_begin, rows, doy, windows, checked, offset,
                            (_np_ptr(thr, C.c_double), len(thr)), len(thr),
                            lambda L, *a: L.wagg_edd_ladder_work_bytes(*a), out, status, workspace, stream)
+
+
+def exposure_reduce(tasmin, tasmax, row_begin, rows, offset, edges, doy=None, windows=None, checked=False, out=None, status=None,
+                    stream=None, workspace=True):
+    """The time a day's sinusoidal temperature curve spends in each bin, summed per period, in ONE launch
+    (``wagg_exposure_reduce_*``): ``out[k, p, j]`` sums ``A(edges[k]) - A(edges[k + 1])`` over the rows ``t`` of period ``p`` on
+    which cell ``j`` is in season, ``A(e)`` being the fraction of the day the single sine through ``tasmin[t, j] + offset`` and
+    ``tasmax[t, j] + offset`` (:func:`edd_ladder_reduce`'s model; ``A = -d EDD / de``) lies above ``e``: 0 for a NaN in either
+    field, exactly 1 where tasmin is not below ``e``, exactly 0 where tasmax is not above it, ``acos(z) / pi`` between.
+    ``tasmin`` / ``tasmax``: (T, n) CUDA tensors of one dtype and row stride; ``edges``: 2 .. ``_lib.EXPOSURE_EDGES_MAX``
+    strictly ascending numbers, ``-inf`` allowed first and ``+inf`` last (the kernel takes the bins ``_lib.EXPOSURE_GROUP`` at a
+    time), converted to the element type; everything else as for :func:`edd_ladder_reduce`.  Returns ``(bins, status)``: the
+    (n_bins, P, n) tensor in days and the status word (bit 0: an in-season value of either field was +-inf)."""
+    X = _check_X(tasmin, "TG")
+    X2 = _check_X(tasmax, "TG")
+    if X2.shape != X.shape or X2.dtype != X.dtype or _ld(X2) != _ld(X) or X2.device != X.device:
+        raise ValueError("tasmin and tasmax must have the same shape, dtype, row stride and device")
+    e = np.ascontiguousarray(np.atleast_1d(edges), dtype=np.float64)
+    if e.ndim != 1 or not 2 <= len(e) <= _lib.EXPOSURE_EDGES_MAX:
+        raise ValueError("2..%d bin edges per call, got %s" % (_lib.EXPOSURE_EDGES_MAX, e.shape))
+    if np.isnan(e).any() or not (e[1:] > e[:-1]).all():
+        raise ValueError("bin edges must ascend strictly and hold no NaN, got %r" % (e.tolist(),))
+    return _grouped_reduce("wagg_exposure_reduce", (X, X2), row_begin, rows, doy, windows, checked, offset,
+                           (_np_ptr(e, C.c_double), len(e)), len(e) - 1,
+                           lambda L, n, P, n_rows, planes: L.wagg_exposure_work_bytes(n, P, n_rows, planes + 1),      # (it takes n_edges)
+                           out, status, workspace, stream)
 
 
 def bin_thresholds(edges, offset, dtype):

@@ -34,6 +34,7 @@ from . import aggregations as _agg, engine as _engine, minixr
 from ._labels import _exact_index
 from ._layout import _flatten_for_device, _is_device_tensor, _result_dims, _spatial_layout, _to_device
 from ._lib import BIN_EDGES_MAX as _BIN_EDGES_MAX, EDD_LADDER_MAX as _EDD_LADDER_MAX, HINGE_MAX as _HINGE_MAX, SEASON_INVERT, SEASON_NULL
+from ._lib import EXPOSURE_EDGES_MAX as _EXPOSURE_EDGES_MAX
 from ._plans import _drop_plan, _plan_for
 from ._prepared import PreparedWeights
 
@@ -363,8 +364,8 @@ def _plain_variable(ds, variable, what):
 
 def _grouped_totals(ds, variable, aggwt, agglev, weights, backup_aggwt, lists, P, season, grid, time_values, cells, name, of, rule,
                     launches):
-    """The sum-first route of the grouped statistics (ladder, bins, hinges): every launch sums its planes per period first, then
-    one apply per launch contracts its planes * P rows on whatever plan serves the table.  ``name`` / ``of``: the statistic in
+    """The sum-first route of the grouped statistics (ladder, bins, hinges, exposure bins): every launch sums its planes per period
+    first, then one apply per launch contracts its planes * P rows on whatever plan serves the table.  ``name`` / ``of``: the statistic in
     the messages ("bin count" / "bins"); ``rule(ds, variable, what)``: ``(second field or None, offset)`` of a variable the
     statistic takes, ValueError for any other; ``launches``: an iterable, consumed as the launches run, of
     ``reduce(Xd, Hd, rb, rw, offset, **season)`` -> ``(planes, status)``, each one engine call on its cut of the parameter
@@ -426,6 +427,19 @@ def _bin_totals(ds, variable, aggwt, agglev, weights, backup_aggwt, lists, P, ed
 
     return _grouped_totals(ds, variable, aggwt, agglev, weights, backup_aggwt, lists, P, season, grid, time_values, cells, "bin count",
                            "bins", _plain_variable, launches())
+
+
+def _exposure_totals(ds, variable, aggwt, agglev, weights, backup_aggwt, lists, P, edges, season, grid, time_values, cells="all"):
+    """Period totals of the time the daily sinusoid of ``variable`` (a degree-day variable: tasmin with its tasmax; its own terms
+    are ignored) spends in every bin ``[edges[k], edges[k + 1])`` (``wagg_exposure_reduce_*``, up to 64 bins a launch) through
+    :func:`_grouped_totals`; ``stack`` is the (n_bins, P | R, R | P) results in bin order."""
+    def launches():
+        for k0 in range(0, len(edges) - 1, _EXPOSURE_EDGES_MAX - 1):             # (consecutive launches share an edge)
+            part = [float(e) for e in edges[k0:k0 + _EXPOSURE_EDGES_MAX]]
+            yield lambda X, H, rb, rw, offset, **kw: _engine.exposure_reduce(X, H, rb, rw, offset, part, **kw)
+
+    return _grouped_totals(ds, variable, aggwt, agglev, weights, backup_aggwt, lists, P, season, grid, time_values, cells,
+                           "exposure total", "exposure bins", _degree_day_variable, launches())
 
 
 def _hinge_totals(ds, variable, aggwt, agglev, weights, backup_aggwt, lists, P, knots, power, side, tail, season, grid, time_values,

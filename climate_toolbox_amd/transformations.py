@@ -23,7 +23,8 @@ import numpy as np
 from . import minixr
 from . import aggregations as _agg
 
-__all__ = ["tas_poly", "tas_poly_aggregate", "snyder_edd", "snyder_gdd", "snyder_edd_aggregate", "tas_bins_aggregate",
+__all__ = ["tas_poly", "tas_poly_aggregate", "snyder_edd", "snyder_gdd", "snyder_edd_aggregate", "snyder_exposure_aggregate",
+           "tas_bins_aggregate",
            "tas_hinge_aggregate", "tas_rcspline_aggregate",
            "validate_edd_snyder_agriculture", "ordinal", "remove_leap_days", "convert_kelvin_to_celsius"]
 
@@ -332,6 +333,51 @@ def snyder_edd_aggregate(ds, thresholds, aggwt, agglev, weights, tasmin="tasmin"
             res = np.stack(planes)
     out = _agg._as_dataset({varname: res}, ("refTemp",) + tuple(rdims), dict(coords, refTemp=thr), was_xr)
     out[varname].attrs["units"] = units
+    return out
+
+
+def snyder_exposure_aggregate(ds, edges, aggwt, agglev, weights, tasmin="tasmin", tasmax="tasmax", varname="exposure",
+                              backup_aggwt="areawt", period="year", season=None, cells="all"):
+    """The time a day's sinusoidal temperature curve spends in each bin ``[edges[k], edges[k + 1])`` -- the Schlenker-Roberts
+    exposure bins -- summed per period (and growing season) and aggregated to regions.  The curve is the single sine through
+    ``ds[tasmin]`` / ``ds[tasmax]`` that :func:`snyder_edd` integrates (same checks: equal units, tasmin <= tasmax everywhere;
+    degrees C, or Kelvin fields shifted by ``convert_kelvin_to_celsius``), and the fraction of a day above ``e`` is the
+    derivative of the degree-day ladder, ``A(e) = -d EDD / de``; bin ``k`` of a day is ``A(edges[k]) - A(edges[k + 1])``.
+    Where :func:`tas_bins_aggregate` puts a 22-38 C day wholly into the bin of its mean, this call spreads it over every bin
+    its curve passes through.  One launch per 64 bins (``wagg_exposure_reduce_*``) instead of two passes over the grid per edge.
+
+    edges    as for :func:`tas_bins_aggregate`: at least two strictly ascending numbers, ``-inf`` allowed first and ``+inf``
+             last, else ValueError; converted to the element type.  A day with NaN in either field is in no bin; a counted
+             +-inf raises ValueError.
+    period   "year", "month" or a label per day; required (None is ValueError: an exposure total is a sum over days).
+    season, cells   exactly as in :func:`snyder_edd_aggregate`; "referenced" packs both fields.
+
+    Returns one Dataset with the variable ``varname`` of dims ``("bin", "period", agglev)`` (the last two in the order the
+    period call gives them), the coordinate ``bin`` = the lower edges as float64, ``attrs["units"] = "days"`` and
+    ``attrs["bin_edges"]`` as :func:`tas_bins_aggregate` writes them; ``results_on_device()`` is honoured."""
+    e = _bin_edges(edges)
+    if period is None:
+        raise ValueError("snyder_exposure_aggregate needs period=: an exposure total is a sum over days"
+                         + ("" if season is None else " (season= needs period=)"))
+    from .periods import _check_cells
+    _check_cells(cells)
+    if isinstance(weights, str):
+        weights = _agg.prepare_spatial_weights_data(weights)
+    lo, hi = ds[tasmin], ds[tasmax]
+    assert _units(lo) == _units(hi)
+    base = _degree_days(lo, hi, [(1.0, 0.0)], "days")                # (the checks of snyder_edd; the terms are not used)
+    if "time" not in ds.coords:
+        raise ValueError("the dataset has no 'time' coordinate to form periods from")
+    var = minixr.LazyArray(base._values, base.dims, lon_perm=base._lon_perm, edd=base._edd, name=varname)
+    re = _agg._reindex_spatial_data_to_regions(minixr.Dataset({varname: var}, coords=dict(ds.coords)), weights)
+    from . import seasons
+    time_values, labels, grid, lists = _period_lists(ds, period, season)
+    res, rdims, coords, was_xr = seasons._exposure_totals(re, varname, aggwt, agglev, weights, backup_aggwt, lists, len(labels), e, season,
+                                                          grid, time_values, cells=cells)
+    rdims, coords = _time_as_period(rdims, coords, labels)
+    out = _agg._as_dataset({varname: res}, ("bin",) + tuple(rdims), dict(coords, bin=e[:-1].copy()), was_xr)
+    out[varname].attrs["units"] = "days"
+    out[varname].attrs["bin_edges"] = ", ".join(repr(float(x)) for x in e)
     return out
 
 

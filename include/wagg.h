@@ -840,6 +840,45 @@ int wagg_hinge_reduce_f64(const double *X_dev, int64_t T, int64_t n, int64_t ldx
                           int32_t *status_dev, void *work_dev, int64_t work_bytes, void *stream);
 int64_t wagg_hinge_work_bytes(int64_t n, int32_t P, int64_t n_rows, int n_knots);
 
+/* ---- sinusoid exposure bins: the time a day's temperature curve spends in each bin, per period and season (0.12.0) -------------
+ * out[k][p][j] = sum over the rows t of period p, IN LIST ORDER, on which cell j is in season, of
+ * A(lo, hi, edges[k]) - A(lo, hi, edges[k + 1]),  lo = tasmin[t, j] + offset, hi = tasmax[t, j] + offset (shifted in the element
+ * type, as the ladder shifts them),  k = 0 .. n_edges - 2,  2 <= n_edges <= WAGG_EXPOSURE_EDGES_MAX (64 bins) -- one launch, the
+ * bins taken in groups of WAGG_EXPOSURE_GROUP.  A is the fraction of the day the single-sine curve of snyder_edd spends above
+ * e = edges[k] converted to the element type, A = -d EDD / de:
+ *   0                          if lo or hi is NaN   (the day is in no bin; checked first)
+ *   1                          if !(lo < e)         (snyder_edd's own comparisons, in its order)
+ *   0                          if !(hi > e)
+ *   clamp(acos(z) / pi, 0, 1)  otherwise,  z = (e - M) / w clamped to [-1, 1],  M = (hi + lo) / 2,  w = (hi - lo) / 2
+ * The outer cases are exactly 1 and 0; e = -inf gives 1 for every day without NaN, e = +inf gives 0; tasmin > tasmax is a step
+ * at tasmin.  fp32 evaluates acos(z) / pi as sqrt(t) Q(t), t = 1 - |z| = min(hi - e, e - lo) / w, with a fitted Q (<= 1.5e-7
+ * from the fp64 libm value of the same lo, hi, e); fp64 calls libm.  The per-day difference is formed in the element type,
+ * sums are fp64.  Arguments as for wagg_edd_ladder_reduce_* with (edges, n_edges) in place of (thresholds, n_thr):
+ *   edges              n_edges host doubles, strictly ascending; -inf may come first and +inf last (open end bins); a NaN edge,
+ *                      equal or descending edges are WAGG_EINVAL
+ *   offset             finite
+ *   flags              WAGG_PERIOD_ROWS_CHECKED only (no keep-NaN form)
+ *   out_dev            plane k (a bin) at out_dev + k * out_pstride, row p at + p * ldo (out_pstride >= P * ldo when n_edges > 2)
+ *   work_dev           wagg_exposure_work_bytes(n, P, n_rows, n_edges) bytes: what wagg_period_reduce_work_bytes reports for
+ *                      n_edges - 1 planes.  Without it a period's list is summed in one part.
+ * An IN-SEASON +-inf in either field sets bit 0 of status_dev (its bins are then unspecified but finite); a value out of season
+ * reaches neither a sum nor the status word; a piece none of whose cells is in season is not read.  Per edge and row a wave
+ * evaluates the arccosine only if a lane's in-season cells span the edge; the value is the one the full function selects, so a
+ * column's bins do not depend on its neighbours.                                                                              */
+#define WAGG_EXPOSURE_EDGES_MAX 65
+#define WAGG_EXPOSURE_GROUP 8
+int wagg_exposure_reduce_f32(const float *tasmin_dev, const float *tasmax_dev, int64_t T, int64_t n, int64_t ldx,
+                             const int32_t *row_begin_dev, const int32_t *rows_dev, int32_t P, int64_t n_rows,
+                             const int32_t *doy_dev, const int32_t *win_dev, double offset, const double *edges, int n_edges,
+                             int flags, float *out_dev, int64_t ldo, int64_t out_pstride, int32_t *status_dev, void *work_dev,
+                             int64_t work_bytes, void *stream);
+int wagg_exposure_reduce_f64(const double *tasmin_dev, const double *tasmax_dev, int64_t T, int64_t n, int64_t ldx,
+                             const int32_t *row_begin_dev, const int32_t *rows_dev, int32_t P, int64_t n_rows,
+                             const int32_t *doy_dev, const int32_t *win_dev, double offset, const double *edges, int n_edges,
+                             int flags, double *out_dev, int64_t ldo, int64_t out_pstride, int32_t *status_dev, void *work_dev,
+                             int64_t work_bytes, void *stream);
+int64_t wagg_exposure_work_bytes(int64_t n, int32_t P, int64_t n_rows, int n_edges);
+
 /* ---- packed rows: only the quads a segment table references, as a device matrix (0.9.0) ---------------------------------------
  * A single segment-table plan with a whole-line chunking (wagg_plan_info.lines) knows the distinct aligned 4-cell QUADS of a
  * grid row that hold a referenced cell (c2-real: a third of the row).  Its compact row lays them side by side in grid order:
