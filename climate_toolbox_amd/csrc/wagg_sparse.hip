@@ -1645,6 +1645,80 @@ static int launch_many(const wagg_plan *plan, const T *X, int64_t Ttot, int64_t 
     return WAGG_OK;
 }
 
+// ---- plan builder: what wagg_plan_create does with a finished chunking (wagg_chunk.h) ---------------------------------------
+// one chunking -> device arrays `d` (`lines`: a whole-line chunking, whose entries are partial rows)
+static hipError_t upload_chunking(const HostChunking &c, const std::vector<double> &den, const std::vector<float> &den32, bool lines,
+                                  SparsePlanDev &d) {
+    hipError_t he = hipSuccess;
+    auto up = [&](auto &buf, const auto &h) { if (he == hipSuccess) he = buf.upload(h); };
+    std::vector<float> seg_w32(c.seg_w.size());
+    for (size_t i = 0; i < c.seg_w.size(); ++i) seg_w32[i] = (float)c.seg_w[i];
+    up(d.grp_chunk_begin, c.grp_chunk_begin); up(d.grp_giant, c.grp_giant);
+    up(d.chunk_u_begin, c.chunk_u_begin); up(d.chunk_e_begin, c.chunk_e_begin);
+    up(d.ucell, c.ucell); up(d.ent_region, c.ent_region); up(d.ent_seg_begin, c.ent_seg_begin);
+    up(d.seg_u, c.seg_u); up(d.seg_w32, seg_w32); up(d.seg_w64, c.seg_w);
+    up(d.den32, den32); up(d.den64, den); up(d.empty_regions, c.empty); up(d.chunk_desc, c.chunk_desc);
+    {
+        std::vector<double> ed64(c.ent_region.size() + 1, 1.0);   // +1: the clamped ent_seg_begin twin
+        std::vector<float> ed32(c.ent_region.size() + 1, 1.0f);
+        for (size_t e = 0; e < c.ent_region.size() && !lines; ++e) {       // (partial rows are divided when combined)
+            ed64[e] = den[(size_t)c.ent_region[e]];
+            ed32[e] = den32[(size_t)c.ent_region[e]];
+        }
+        up(d.ent_den64, ed64); up(d.ent_den32, ed32);
+    }
+    if (lines) {
+        up(d.part_begin, c.part_begin); d.n_part = c.n_part_rows;
+        up(d.ucell_c, c.ucell_c);
+        d.run_src = c.run_src; d.run_len = c.run_len; d.Gc = c.Gc;
+        if (!c.ucell_q.empty()) up(d.ucell_q, c.ucell_q);
+        d.run_src_q = c.run_src_q; d.run_len_q = c.run_len_q; d.Gq = c.Gq;
+    }
+    d.g0_normal = c.g0_normal; d.c0_normal = c.c0_normal;
+    d.n_groups = (int64_t)c.grp_giant.size(); d.n_empty = (int64_t)c.empty.size();
+    return he;
+}
+
+// what wagg_plan_info and the WAGG_PLAN_STATS line keep of one chunking (a job notes them; its arrays go when it is uploaded)
+struct ChunkCounts { int64_t n_groups, n_chunks, n_ucells, n_giant, n_empty, lines128, sectors64, n_part_rows; };
+static ChunkCounts counts_of(const HostChunking &c) {
+    return {(int64_t)c.grp_giant.size(), (int64_t)c.chunk_u_begin.size() - 1,
+            (int64_t)c.ucell.size() * 4,    // cells fetched per timestep (whole quads)
+            c.n_giant, (int64_t)c.empty.size(), c.lines128, c.sectors64, c.n_part_rows};
+}
+
+// the info fields of one chunking (kind: 0 region-shaped, 1 / 2 whole lines fp32 / fp64; 3 adds none -- info.lines names it)
+static void fill_info(int kind, const ChunkCounts &n, wagg_plan_info &info) {
+    if (kind == 0) {
+        info.n_groups = n.n_groups;
+        info.n_chunks = n.n_chunks;
+        info.n_ucells = n.n_ucells;
+        info.n_giant = n.n_giant;
+        info.n_empty = n.n_empty;
+        info.n_lines128 = n.lines128; info.n_sectors64 = n.sectors64;
+    } else if (kind == 1) {
+        info.n_partial_rows = n.n_part_rows;
+        info.lines_chunks = n.n_chunks;
+        info.lines_ucells = n.n_ucells;
+        info.lines_lines128 = n.lines128;
+    } else if (kind == 2) {
+        info.n_partial_rows64 = n.n_part_rows;
+        info.lines64_chunks = n.n_chunks;
+        info.lines64_ucells = n.n_ucells;
+    }
+}
+
+// plan statistics without a device (host experiments on the chunk builder; diagnostic build, WAGG_PLAN_STATS)
+static void plan_stats([[maybe_unused]] const ChunkCounts &n, [[maybe_unused]] int line_cells, [[maybe_unused]] int band_rows,
+                       [[maybe_unused]] int64_t nnz) {
+#ifdef WAGG_DIAG
+    if (diag_set("WAGG_PLAN_STATS"))
+        fprintf(stderr, "[wagg plan] line_cells=%d band_rows=%d chunks=%lld groups=%lld giant=%lld ucells=%lld lines128=%lld sectors64=%lld nnz=%lld partial_rows=%lld\n",
+                line_cells, band_rows, (long long)n.n_chunks, (long long)n.n_groups, (long long)n.n_giant, (long long)n.n_ucells,
+                (long long)n.lines128, (long long)n.sectors64, (long long)nnz, (long long)n.n_part_rows);
+#endif
+}
+
 }  // namespace wagg
 
 // ---------------------------------------------------------------------------------------------
@@ -1669,69 +1743,18 @@ extern "C" int wagg_plan_create(const int32_t *cell_idx, const int32_t *region_c
     WAGG_REQUIRE(nseg == 0 || (cell_idx && region_code && w_eff), "NULL segment arrays");
     if (row_len <= 0 || row_len > G) row_len = G;
 
-    struct Seg { int32_t region, cell; double w; };
-    std::vector<Seg> segs;
-    std::vector<double> den((size_t)R, 0.0);
     try {
-        segs.reserve((size_t)nseg);
-        for (int64_t i = 0; i < nseg; ++i) {
-            const int32_t r = region_code[i];
-            if (r < 0) continue;                                  // null label (S3)
-            WAGG_REQUIRE(r < R, "region_code[%lld]=%d out of range [0,%d)", (long long)i, r, R);
-            WAGG_REQUIRE(cell_idx[i] >= 0 && cell_idx[i] < G, "cell_idx[%lld]=%d out of range",
-                         (long long)i, cell_idx[i]);
-            if (std::isnan(w_eff[i])) continue;                   // skipna on :78/:79
-            den[(size_t)r] += w_eff[i];                           // aggregations.py:79
-            segs.push_back({r, cell_idx[i], w_eff[i]});
+        SegTable table;
+        ChunkError bad;
+        if (!coalesce_table(cell_idx, region_code, w_eff, nseg, G, R, row_len, table, bad)) {
+            set_error("%s", bad.text.c_str());
+            return bad.code;
         }
-        // by (region, cell), rows of one pair in table order (S5: they are added in that order below).  std::stable_sort on
-        // the 16-byte rows was half of a c2-real plan build (42 of ~80 ms for 4e5 rows); stable counting passes -- by cell,
-        // then by region -- do it in a third of that, and a table that already comes by cell (rows = grid order, the usual
-        // export) or by (region, cell) skips the passes it does not need
-        {
-            bool by_cell = true, by_region_cell = true;
-            for (size_t i = 1; i < segs.size(); ++i) {
-                by_cell = by_cell && segs[i - 1].cell <= segs[i].cell;
-                by_region_cell = by_region_cell && (segs[i - 1].region < segs[i].region ||
-                                                    (segs[i - 1].region == segs[i].region && segs[i - 1].cell <= segs[i].cell));
-            }
-            auto counting_pass = [&](int64_t n_keys, auto key_of) {
-                std::vector<int64_t> first((size_t)n_keys + 1, 0);
-                for (const Seg &sg : segs) ++first[(size_t)key_of(sg) + 1];
-                for (int64_t k = 0; k < n_keys; ++k) first[(size_t)k + 1] += first[(size_t)k];
-                std::vector<Seg> sorted(segs.size());
-                for (const Seg &sg : segs) sorted[(size_t)first[(size_t)key_of(sg)]++] = sg;
-                segs.swap(sorted);
-            };
-            if (by_region_cell) {
-                // nothing to do
-            } else if (G > 8 * (int64_t)segs.size() + (1 << 22)) {          // a counter per cell would dwarf the table
-                std::stable_sort(segs.begin(), segs.end(), [](const Seg &a, const Seg &b) {
-                    return a.region != b.region ? a.region < b.region : a.cell < b.cell;
-                });
-            } else {
-                if (!by_cell) counting_pass(G, [](const Seg &sg) { return (int64_t)sg.cell; });
-                counting_pass(R, [](const Seg &sg) { return (int64_t)sg.region; });
-            }
-        }
-        // coalesce duplicate (cell, region) rows (S5)
-        size_t m = 0;
-        for (size_t i = 0; i < segs.size(); ++i) {
-            if (m && segs[m - 1].region == segs[i].region && segs[m - 1].cell == segs[i].cell)
-                segs[m - 1].w += segs[i].w;
-            else segs[m++] = segs[i];
-        }
-        segs.resize(m);
-        const int64_t nnz = (int64_t)m;
-
-        // per-region ranges + spatial key
-        std::vector<int64_t> rbeg((size_t)R + 1, 0);
-        for (const Seg &s : segs) rbeg[(size_t)s.region + 1]++;
-        for (int32_t r = 0; r < R; ++r) rbeg[(size_t)r + 1] += rbeg[(size_t)r];
+        const std::vector<double> &den = table.den;
         wagg_plan *plan = new wagg_plan();
         std::unique_ptr<wagg_plan> plan_guard(plan);
         plan->den_host = den;
-        plan->info.nseg_in = nseg; plan->info.nnz = nnz;
+        plan->info.nseg_in = nseg; plan->info.nnz = table.nnz;
         plan->info.G = G; plan->info.R = R;
         plan->flags = flags;
         std::vector<float> den32(den.size());
@@ -1745,469 +1768,23 @@ extern "C" int wagg_plan_create(const int32_t *cell_idx, const int32_t *region_c
             he = hipHostGetDevicePointer((void **)&plan->timeout_dev, plan->timeout_host, 0);
         }
 #endif
-        // one chunking of the table -> device arrays `d`; returns false when the whole-line chunking does not apply
-        // (line_cells: 0 = region-shaped chunks; 32 / 16 = whole lines of that many cells, 128 bytes of a fp32 / fp64 row)
-        // (kind: 0 region-shaped, 1 whole lines fp32, 2 whole lines fp64, 3 the 64-cell chunks of fp64 degree days)
-        // (`he`: the caller's error word -- the whole-line chunkings are built on threads of their own, each with its own)
-        auto build = [&](int line_cells, int lines_per_chunk, int kind, SparsePlanDev &d, hipError_t &he) -> bool {
-        const bool for_f64 = kind >= 2;
-        const bool want_lines = line_cells > 0;
-        std::vector<int32_t> grp_chunk_begin{0}, grp_giant, chunk_u_begin{0}, chunk_e_begin{0};
-        std::vector<int32_t> ucell, ent_region, ent_seg_begin{0}, seg_u;   // ucell = first cell of each quad
-        std::vector<double> seg_w;
-        std::vector<int32_t> part_begin;                                   // whole-line plan only
-        int64_t n_part_rows = 0;
-        std::vector<int32_t> empty;
-        int64_t n_giant = 0;
-        int band_rows = 8;
-        seg_u.reserve((size_t)nnz); seg_w.reserve((size_t)nnz);
-
-        // ---- whole-line plan (round 3) --------------------------------------------------------------------------------
-        // A chunk = up to 8 whole 32-cell LINES (128 bytes of a fp32 row, 256 of a fp64 row) of ONE column strip: the
-        // land lines of the strip in row order, eight at a time (ocean rows in between are skipped).  Every line belongs
-        // to exactly one chunk and is fetched whole: 8 line requests per timestep and chunk where the region-shaped
-        // chunks below need ~23 (their quads straddle lines, and border lines are fetched by both neighbours), at
-        // ~1.4x the bytes (the ocean cells of a coastal line come along).  The price: a region cut by a strip or by a
-        // group of eight lines becomes several (chunk, region) ENTRIES, each a partial sum with a row of its own in the
-        // partial buffer; combine_parts_kernel adds them up (1.6 rows per region on the 0.25-degree impact regions).
-        // Taken when the grid's row length is known (whole rows of whole quads) and the table is compact enough.
-        const int LINE = want_lines ? line_cells : 32;                     // cells per line
-        const int LPC = lines_per_chunk;                                   // lines per chunk
-        bool lines_plan = want_lines;
-        if (lines_plan) {
-            struct LSeg { int64_t line; int32_t region, col; double w; };
-            // segments by (line, region, column), line = strip * n_rows + row: `segs` is sorted by (region, cell), so a STABLE
-            // counting sort on the line alone gives that order (cells of one line and region ascend with their column)
-            const int64_t n_rows_ = G / row_len, n_strips_ = (row_len + LINE - 1) / LINE;
-            std::vector<LSeg> ls((size_t)nnz);
-            {
-                std::vector<int64_t> first((size_t)(n_rows_ * n_strips_) + 1, 0);
-                std::vector<int64_t> line_of((size_t)nnz);
-                for (int64_t i = 0; i < nnz; ++i) {
-                    const int64_t row = segs[(size_t)i].cell / row_len, col = segs[(size_t)i].cell % row_len;
-                    line_of[(size_t)i] = (col / LINE) * n_rows_ + row;
-                    ++first[(size_t)line_of[(size_t)i] + 1];
-                }
-                for (size_t l = 1; l < first.size(); ++l) first[l] += first[l - 1];
-                for (int64_t i = 0; i < nnz; ++i) {
-                    const int64_t col = segs[(size_t)i].cell % row_len;
-                    ls[(size_t)first[(size_t)line_of[(size_t)i]]++] = {line_of[(size_t)i], segs[(size_t)i].region, (int32_t)(col % LINE), segs[(size_t)i].w};
-                }
-            }
-            const int64_t n_rows = G / row_len;
-            std::vector<std::vector<int32_t>> parts((size_t)R);
-            std::vector<int32_t> region_mark((size_t)R, -1);
-            struct CSeg { int32_t region, ulocal; double w; };
-            // pass 1: form the chunks strip by strip
-            struct LChunk { int64_t key; std::vector<int32_t> quads; std::vector<CSeg> cs; };
-            std::vector<LChunk> chunks;
-            const int64_t n_strips = (row_len + LINE - 1) / LINE;
-            size_t i = 0;
-            while (i < ls.size() && lines_plan) {
-                // one chunk: lines of this strip while it holds < LPC lines, <= SEG_MAX segments, <= RG_MAX regions
-                const int64_t strip = ls[i].line / n_rows;
-                const int32_t chunk_id = (int32_t)chunks.size();
-                int n_lines = 0, n_regions = 0;
-                LChunk ch;
-                ch.key = ((ls[i].line % n_rows) / LPC) * n_strips + strip;       // band of LPC grid rows, then strip
-                while (i < ls.size() && ls[i].line / n_rows == strip && n_lines < LPC) {
-                    size_t j = i;                                          // the segments of the next line
-                    int fresh = 0;
-                    while (j < ls.size() && ls[j].line == ls[i].line) {
-                        if (region_mark[(size_t)ls[j].region] != chunk_id) { region_mark[(size_t)ls[j].region] = chunk_id; ++fresh; }
-                        ++j;
-                    }
-                    if (n_lines > 0 && ((int64_t)ch.cs.size() + (int64_t)(j - i) > SEG_MAX || n_regions + fresh > RG_MAX)) {
-                        for (size_t k = i; k < j; ++k) region_mark[(size_t)ls[k].region] = -1;   // (marks of the line not taken)
-                        for (const CSeg &c : ch.cs) region_mark[(size_t)c.region] = chunk_id;
-                        break;
-                    }
-                    if ((int64_t)(j - i) > SEG_MAX || fresh > RG_MAX) { lines_plan = false; break; }   // one line alone is too much
-                    n_regions += fresh;
-                    const int64_t row = ls[i].line % n_rows;
-                    for (int q = 0; q < LINE / 4; ++q) {                   // the line's quads; those behind the row end repeat its last
-                        int64_t c0 = strip * LINE + 4 * q;
-                        if (c0 + 4 > row_len) c0 = row_len - 4;
-                        ch.quads.push_back((int32_t)(row * row_len + c0));
-                    }
-                    for (size_t k = i; k < j; ++k) ch.cs.push_back({ls[k].region, n_lines * LINE + ls[k].col, ls[k].w});
-                    ++n_lines;
-                    i = j;
-                }
-                if (!lines_plan) break;
-                std::sort(ch.cs.begin(), ch.cs.end(), [](const CSeg &a, const CSeg &b) {
-                    return a.region != b.region ? a.region < b.region : a.ulocal < b.ulocal; });
-                chunks.push_back(std::move(ch));
-            }
-            // pass 2: flatten, in the order formed (strip-major: down one column strip, then the next).  Measured against
-            // band-major order (all strips of eight grid rows, then the next eight rows: neighbouring lines of the same
-            // DRAM pages in flight together) on c2-real / c3-real: 0.236 / 0.331 ms strip-major, 0.237 / 0.352 ms
-            // band-major (gpurun r3r) -- the diagnostic build keeps the switch
-            if (diag_env("WAGG_LINES_ORDER") == 2)
-                std::stable_sort(chunks.begin(), chunks.end(), [](const LChunk &a, const LChunk &b) { return a.key < b.key; });
-            int64_t n_part = 0;
-            for (const LChunk &ch : chunks) {
-                if (!lines_plan) break;
-                ucell.insert(ucell.end(), ch.quads.begin(), ch.quads.end());
-                chunk_u_begin.push_back((int32_t)ucell.size());
-                const std::vector<CSeg> &cs = ch.cs;
-                // the chunk's entries, longest first: the consumer waves of sparse_lcv_kernel take them from a shared
-                // counter, so the long ones start early and the short ones fill the end (longest-processing-time order)
-                std::vector<std::pair<size_t, size_t>> runs;
-                for (size_t k = 0; k < cs.size();) {
-                    size_t m2 = k;
-                    while (m2 < cs.size() && cs[m2].region == cs[k].region) ++m2;
-                    runs.push_back({k, m2});
-                    k = m2;
-                }
-                std::stable_sort(runs.begin(), runs.end(), [](const std::pair<size_t, size_t> &a, const std::pair<size_t, size_t> &b) {
-                    return a.second - a.first > b.second - b.first; });
-                for (const auto &run : runs) {
-                    for (size_t m2 = run.first; m2 < run.second; ++m2) { seg_u.push_back(cs[m2].ulocal); seg_w.push_back(cs[m2].w); }
-                    parts[(size_t)cs[run.first].region].push_back((int32_t)n_part);
-                    ent_region.push_back((int32_t)n_part++);              // the entry's row in the partial buffer
-                    ent_seg_begin.push_back((int32_t)seg_u.size());
-                }
-                chunk_e_begin.push_back((int32_t)ent_region.size());
-                grp_giant.push_back(0);
-                grp_chunk_begin.push_back((int32_t)(chunk_u_begin.size() - 1));
-            }
-            // scattered regions (a c5-like table) would need more partial rows than the table has regions many times
-            // over: such tables keep the region-shaped chunks (and usually take a dense-family form anyway)
-            if (lines_plan && n_part > 4 * (int64_t)R + 1024) lines_plan = false;
-            if (lines_plan) {
-                // partial rows are numbered region-major: region r owns rows part_begin[r] .. part_begin[r + 1] - 1 of the
-                // partial buffer, in chunk order, so the combine kernel streams the buffer front to back
-                part_begin.assign((size_t)R + 1, 0);
-                std::vector<int32_t> new_id((size_t)n_part, 0);
-                for (int32_t r = 0; r < R; ++r) {
-                    part_begin[(size_t)r + 1] = part_begin[(size_t)r] + (int32_t)parts[(size_t)r].size();
-                    for (size_t j = 0; j < parts[(size_t)r].size(); ++j)
-                        new_id[(size_t)parts[(size_t)r][j]] = part_begin[(size_t)r] + (int32_t)j;
-                    if (parts[(size_t)r].empty()) empty.push_back(r);
-                }
-                for (int32_t &e : ent_region) e = new_id[(size_t)e];
-                n_part_rows = n_part;
-            } else {                                                        // start over with the region-shaped chunks
-                grp_chunk_begin.assign(1, 0); grp_giant.clear(); chunk_u_begin.assign(1, 0); chunk_e_begin.assign(1, 0);
-                ucell.clear(); ent_region.clear(); ent_seg_begin.assign(1, 0); seg_u.clear(); seg_w.clear();
-            }
-        }
-        if (!lines_plan) {
-        // regions are ordered along latitude bands of `band_rows` grid rows (column-major inside a
-        // band): a chunk then covers ~band_rows rows x a run of columns
-        if (const int v = diag_env("WAGG_BAND_ROWS")) { if (v >= 1 && v <= 1024) band_rows = v; }
-        std::vector<int32_t> order;
-        std::vector<double> key_col((size_t)R, 0.0);
-        std::vector<int64_t> key_band((size_t)R, 0);
-        for (int32_t r = 0; r < R; ++r) {
-            const int64_t n = rbeg[(size_t)r + 1] - rbeg[(size_t)r];
-            if (n == 0) { empty.push_back(r); continue; }
-            double srow = 0, scol = 0;
-            for (int64_t i = rbeg[(size_t)r]; i < rbeg[(size_t)r + 1]; ++i) {
-                srow += (double)(segs[(size_t)i].cell / row_len);
-                scol += (double)(segs[(size_t)i].cell % row_len);
-            }
-            key_band[(size_t)r] = (int64_t)(srow / (double)n) / band_rows;
-            key_col[(size_t)r] = scol / (double)n;
-            order.push_back(r);
-        }
-        std::sort(order.begin(), order.end(), [&](int32_t a, int32_t b) {
-            if (key_band[(size_t)a] != key_band[(size_t)b]) return key_band[(size_t)a] < key_band[(size_t)b];
-            if (key_col[(size_t)a] != key_col[(size_t)b]) return key_col[(size_t)a] < key_col[(size_t)b];
-            return a < b;
-        });
-
-        // greedy grouping on aligned 4-cell QUADS (16 bytes of a fp32 row): the kernel fetches
-        // a chunk as up to UQ quads per timestep with one dwordx4 per lane
-        struct Group { std::vector<int32_t> regions; int64_t n_q = 0, n_seg = 0; bool giant = false; };
-        std::vector<Group> groups;
-        std::vector<int32_t> stamp((size_t)(G + 3) / 4, -1);
-        auto quads_of = [&](int32_t r) {       // distinct quads of a region (its cells are sorted)
-            int64_t n = 0;
-            int32_t last = -1;
-            for (int64_t i = rbeg[(size_t)r]; i < rbeg[(size_t)r + 1]; ++i) {
-                const int32_t q = segs[(size_t)i].cell >> 2;
-                if (q != last) { ++n; last = q; }
-            }
-            return n;
-        };
-        Group cur;
-        int32_t cur_id = 0;
-        auto close = [&]() {
-            if (!cur.regions.empty()) { groups.push_back(std::move(cur)); cur = Group(); }
-            ++cur_id;
-        };
-        for (int32_t r : order) {
-            const int64_t b = rbeg[(size_t)r], e = rbeg[(size_t)r + 1];
-            const int64_t nq_r = quads_of(r);
-            if (nq_r > UQ || e - b > SEG_MAX) {
-                close();
-                Group gg; gg.regions.push_back(r); gg.n_q = nq_r; gg.giant = true;
-                groups.push_back(std::move(gg));
-                ++n_giant;
-                continue;
-            }
-            int64_t fresh = 0;
-            {
-                int32_t last = -1;
-                for (int64_t i = b; i < e; ++i) {
-                    const int32_t q = segs[(size_t)i].cell >> 2;
-                    if (q != last) { fresh += stamp[(size_t)q] != cur_id; last = q; }
-                }
-            }
-            if (cur.n_q + fresh > UQ || (int64_t)cur.regions.size() + 1 > RG_MAX ||
-                cur.n_seg + (e - b) > SEG_MAX) {
-                close();
-                fresh = nq_r;
-            }
-            for (int64_t i = b; i < e; ++i) stamp[(size_t)(segs[(size_t)i].cell >> 2)] = cur_id;
-            cur.n_q += fresh;
-            cur.n_seg += e - b;
-            cur.regions.push_back(r);
-        }
-        close();
-        // giant groups (many chunks) first, largest first; all other groups stay in band/column
-        // order so that consecutive workgroups touch neighbouring cells of the same grid rows
-        std::stable_sort(groups.begin(), groups.end(), [](const Group &a, const Group &b) {
-            if (a.giant != b.giant) return a.giant;
-            return a.giant && a.n_q > b.n_q;
-        });
-
-        // flatten
-        std::vector<int32_t> &pos = stamp;  // reuse as quad -> local index scratch
-        std::vector<int32_t> quads;
-        for (const Group &gr : groups) {
-            grp_giant.push_back(gr.giant ? 1 : 0);
-            if (gr.giant) {
-                const int32_t r = gr.regions[0];
-                const int64_t b = rbeg[(size_t)r], e = rbeg[(size_t)r + 1];
-                int64_t cb = b;
-                while (cb < e) {
-                    // take segments until the chunk holds UQ quads
-                    int64_t ce = cb, nq = 0;
-                    int32_t last = -1;
-                    const size_t ubase = ucell.size();
-                    while (ce < e) {
-                        const int32_t q = segs[(size_t)ce].cell >> 2;
-                        if (q != last) {
-                            if (nq == UQ) break;
-                            ucell.push_back(q * 4);
-                            ++nq; last = q;
-                        }
-                        ++ce;
-                    }
-                    chunk_u_begin.push_back((int32_t)ucell.size());
-                    // split the chunk's segments over the waves
-                    const int64_t n = ce - cb, per = (n + NWAVE - 1) / NWAVE;
-                    for (int64_t sb = 0; sb < n; sb += per) {
-                        const int64_t se = std::min<int64_t>(sb + per, n);
-                        for (int64_t i = sb; i < se; ++i) {
-                            const int32_t cell = segs[(size_t)(cb + i)].cell;
-                            // local quad index: position of cell>>2 among this chunk's quads
-                            const auto it = std::lower_bound(ucell.begin() + (std::ptrdiff_t)ubase, ucell.end(),
-                                                             (cell >> 2) * 4);
-                            seg_u.push_back((int32_t)((it - (ucell.begin() + (std::ptrdiff_t)ubase)) * 4 + (cell & 3)));
-                            seg_w.push_back(segs[(size_t)(cb + i)].w);
-                        }
-                        ent_region.push_back(r);
-                        ent_seg_begin.push_back((int32_t)seg_u.size());
-                    }
-                    chunk_e_begin.push_back((int32_t)ent_region.size());
-                    cb = ce;
-                }
-            } else {
-                quads.clear();
-                for (int32_t r : gr.regions)
-                    for (int64_t i = rbeg[(size_t)r]; i < rbeg[(size_t)r + 1]; ++i)
-                        quads.push_back(segs[(size_t)i].cell >> 2);
-                std::sort(quads.begin(), quads.end());
-                quads.erase(std::unique(quads.begin(), quads.end()), quads.end());
-                for (size_t i = 0; i < quads.size(); ++i) {
-                    pos[(size_t)quads[i]] = (int32_t)i;
-                    ucell.push_back(quads[i] * 4);
-                }
-                chunk_u_begin.push_back((int32_t)ucell.size());
-                for (int32_t r : gr.regions) {
-                    for (int64_t i = rbeg[(size_t)r]; i < rbeg[(size_t)r + 1]; ++i) {
-                        const int32_t cell = segs[(size_t)i].cell;
-                        seg_u.push_back(pos[(size_t)(cell >> 2)] * 4 + (cell & 3));
-                        seg_w.push_back(segs[(size_t)i].w);
-                    }
-                    ent_region.push_back(r);
-                    ent_seg_begin.push_back((int32_t)seg_u.size());
-                }
-                chunk_e_begin.push_back((int32_t)ent_region.size());
-            }
-            grp_chunk_begin.push_back((int32_t)(chunk_u_begin.size() - 1));
-        }
-        }   // region-shaped chunks
-
-        // bit 15 of a segment's local cell index marks the LAST segment of its region entry
-        // (local indices are < 256); entries without segments cannot exist (every entry has >= 1)
-        for (size_t e = 0; e + 1 < ent_seg_begin.size(); ++e)
-            if (ent_seg_begin[e + 1] > ent_seg_begin[e]) seg_u[(size_t)ent_seg_begin[e + 1] - 1] |= SEG_LAST;
-        // bits 16..23: index of the segment's entry inside its chunk (read by the MFMA kernel)
-        for (size_t c = 0; c + 1 < chunk_e_begin.size(); ++c)
-            for (int32_t e = chunk_e_begin[c]; e < chunk_e_begin[c + 1]; ++e)
-                for (int32_t q = ent_seg_begin[(size_t)e]; q < ent_seg_begin[(size_t)e + 1]; ++q)
-                    seg_u[(size_t)q] |= (e - chunk_e_begin[c]) << 16;
-        // per-chunk descriptors for the persistent kernel; giant groups come first.  dd[6] packs the
-        // entry split points of the four waves (contiguous entry ranges with ~equal segment counts)
-        std::vector<int32_t> chunk_desc((size_t)(chunk_u_begin.size() - 1) * 8, 0);
-        for (size_t c = 0; c + 1 < chunk_u_begin.size(); ++c) {
-            int32_t *dd = &chunk_desc[c * 8];
-            dd[0] = chunk_u_begin[c]; dd[1] = chunk_u_begin[c + 1] - chunk_u_begin[c];
-            dd[2] = chunk_e_begin[c]; dd[3] = chunk_e_begin[c + 1] - chunk_e_begin[c];
-            dd[4] = ent_seg_begin[(size_t)chunk_e_begin[c]];
-            dd[5] = ent_seg_begin[(size_t)chunk_e_begin[c + 1]] - dd[4];
-            int32_t split[SWAVE + 1];
-            for (int i = 0; i <= SWAVE; ++i) split[i] = i == SWAVE ? dd[3] : 0;
-            int w = 1;
-            for (int32_t e = 0; e < dd[3] && w < SWAVE; ++e) {
-                const int64_t done = ent_seg_begin[(size_t)(dd[2] + e + 1)] - dd[4];
-                while (w < SWAVE && done * SWAVE >= (int64_t)dd[5] * w) split[w++] = e + 1;
-            }
-            while (w < SWAVE) split[w++] = dd[3];
-            uint64_t packed = 0;
-            for (int i = 1; i < SWAVE; ++i) packed |= (uint64_t)(split[i] & 0xff) << (8 * (i - 1));
-            dd[6] = (int32_t)(uint32_t)(packed & 0xffffffffu);
-            dd[7] = (int32_t)(uint32_t)(packed >> 32);
-        }
-        int g0_normal = 0;
-        while (g0_normal < (int)grp_giant.size() && grp_giant[(size_t)g0_normal]) ++g0_normal;
-        const int c0_normal = grp_chunk_begin[(size_t)g0_normal];
-
-        if (lines_plan != want_lines) return false;
-        if (!want_lines) {
-            plan->info.n_groups = (int64_t)grp_giant.size();
-            plan->info.n_chunks = (int64_t)chunk_u_begin.size() - 1;
-            plan->info.n_ucells = (int64_t)ucell.size() * 4;    // cells fetched per timestep (whole quads)
-            plan->info.n_giant = n_giant;
-            plan->info.n_empty = (int64_t)empty.size();
-        } else if (kind == 3) {
-            // (info.lines: set by the caller once the builder threads have joined)
-        } else if (!for_f64) {
-            plan->info.n_partial_rows = n_part_rows;
-            plan->info.lines_chunks = (int64_t)chunk_u_begin.size() - 1;
-            plan->info.lines_ucells = (int64_t)ucell.size() * 4;
-        } else {
-            plan->info.n_partial_rows64 = n_part_rows;
-            plan->info.lines64_chunks = (int64_t)chunk_u_begin.size() - 1;
-            plan->info.lines64_ucells = (int64_t)ucell.size() * 4;
-        }
-        int64_t l128s = 0, s64s = 0;
-        for (size_t c = 0; c + 1 < chunk_u_begin.size(); ++c) {      // locality statistics of the gather
-            int32_t l128 = -1, s64 = -1;
-            std::vector<int32_t> qs(ucell.begin() + chunk_u_begin[c], ucell.begin() + chunk_u_begin[c + 1]);
-            std::sort(qs.begin(), qs.end());
-            for (int32_t q : qs) {
-                if ((q >> 5) != l128) { l128 = q >> 5; ++l128s; }
-                if ((q >> 4) != s64) { s64 = q >> 4; ++s64s; }
-            }
-        }
-        if (!want_lines) { plan->info.n_lines128 = l128s; plan->info.n_sectors64 = s64s; }
-        else if (kind == 1) plan->info.lines_lines128 = l128s;
-#ifdef WAGG_DIAG
-        if (diag_set("WAGG_PLAN_STATS"))      // plan statistics without a device (host experiments on the chunk builder)
-            fprintf(stderr, "[wagg plan] line_cells=%d band_rows=%d chunks=%lld groups=%lld giant=%lld ucells=%lld lines128=%lld sectors64=%lld nnz=%lld partial_rows=%lld\n",
-                    lines_plan ? line_cells : 0, band_rows, (long long)chunk_u_begin.size() - 1, (long long)grp_giant.size(), (long long)n_giant,
-                    (long long)ucell.size() * 4, (long long)l128s, (long long)s64s, (long long)nnz, (long long)n_part_rows);
-#endif
-        // Whole-line chunkings: which quads of a chunk does a segment really read?  A chunk fetches every quad of its lines; the
-        // others are parked in the image and never read -- except quad 0, whose first cell the padding lanes of the consumers
-        // read with weight 0 (so it counts as referenced: its data must be sane for 0 * x = 0).  Unreferenced quads get bit 0 of
-        // their ucell entry set (UCELL_UNREF; quads are 4-cell aligned, the low bits are free): the kernels mask it off the address,
-        // and sparse_lcv_kernel leaves what such a quad loads out of its finite / general decision (Regs::unref).
-        // (a segment's local cell index is the low byte of seg_u -- bit 15 and bits 16..23 carry flags by now, see above)
-        std::vector<char> used;
-        bool map_ok = lines_plan && kind >= 1;
-        if (map_ok) {
-            used.assign(ucell.size(), 0);
-            for (size_t c = 0; c + 1 < chunk_u_begin.size() && map_ok; ++c) {
-                const int32_t nq = chunk_u_begin[c + 1] - chunk_u_begin[c];
-                if (nq > 0) used[(size_t)chunk_u_begin[c]] = 1;
-                for (int32_t e = chunk_e_begin[c]; e < chunk_e_begin[c + 1] && map_ok; ++e)
-                    for (int32_t sg = ent_seg_begin[(size_t)e]; sg < ent_seg_begin[(size_t)e + 1]; ++sg) {
-                        const int32_t q = (seg_u[(size_t)sg] & 0xff) >> 2;
-                        if (q >= nq) { map_ok = false; break; }                  // (cannot happen; then: no flags, no quad map)
-                        used[(size_t)chunk_u_begin[c] + (size_t)q] = 1;
-                    }
-            }
-            if (map_ok)
-                for (size_t i = 0; i < ucell.size(); ++i) if (!used[i]) ucell[i] |= UCELL_UNREF;
-        }
-        std::vector<float> seg_w32(seg_w.size());
-        for (size_t i = 0; i < seg_w.size(); ++i) seg_w32[i] = (float)seg_w[i];
-        auto up = [&](auto &buf, const auto &h) { if (he == hipSuccess) he = buf.upload(h); };
-        up(d.grp_chunk_begin, grp_chunk_begin); up(d.grp_giant, grp_giant);
-        up(d.chunk_u_begin, chunk_u_begin); up(d.chunk_e_begin, chunk_e_begin);
-        up(d.ucell, ucell); up(d.ent_region, ent_region); up(d.ent_seg_begin, ent_seg_begin);
-        up(d.seg_u, seg_u); up(d.seg_w32, seg_w32); up(d.seg_w64, seg_w);
-        up(d.den32, den32); up(d.den64, den); up(d.empty_regions, empty); up(d.chunk_desc, chunk_desc);
-        {
-            std::vector<double> ed64(ent_region.size() + 1, 1.0);   // +1: the clamped ent_seg_begin twin
-            std::vector<float> ed32(ent_region.size() + 1, 1.0f);
-            for (size_t e = 0; e < ent_region.size() && !lines_plan; ++e) {       // (partial rows are divided when combined)
-                ed64[e] = den[(size_t)ent_region[e]];
-                ed32[e] = den32[(size_t)ent_region[e]];
-            }
-            up(d.ent_den64, ed64); up(d.ent_den32, ed32);
-        }
-        if (lines_plan) { up(d.part_begin, part_begin); d.n_part = n_part_rows; }
-        if (lines_plan && kind >= 1) {
-            // the compact row of the lines-only host path: the distinct quads of this chunking in grid order, side by side
-            // (ucell entries carry UCELL_UNREF in bit 0: compared without it, handed on with it)
-            std::vector<int32_t> uq(ucell.size());
-            for (size_t i = 0; i < ucell.size(); ++i) uq[i] = ucell[i] & ~UCELL_UNREF;
-            std::sort(uq.begin(), uq.end());
-            uq.erase(std::unique(uq.begin(), uq.end()), uq.end());
-            std::vector<int32_t> ucell_c(ucell.size());
-            for (size_t i = 0; i < ucell.size(); ++i)
-                ucell_c[i] = (int32_t)(4 * (std::lower_bound(uq.begin(), uq.end(), ucell[i] & ~UCELL_UNREF) - uq.begin())) | (ucell[i] & UCELL_UNREF);
-            d.run_src.clear(); d.run_len.clear();
-            for (size_t i = 0; i < uq.size(); ++i) {
-                if (i > 0 && uq[i] == uq[i - 1] + 4) d.run_len.back() += 4;
-                else { d.run_src.push_back((int64_t)uq[i]); d.run_len.push_back(4); }
-            }
-            up(d.ucell_c, ucell_c);
-            d.Gc = 4 * (int64_t)uq.size();
-            // ... and the quads that count as referenced only (wagg_sparse_int.h: ucell_q); the others point at position 0 of
-            // the row (any valid address: what they load is neither read nor counted)
-            if (map_ok) {
-                std::vector<int32_t> uqq;
-                for (size_t i = 0; i < ucell.size(); ++i) if (used[i]) uqq.push_back(ucell[i]);
-                std::sort(uqq.begin(), uqq.end());
-                uqq.erase(std::unique(uqq.begin(), uqq.end()), uqq.end());
-                std::vector<int32_t> ucell_q(ucell.size(), UCELL_UNREF);
-                for (size_t i = 0; i < ucell.size(); ++i)
-                    if (used[i]) ucell_q[i] = (int32_t)(4 * (std::lower_bound(uqq.begin(), uqq.end(), ucell[i]) - uqq.begin()));
-                d.run_src_q.clear(); d.run_len_q.clear();
-                for (size_t i = 0; i < uqq.size(); ++i) {
-                    if (i > 0 && uqq[i] == uqq[i - 1] + 4) d.run_len_q.back() += 4;
-                    else { d.run_src_q.push_back((int64_t)uqq[i]); d.run_len_q.push_back(4); }
-                }
-                up(d.ucell_q, ucell_q);
-                d.Gq = 4 * (int64_t)uqq.size();
-            }
-        }
-        d.g0_normal = g0_normal; d.c0_normal = c0_normal;
-        d.n_groups = (int64_t)grp_giant.size(); d.n_empty = (int64_t)empty.size();
-        return true;
-        };   // build
+        ChunkKnobs knobs;
+        if (const int v = diag_env("WAGG_BAND_ROWS")) { if (v >= 1 && v <= 1024) knobs.band_rows = v; }
+        knobs.lines_order = diag_env("WAGG_LINES_ORDER");
 
         // The chunkings are independent of each other: the region-shaped one is built here, the whole-line ones (for the
         // kernel that is bound by line requests; their extra bytes -- ocean cells of coastal lines -- cost the other kernels
         // more than the aligned lines save them: c3, fp64: 0.47 -> 0.52 ms) meanwhile on threads of their own.  c2-real:
         // 87 ms one after the other (39 + 3 x ~16), ~45 ms this way.
-        const bool want_line_plans = !(flags & (WAGG_PLAN_NO_LINES | WAGG_PLAN_NO_LC | WAGG_PLAN_NO_STREAM)) && row_len < G && G % row_len == 0 &&
-                                     row_len % 4 == 0 && nnz > 0 && he == hipSuccess;
+        const bool want_line_plans = !(flags & (WAGG_PLAN_NO_LINES | WAGG_PLAN_NO_LC | WAGG_PLAN_NO_STREAM)) && lines_applicable(table) &&
+                                     he == hipSuccess;
         // (diagnostic build: WAGG_LINE_MULT = 2, 4, 8 makes the lines that many times longer and the chunk that many
         // times flatter -- 8 lines x 128 bytes by default, 1 x 1 KiB at the other end; 16: half lines (64 bytes), 16 per chunk)
         int mult = diag_env("WAGG_LINE_MULT");
         const bool half_lines = mult == 16;
         if (mult != 2 && mult != 4 && mult != 8) mult = 1;
-        struct LineJob { int line_cells, lines_per_chunk, kind; SparsePlanDev *d; bool ok = false; hipError_t he = hipSuccess; bool oom = false, failed = false; };
+        // (kind: 1 whole lines fp32, 2 whole lines fp64, 3 the 64-cell chunks of fp64 degree days; 0 = region-shaped, below)
+        struct LineJob { int line_cells, lines_per_chunk, kind; SparsePlanDev *d; bool ok = false; hipError_t he = hipSuccess; bool oom = false, failed = false; ChunkCounts n{}; };
         LineJob jobs[3] = {{half_lines ? 16 : 32 * mult, half_lines ? 16 : 8 / mult, 1, &plan->dl},
                            {half_lines ? 8 : 16 * mult, half_lines ? 16 : 8 / mult, 2, &plan->dl64},
                            {16, 4, 3, &plan->dl64e}};
@@ -2215,11 +1792,17 @@ extern "C" int wagg_plan_create(const int32_t *cell_idx, const int32_t *region_c
         // meets are noted in the job.  A thread that cannot be started (std::system_error: EAGAIN under a thread or process
         // limit -- every plan build asks for three, concurrent drop-in calls multiply that) means the job runs here, on the
         // calling thread, like all of them do under WAGG_PLAN_SERIAL_BUILD.  The joiner runs before anything leaves this
-        // scope, so no joinable thread is ever destroyed and `build` / `jobs` outlive every worker.
-        auto run_job = [&build](LineJob &j, int dev, bool set_device) noexcept {
+        // scope, so no joinable thread is ever destroyed and `table` / `jobs` outlive every worker.
+        auto run_job = [&](LineJob &j, int dev, bool set_device) noexcept {
             try {
                 if (set_device) j.he = hipSetDevice(dev);            // a new thread starts on device 0
-                if (j.he == hipSuccess) j.ok = build(j.line_cells, j.lines_per_chunk, j.kind, *j.d, j.he);
+                HostChunking c;
+                if (j.he != hipSuccess || !chunk_lines(table, j.line_cells, j.lines_per_chunk, knobs, c)) return;
+                finish_chunking(c, true, true);
+                j.n = counts_of(c);
+                plan_stats(j.n, j.line_cells, ChunkKnobs().band_rows, table.nnz);
+                j.he = upload_chunking(c, den, den32, true, *j.d);
+                j.ok = true;
             } catch (const std::bad_alloc &) { j.oom = true; }
             catch (...) { j.failed = true; }
         };
@@ -2241,7 +1824,15 @@ extern "C" int wagg_plan_create(const int32_t *cell_idx, const int32_t *region_c
                 if (!started) run_job(j, plan->device, false);
             }
         }
-        try { build(0, 0, 0, plan->d, he); } catch (const std::bad_alloc &) { oom = true; } catch (...) { failed = true; }
+        ChunkCounts n0{};
+        try {
+            HostChunking c;
+            chunk_regions(table, knobs, c);
+            finish_chunking(c, false, false);
+            n0 = counts_of(c);
+            plan_stats(n0, 0, knobs.band_rows, table.nnz);
+            if (he == hipSuccess) he = upload_chunking(c, den, den32, false, plan->d);
+        } catch (const std::bad_alloc &) { oom = true; } catch (...) { failed = true; }
         for (std::thread &w : workers.t) w.join();
         for (const LineJob &j : jobs) { if (he == hipSuccess) he = j.he; oom |= j.oom; failed |= j.failed; }
         if (failed) {
@@ -2249,6 +1840,8 @@ extern "C" int wagg_plan_create(const int32_t *cell_idx, const int32_t *region_c
             return WAGG_EINTERNAL;                                    // (plan_guard deletes the plan)
         }
         if (oom) throw std::bad_alloc();
+        fill_info(0, n0, plan->info);
+        for (const LineJob &j : jobs) if (j.ok) fill_info(j.kind, j.n, plan->info);
         if (want_line_plans && he == hipSuccess) {
             plan->has_lines = jobs[0].ok; plan->has_lines64 = jobs[1].ok; plan->has_lines64e = jobs[2].ok;
             plan->info.lines = (jobs[0].ok ? 1 : 0) | (jobs[1].ok ? 2 : 0) | (jobs[2].ok ? 4 : 0);
@@ -2601,9 +2194,11 @@ extern "C" int wagg_plan_create_many(const int32_t *cell_idx, const int32_t *reg
         // every check runs here, before any device call
         std::vector<uint8_t> kept((size_t)nseg, 0);       // a row is kept if some weighting keeps it
         for (int64_t i = 0; i < nseg; ++i) {
-            const int32_t r = region_code[i];
-            WAGG_REQUIRE(r < R, "region_code[%lld]=%d out of range [0,%d)", (long long)i, r, R);
-            WAGG_REQUIRE(cell_idx[i] >= 0 && cell_idx[i] < G, "cell_idx[%lld]=%d out of range", (long long)i, cell_idx[i]);
+            ChunkError bad;
+            if (!row_in_range(i, region_code[i], cell_idx[i], G, R, bad)) {
+                set_error("%s", bad.text.c_str());
+                return bad.code;
+            }
             bool any = false;
             for (int k = 0; k < K; ++k) any = any || !std::isnan(w_eff[k][i]);
             kept[(size_t)i] = any ? 1 : 0;

@@ -4,6 +4,7 @@
 #include <mutex>
 #include <vector>
 
+#include "wagg_chunk.h"
 #include "wagg_host.h"
 
 namespace wagg {
@@ -19,19 +20,11 @@ static inline constexpr int diag_env(const char *) { return 0; }
 static inline constexpr bool diag_set(const char *) { return false; }
 #endif
 
-constexpr int UC = 256;      // cell slots per LDS chunk == workgroup size
-constexpr int UQ = UC / 4;   // aligned 4-cell quads per chunk (one per lane of a wave)
+// (UC, UQ, RG_MAX, SEG_MAX, NWAVE, SWAVE and the seg_u / ucell flag bits: wagg_chunk.h)
 [[maybe_unused]] constexpr int UROW = UC + 4; // LDS row stride in elements (t-major image, 16-byte aligned rows): fp32, 260 dwords = 4 (mod 64)
 // the same for a type: fp64 rows of UC + 2 doubles are 516 dwords = 4 (mod 64) as well (UC + 4 doubles = 8 (mod 64) made a
 // lane = timestep column read 4-way conflicted: VERDICT r2 item 5); still 16-byte aligned for the vector stores
 template <typename T> constexpr int urow() { return sizeof(T) == 8 ? UC + 2 : UC + 4; }
-constexpr int RG_MAX = 127;  // regions per group
-constexpr int SEG_MAX = 512; // segments per chunk staged in LDS
-constexpr int UCELL_UNREF = 1;     // bit 0 of a ucell entry of a WHOLE-LINE chunking: the quad holds no referenced cell (wagg_sparse.hip)
-constexpr int SEG_LAST = 0x8000;   // flag bit in a segment's local cell index: last segment of its entry
-constexpr int SEG_UMASK = 0x7fff;
-constexpr int NWAVE = 4;      // waves of the chunk-walking kernel (256 threads)
-constexpr int SWAVE = 8;      // waves of the persistent stream kernel (512 threads)
 constexpr int STHREADS = SWAVE * 64;
 
 struct SparsePlanDev {
