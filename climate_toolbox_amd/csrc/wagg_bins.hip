@@ -45,17 +45,6 @@ template <typename T> struct BinThresholds {
     T c[WAGG_BIN_EDGES_MAX];
 };
 
-// the smallest value of T that is not below c (c is not NaN)
-template <typename T> static T ceil_to(double c) {
-    if constexpr (sizeof(T) == 8) {
-        return c;
-    } else {
-        float f = (float)c;                                          // (to nearest; +-inf and what overflows stay / become +-inf)
-        if ((double)f < c) f = std::nextafterf(f, HUGE_VALF);         // (-inf for c < -FLT_MAX steps to -FLT_MAX >= c)
-        return f;
-    }
-}
-
 // SEASON = false: doy / win are not read, every valid listed row counts.  DST = T: the finished counts go to `out`; DST = double:
 // the counts of part `s` go to `out` = the workspace (ldo = n, pstride = P * n), finished by rowlist_finish.
 template <typename T, int VEC, bool SEASON, typename DST>

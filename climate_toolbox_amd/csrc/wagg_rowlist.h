@@ -13,6 +13,7 @@
 #pragma once
 #include "wagg_common.h"
 
+#include <cmath>
 #include <type_traits>
 
 namespace wagg {
@@ -108,6 +109,18 @@ inline int rowlist_xf(int transform, double offset, int pow_first, int n_pow, co
     xf.pow_first = pow_first;
     for (int k = 0; k < RL_MAX_PLANES; ++k) xf.thr[k] = (T)(transform == WAGG_XF_EDD && k < n_thr ? thresholds[k] : 0.0);
     return WAGG_OK;
+}
+
+// the smallest value of T that is not below c (c is not NaN): the exact comparison of the bins and the spells, x >= ceil_to<T>(c)
+// for a value x of T exactly when (double)x >= c
+template <typename T> inline T ceil_to(double c) {
+    if constexpr (sizeof(T) == 8) {
+        return c;
+    } else {
+        float f = (float)c;                                          // (to nearest; +-inf and what overflows stay / become +-inf)
+        if ((double)f < c) f = std::nextafterf(f, HUGE_VALF);         // (-inf for c < -FLT_MAX steps to -FLT_MAX >= c)
+        return f;
+    }
 }
 
 // The checks every entry point makes, in the order it has always made them: the sizes first, then -- behind the entry point's

@@ -866,8 +866,8 @@ def _season_vector(a, length, what, device):
 
 
 class _RowlistCall:
-    """What the six row-list calls -- :func:`period_reduce`, :func:`season_reduce` and, through :func:`_grouped_reduce`,
-    :func:`edd_ladder_reduce`, :func:`exposure_reduce`, :func:`bin_days_reduce` and :func:`hinge_reduce` -- do alike around
+    """What the seven row-list calls -- :func:`period_reduce`, :func:`season_reduce` and, through :func:`_grouped_reduce`,
+    :func:`edd_ladder_reduce`, :func:`exposure_reduce`, :func:`bin_days_reduce`, :func:`hinge_reduce` and :func:`spell_reduce` -- do alike around
     their library call, in the order they do it: the row lists (and, with ``season = (doy, windows)``, those two vectors) as int32 CUDA tensors and ``P``;
     then ``out``, ``status`` and the workspace; at the end what must outlive the kernels on the caller's stream."""
 
@@ -988,8 +988,8 @@ def season_reduce(X, row_begin, rows, doy, windows, X2=None, poly=None, edd=None
 
 def _grouped_reduce(name, fields, row_begin, rows, doy, windows, checked, offset, middle, planes, work_bytes, out, status, workspace,
                     stream):
-    """What :func:`edd_ladder_reduce`, :func:`exposure_reduce`, :func:`bin_days_reduce` and :func:`hinge_reduce` do alike behind
-    their own validation: the doy / windows pairing, the :class:`_RowlistCall`, ``out`` / ``status`` / workspace, and the library call ``name`` + ``_f32``
+    """What :func:`edd_ladder_reduce`, :func:`exposure_reduce`, :func:`bin_days_reduce`, :func:`hinge_reduce` and
+    :func:`spell_reduce` do alike behind their own validation: the doy / windows pairing, the :class:`_RowlistCall`, ``out`` / ``status`` / workspace, and the library call ``name`` + ``_f32``
     or ``_f64`` by the dtype of ``fields`` (one checked (T, n) tensor, or tasmin and tasmax) -- the fields and the arguments
     every grouped entry point begins with (sizes, lists, season, ``offset``), the family's ``middle`` ones, and the ones every
     one ends with (flags, ``out`` and its strides, status, workspace, stream).  ``work_bytes(L, n, P, n_rows, planes)``: the
@@ -1096,6 +1096,44 @@ def bin_days_reduce(X, row_begin, rows, offset, edges, doy=None, windows=None, c
                            (_np_ptr(e, C.c_double), len(e)), len(e) - 1,
                            lambda L, n, P, n_rows, planes: L.wagg_bin_days_work_bytes(n, P, n_rows, planes + 1),      # (it takes n_edges)
                            out, status, True if workspace is None else workspace, stream)
+
+
+_SPELL_STATS = {"days": _lib.SPELL_DAYS, "events": _lib.SPELL_EVENTS, "longest": _lib.SPELL_LONGEST}
+
+
+def spell_reduce(X, row_begin, rows, offset, thresholds, min_length=1, stat="days", side="above", doy=None, windows=None, checked=False,
+                 out=None, status=None, stream=None):
+    """Runs of consecutive days past every threshold of a list, per period, in ONE launch (``wagg_spell_reduce_*``).  Entry ``i``
+    of period ``p``'s list is hot for cell ``j`` and threshold ``k`` when its row ``t`` lies in the field, the cell is in season
+    on ``doy[t]`` and ``X[t, j] + offset >= thresholds[k]`` (``side="above"``) or ``< thresholds[k]`` (``"below"``); a run is a
+    maximal stretch of hot entries whose row numbers ascend by one.  A gap in the row numbers, an out-of-season day, a NaN and
+    the end of the period's list end a run: runs are truncated at period boundaries.  ``out[k, p, j]`` is, by ``stat``:
+    ``"days"`` the hot entries in runs of at least ``min_length``, ``"events"`` the number of such runs, ``"longest"`` the
+    length of the longest run (``min_length`` must then be 1).  ``X``: a (T, n) CUDA tensor; ``thresholds``: 1 ..
+    ``_lib.SPELL_MAX`` finite numbers in any order, duplicates allowed (the kernel takes them ``_lib.SPELL_GROUP`` at a time);
+    ``min_length``: 1 .. ``_lib.SPELL_MIN_LENGTH_MAX``; ``row_begin`` / ``rows`` / ``doy`` / ``windows`` / ``checked`` as for
+    :func:`bin_days_reduce`.  The comparison is that of :func:`bin_thresholds`: the raw value against ``ceilT(thresholds[k] -
+    offset)``, so an fp32 field is classified as its exact values would be in fp64; NaN is never hot.  There is no workspace:
+    a run does not add across the parts of a list, so a period's list is never split.  Returns ``(counts, status)``: the
+    (n_thr, P, n) tensor of ``X``'s dtype (exact in fp32 up to 2^24) and the status word (bit 0: an in-season value was
+    +-inf, hot or not)."""
+    X = _check_X(X, "TG")
+    thr = np.ascontiguousarray(np.atleast_1d(thresholds), dtype=np.float64)
+    if thr.ndim != 1 or not 1 <= len(thr) <= _lib.SPELL_MAX:
+        raise ValueError("1..%d thresholds per call, got %s" % (_lib.SPELL_MAX, thr.shape))
+    if not np.isfinite(thr).all():
+        raise ValueError("thresholds must be finite, got %r" % (thr.tolist(),))
+    if stat not in _SPELL_STATS:
+        raise ValueError("stat must be 'days', 'events' or 'longest', got %r" % (stat,))
+    if side not in ("above", "below"):
+        raise ValueError("side must be 'above' or 'below', got %r" % (side,))
+    if isinstance(min_length, bool) or not isinstance(min_length, (int, np.integer)) or not 1 <= min_length <= _lib.SPELL_MIN_LENGTH_MAX:
+        raise ValueError("min_length must be an integer in 1..%d, got %r" % (_lib.SPELL_MIN_LENGTH_MAX, min_length))
+    if stat == "longest" and min_length != 1:
+        raise ValueError("stat='longest' does not use min_length: it must be 1, got %r" % (min_length,))
+    return _grouped_reduce("wagg_spell_reduce", (X,), row_begin, rows, doy, windows, checked, offset,
+                           (_np_ptr(thr, C.c_double), len(thr), int(min_length), _SPELL_STATS[stat], 0 if side == "above" else 1),
+                           len(thr), lambda L, *a: L.wagg_spell_work_bytes(*a), out, status, False, stream)
 
 
 def hinge_reduce(X, row_begin, rows, offset, knots, power=1, side="above", tail=None, doy=None, windows=None, checked=False, out=None,

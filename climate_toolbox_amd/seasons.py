@@ -34,6 +34,7 @@ from . import aggregations as _agg, engine as _engine, minixr
 from ._labels import _exact_index
 from ._layout import _flatten_for_device, _is_device_tensor, _result_dims, _spatial_layout, _to_device
 from ._lib import BIN_EDGES_MAX as _BIN_EDGES_MAX, EDD_LADDER_MAX as _EDD_LADDER_MAX, HINGE_MAX as _HINGE_MAX, SEASON_INVERT, SEASON_NULL
+from ._lib import SPELL_MAX as _SPELL_MAX
 from ._lib import EXPOSURE_EDGES_MAX as _EXPOSURE_EDGES_MAX
 from ._plans import _drop_plan, _plan_for
 from ._prepared import PreparedWeights
@@ -364,7 +365,7 @@ def _plain_variable(ds, variable, what):
 
 def _grouped_totals(ds, variable, aggwt, agglev, weights, backup_aggwt, lists, P, season, grid, time_values, cells, name, of, rule,
                     launches):
-    """The sum-first route of the grouped statistics (ladder, bins, hinges, exposure bins): every launch sums its planes per period
+    """The sum-first route of the grouped statistics (ladder, bins, hinges, exposure bins, spells): every launch sums its planes per period
     first, then one apply per launch contracts its planes * P rows on whatever plan serves the table.  ``name`` / ``of``: the statistic in
     the messages ("bin count" / "bins"); ``rule(ds, variable, what)``: ``(second field or None, offset)`` of a variable the
     statistic takes, ValueError for any other; ``launches``: an iterable, consumed as the launches run, of
@@ -456,3 +457,19 @@ def _hinge_totals(ds, variable, aggwt, agglev, weights, backup_aggwt, lists, P, 
 
     return _grouped_totals(ds, variable, aggwt, agglev, weights, backup_aggwt, lists, P, season, grid, time_values, cells, "hinge total",
                            "hinges", _plain_variable, launches())
+
+
+def _spell_totals(ds, variable, aggwt, agglev, weights, backup_aggwt, lists, P, thresholds, min_length, stat, side, season, grid,
+                  time_values, cells="all"):
+    """Period totals of the spell statistic ``stat`` of ``variable`` at EVERY threshold (``wagg_spell_reduce_*``, up to 64
+    thresholds a launch) through :func:`_grouped_totals`.  ``variable``: as for :func:`_bin_totals` (the thresholds are in degrees
+    C for a shifted one).  A run ends with its period's list: the regional value is the weighted mean of per-cell counts of runs
+    truncated there.  ``stack`` is the (n_thr, P | R, R | P) results in the thresholds' order."""
+    def launches():
+        for k0 in range(0, len(thresholds), _SPELL_MAX):
+            part = [float(t) for t in thresholds[k0:k0 + _SPELL_MAX]]
+            yield lambda X, H, rb, rw, offset, **kw: _engine.spell_reduce(X, rb, rw, offset, part, min_length=min_length, stat=stat,
+                                                                          side=side, **kw)
+
+    return _grouped_totals(ds, variable, aggwt, agglev, weights, backup_aggwt, lists, P, season, grid, time_values, cells, "spell count",
+                           "spells", _plain_variable, launches())

@@ -25,7 +25,7 @@ from . import aggregations as _agg
 
 __all__ = ["tas_poly", "tas_poly_aggregate", "snyder_edd", "snyder_gdd", "snyder_edd_aggregate", "snyder_exposure_aggregate",
            "tas_bins_aggregate",
-           "tas_hinge_aggregate", "tas_rcspline_aggregate",
+           "tas_hinge_aggregate", "tas_rcspline_aggregate", "tas_spell_aggregate",
            "validate_edd_snyder_agriculture", "ordinal", "remove_leap_days", "convert_kelvin_to_celsius"]
 
 KELVIN = 273.15
@@ -553,6 +553,77 @@ def tas_rcspline_aggregate(ds, knots, aggwt, agglev, weights, tas="tas", varname
     out = _agg._as_dataset({varname: res}, ("term",) + tuple(rdims), dict(coords, term=t[:-2].copy()), was_xr)
     out[varname].attrs["units"] = "{}^3".format(units)
     out[varname].attrs["knots"] = ", ".join(repr(float(x)) for x in t)
+    return out
+
+
+def _spell_thresholds(thresholds):
+    """``thresholds`` as a float64 vector in the caller's order: at least one finite number (duplicates allowed) -- else ValueError"""
+    try:
+        t = np.asarray(list(thresholds), dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError("thresholds must be a sequence of numbers, got %r" % (thresholds,)) from None
+    if t.ndim != 1 or len(t) < 1 or not np.isfinite(t).all():
+        raise ValueError("thresholds must be a non-empty sequence of finite numbers, got %r" % (thresholds,))
+    return t
+
+
+def tas_spell_aggregate(ds, thresholds, aggwt, agglev, weights, min_length=3, stat="days", side="above", tas="tas", varname="tas-spell",
+                        backup_aggwt="areawt", period="year", season=None, cells="all", leap_days="keep"):
+    """Spell statistics of a cell's daily temperature -- runs of consecutive days past a threshold -- per period (and growing
+    season), aggregated to regions: heat-wave and cold-spell days, the number of such events and the longest run (the ETCCDI /
+    xclim spell indices; ``tas="tasmax"``, threshold 35 C, ``min_length=3`` is the usual heat wave).  The one temperature
+    statistic here in which a day's contribution depends on its neighbours, counted on the device in ONE pass per 64 thresholds
+    (``wagg_spell_reduce_*``) instead of a run-length scan and a masked grid per threshold.
+
+    A day is hot for a threshold when ``tas >= threshold`` (``side="above"``) or ``tas < threshold`` (``"below"``); a run is a
+    maximal stretch of hot, in-season, CONSECUTIVE days of one period.  A missing day, a day out of season and a NaN end a run,
+    and so does the end of the period: RUNS ARE TRUNCATED AT PERIOD BOUNDARIES (a heat wave over New Year's Eve counts as one
+    run in each of the two years; with ``period="month"`` every month starts anew; with labels that join the Januaries of
+    several years, a run never reaches from one January into the next).  With ``leap_days="drop"`` 28 February and 1 March are consecutive.
+
+    thresholds  a non-empty sequence of finite numbers in any order, duplicates allowed, else ValueError; in degrees C when
+                ``ds[tas]`` carries the Kelvin shift of ``convert_kelvin_to_celsius``, otherwise in the field's own units.  More
+                than 64 go in several launches.  The comparison is the bins' exact one: an fp32 Kelvin field is classified as
+                its exact values would be in fp64 (``engine.bin_thresholds``).  NaN is never hot; a counted +-inf raises
+                ValueError.
+    min_length  an integer in 1..32767, else ValueError: the least length of a run that counts.
+    stat        "days": the days that belong to runs of at least ``min_length``; "events": the number of such runs; "longest":
+                the length of the longest run -- ``min_length`` is not used there, its default counts as unset, and any value
+                other than 1 or the default is ValueError.
+    side        "above" or "below", else ValueError.
+    tas         the variable (``"tasmax"`` for heat waves): a plain temperature field or a Kelvin-shifted one; a power
+                (``tas_poly``) or a degree-day variable is ValueError.
+    period      "year", "month" or a label per day; required (None is ValueError).
+    season, cells, leap_days   exactly as in :func:`tas_bins_aggregate`.
+
+    The regional value is the weighted mean of the per-cell counts (for "longest": of the per-cell longest runs).  Returns one
+    Dataset with the variable ``varname`` of dims ``("threshold", "period", agglev)`` (the last two in the order the period call
+    gives them), the coordinate ``threshold`` = the thresholds as float64 in the caller's order, ``attrs["units"]`` = ``"days"``
+    (days, longest) or ``"1"`` (events) and ``attrs["min_length"]`` (1 for "longest"), ``attrs["stat"]``, ``attrs["side"]``;
+    ``results_on_device()`` is honoured."""
+    t = _spell_thresholds(thresholds)
+    if stat not in ("days", "events", "longest"):
+        raise ValueError("stat must be 'days', 'events' or 'longest', got %r" % (stat,))
+    if side not in ("above", "below"):
+        raise ValueError("side must be 'above' or 'below', got %r" % (side,))
+    if isinstance(min_length, bool) or not isinstance(min_length, (int, np.integer)) or not 1 <= min_length <= 32767:
+        raise ValueError("min_length must be an integer in 1..32767, got %r" % (min_length,))
+    min_length = int(min_length)
+    if stat == "longest":
+        if min_length not in (1, 3):
+            raise ValueError("stat='longest' does not use min_length (leave it out, or pass 1), got %r" % (min_length,))
+        min_length = 1
+    re, _, weights, time_values, labels, grid, lists = _period_setup("tas_spell_aggregate", "a spell count", ds, tas, weights, period,
+                                                                     season, cells, leap_days)
+    from . import seasons
+    res, rdims, coords, was_xr = seasons._spell_totals(re, tas, aggwt, agglev, weights, backup_aggwt, lists, len(labels), t, min_length,
+                                                       stat, side, season, grid, time_values, cells=cells)
+    rdims, coords = _time_as_period(rdims, coords, labels)
+    out = _agg._as_dataset({varname: res}, ("threshold",) + tuple(rdims), dict(coords, threshold=t.copy()), was_xr)
+    out[varname].attrs["units"] = "1" if stat == "events" else "days"
+    out[varname].attrs["min_length"] = min_length
+    out[varname].attrs["stat"] = stat
+    out[varname].attrs["side"] = side
     return out
 
 

@@ -83,7 +83,8 @@ typedef struct wagg_plan_info {
 /* ---- process / device ------------------------------------------------------------------- */
 int wagg_version(void);                 /* 10000*major + 100*minor + patch; 0.4.0: sized struct getters, wagg_apply_desc,
                                            wagg_host_stats has 18 fields; 0.5.0: many-plans (wagg_plan_create_many);
-                                           0.9.0: packed rows (wagg_pack_rows_*, WAGG_APPLY_COMPACT_ROWS) */
+                                           0.9.0: packed rows (wagg_pack_rows_*, WAGG_APPLY_COMPACT_ROWS);
+                                           0.13.0: spell statistics (wagg_spell_reduce_*) */
 int wagg_device_count(void);            /* number of visible HIP devices (0 if none), never <0  */
 /* Time-axis sharding rule of the multi-GPU form (one process per GPU; climate_toolbox_amd/timeshard.py):
  * rank `rank` of `world` owns rows [*start, *stop) of T; the first T mod world ranks hold one row more. */
@@ -878,6 +879,52 @@ int wagg_exposure_reduce_f64(const double *tasmin_dev, const double *tasmax_dev,
                              int flags, double *out_dev, int64_t ldo, int64_t out_pstride, int32_t *status_dev, void *work_dev,
                              int64_t work_bytes, void *stream);
 int64_t wagg_exposure_work_bytes(int64_t n, int32_t P, int64_t n_rows, int n_edges);
+
+/* ---- spells: runs of consecutive days past a threshold, per period and season, in one pass (0.13.0) ---------------------------
+ * Heat-wave / cold-spell days, the number of such events and the longest run, for thresholds[k],  k = 0 .. n_thr - 1,
+ * 1 <= n_thr <= WAGG_SPELL_MAX -- one launch, the thresholds taken in groups of WAGG_SPELL_GROUP.  The one statistic of the
+ * row-list families in which a day's contribution depends on its neighbours.  Cell j, period p, threshold k: the entries i of
+ * rows[row_begin[p] : row_begin[p + 1]] are walked IN LIST ORDER.  Entry i is HOT when t = rows[i] lies in [0, T), cell j is in
+ * season on doy[t] (when a season is given) and  X[t, j] + offset >= thresholds[k]  (below = 0)  or  < thresholds[k]  (below = 1).
+ * A RUN is a maximal stretch of hot entries i, i + 1, ... with rows[i + 1] == rows[i] + 1.  A gap in the row numbers (a dropped
+ * row, another January of a month-of-all-years labelling), an out-of-season day, a NaN and the end of the period's list all end
+ * the run: RUNS ARE TRUNCATED AT PERIOD BOUNDARIES, a heat wave over New Year's Eve is one run in each of the two years.  With
+ * L = min_length, out[k][p][j] is
+ *   WAGG_SPELL_DAYS      the number of hot entries that belong to runs of length >= L
+ *   WAGG_SPELL_EVENTS    the number of runs of length >= L
+ *   WAGG_SPELL_LONGEST   the length of the longest run (min_length is not used and must be 1)
+ * Arguments as for wagg_bin_days_reduce_*, except
+ *   thresholds         n_thr finite host doubles in any order, duplicates allowed (the planes are independent); NaN or +-inf
+ *                      (a constant plane) is WAGG_EINVAL; in the units of X + offset
+ *   min_length         1..WAGG_SPELL_MIN_LENGTH_MAX;  stat: one of the three above;  below: 0 or 1
+ *   out_dev            plane k (a threshold) at out_dev + k * out_pstride, row p at + p * ldo (out_pstride >= P * ldo when
+ *                      n_thr > 1); the count as a value of the element type, exact in fp32 up to 2^24
+ *   work_dev, work_bytes   IGNORED.  A run does not add across the parts of a list, so this family never splits one:
+ *                      wagg_spell_work_bytes is 0.  (Combining parts through prefix / suffix / interior runs is not built; a
+ *                      single long period on a packed row therefore fills fewer blocks than the other families' launches.)
+ * THE COMPARISON RULE is the bins': the kernel compares the RAW X[t, j] against ceilT(thresholds[k] - offset), the difference
+ * formed in fp64, so an fp32 Kelvin field is classified as its exact values would be in fp64 -- x >= ceilT(c) exactly when
+ * (double)x >= c, and x < ceilT(c) exactly when (double)x < c.  NaN is never hot, on either side.  An IN-SEASON +-inf, hot or not,
+ * sets bit 0 of status_dev; a value out of season is cold and sets no status; a piece none of whose cells is in season is not
+ * read but still ends the runs.  Counts are integers: every run gives the same bits, and plane k of a many-threshold call is
+ * the plane of the call with thresholds[k] alone.                                                                              */
+#define WAGG_SPELL_MAX 64
+#define WAGG_SPELL_GROUP 8
+#define WAGG_SPELL_MIN_LENGTH_MAX 32767
+#define WAGG_SPELL_DAYS 0
+#define WAGG_SPELL_EVENTS 1
+#define WAGG_SPELL_LONGEST 2
+int wagg_spell_reduce_f32(const float *X_dev, int64_t T, int64_t n, int64_t ldx, const int32_t *row_begin_dev,
+                          const int32_t *rows_dev, int32_t P, int64_t n_rows, const int32_t *doy_dev, const int32_t *win_dev,
+                          double offset, const double *thresholds, int n_thr, int min_length, int stat, int below, int flags,
+                          float *out_dev, int64_t ldo, int64_t out_pstride, int32_t *status_dev, void *work_dev, int64_t work_bytes,
+                          void *stream);
+int wagg_spell_reduce_f64(const double *X_dev, int64_t T, int64_t n, int64_t ldx, const int32_t *row_begin_dev,
+                          const int32_t *rows_dev, int32_t P, int64_t n_rows, const int32_t *doy_dev, const int32_t *win_dev,
+                          double offset, const double *thresholds, int n_thr, int min_length, int stat, int below, int flags,
+                          double *out_dev, int64_t ldo, int64_t out_pstride, int32_t *status_dev, void *work_dev, int64_t work_bytes,
+                          void *stream);
+int64_t wagg_spell_work_bytes(int64_t n, int32_t P, int64_t n_rows, int n_thr);
 
 /* ---- packed rows: only the quads a segment table references, as a device matrix (0.9.0) ---------------------------------------
  * A single segment-table plan with a whole-line chunking (wagg_plan_info.lines) knows the distinct aligned 4-cell QUADS of a
