@@ -53,6 +53,7 @@ EXPORTS = (
     "wagg_hinge_reduce_f32", "wagg_hinge_reduce_f64", "wagg_hinge_work_bytes",
     "wagg_exposure_reduce_f32", "wagg_exposure_reduce_f64", "wagg_exposure_work_bytes",
     "wagg_spell_reduce_f32", "wagg_spell_reduce_f64", "wagg_spell_work_bytes",
+    "wagg_rolling_reduce_f32", "wagg_rolling_reduce_f64", "wagg_rolling_work_bytes",
     "wagg_plan_compact_info", "wagg_plan_compact_cells", "wagg_pack_rows_f32", "wagg_pack_rows_f64",
     "wagg_pack_rows_host_f32", "wagg_pack_rows_host_f64",
 )
@@ -76,6 +77,9 @@ EXPOSURE_EDGES_MAX, EXPOSURE_GROUP = 65, 8       # WAGG_EXPOSURE_*: bin edges a 
 SPELL_MAX, SPELL_GROUP = 64, 8                   # WAGG_SPELL_*: thresholds a call takes / the kernel's group size
 SPELL_MIN_LENGTH_MAX = 32767                     # ... the greatest min_length
 SPELL_DAYS, SPELL_EVENTS, SPELL_LONGEST = 0, 1, 2        # ... and the statistic of a call
+ROLL_WINDOW_MAX, ROLL_MAX_WINDOWS, ROLL_GROUP = 16, 8, 8 # WAGG_ROLL_*: the longest window in days / windows a call takes / a block serves
+ROLL_MAX, ROLL_MIN = 0, 1                        # ... the extreme of a call
+ROLL_MEAN, ROLL_SUM = 0, 1                       # ... and what it is the extreme of
 
 
 class HostStats(C.Structure):
@@ -313,6 +317,11 @@ def load():
                                      C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int64, C.c_int64, vp, vp, C.c_int64, vp]
     L.wagg_spell_work_bytes.argtypes = [C.c_int64, C.c_int32, C.c_int64, C.c_int]
     L.wagg_spell_work_bytes.restype = C.c_int64
+    for name in ("wagg_rolling_reduce_f32", "wagg_rolling_reduce_f64"):
+        getattr(L, name).argtypes = [vp, C.c_int64, C.c_int64, C.c_int64, vp, vp, C.c_int32, C.c_int64, vp, vp, C.c_double, i32p, C.c_int,
+                                     C.c_int, C.c_int, C.c_int, vp, C.c_int64, C.c_int64, vp, vp, C.c_int64, vp]
+    L.wagg_rolling_work_bytes.argtypes = [C.c_int64, C.c_int32, C.c_int64, C.c_int]
+    L.wagg_rolling_work_bytes.restype = C.c_int64
     for name in ("wagg_hinge_reduce_f32", "wagg_hinge_reduce_f64"):
         getattr(L, name).argtypes = [vp, C.c_int64, C.c_int64, C.c_int64, vp, vp, C.c_int32, C.c_int64, vp, vp, C.c_double, f64p, C.c_int,
                                      C.c_int, C.c_int, f64p, f64p, f64p, C.c_int, vp, C.c_int64, C.c_int64, vp, vp, C.c_int64, vp]
@@ -332,7 +341,7 @@ def load():
         fn = getattr(L, name)
         if name not in ("wagg_last_error", "wagg_scratch_bytes", "wagg_period_reduce_work_bytes", "wagg_season_reduce_work_bytes",
                         "wagg_edd_ladder_work_bytes", "wagg_bin_days_work_bytes", "wagg_hinge_work_bytes",
-                        "wagg_exposure_work_bytes", "wagg_spell_work_bytes"):
+                        "wagg_exposure_work_bytes", "wagg_spell_work_bytes", "wagg_rolling_work_bytes"):
             fn.restype = C.c_int
     _lib = L
     return L

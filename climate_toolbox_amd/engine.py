@@ -866,8 +866,8 @@ def _season_vector(a, length, what, device):
 
 
 class _RowlistCall:
-    """What the seven row-list calls -- :func:`period_reduce`, :func:`season_reduce` and, through :func:`_grouped_reduce`,
-    :func:`edd_ladder_reduce`, :func:`exposure_reduce`, :func:`bin_days_reduce`, :func:`hinge_reduce` and :func:`spell_reduce` -- do alike around
+    """What the eight row-list calls -- :func:`period_reduce`, :func:`season_reduce` and, through :func:`_grouped_reduce`,
+    :func:`edd_ladder_reduce`, :func:`exposure_reduce`, :func:`bin_days_reduce`, :func:`hinge_reduce`, :func:`spell_reduce` and :func:`rolling_reduce` -- do alike around
     their library call, in the order they do it: the row lists (and, with ``season = (doy, windows)``, those two vectors) as int32 CUDA tensors and ``P``;
     then ``out``, ``status`` and the workspace; at the end what must outlive the kernels on the caller's stream."""
 
@@ -988,8 +988,8 @@ def season_reduce(X, row_begin, rows, doy, windows, X2=None, poly=None, edd=None
 
 def _grouped_reduce(name, fields, row_begin, rows, doy, windows, checked, offset, middle, planes, work_bytes, out, status, workspace,
                     stream):
-    """What :func:`edd_ladder_reduce`, :func:`exposure_reduce`, :func:`bin_days_reduce`, :func:`hinge_reduce` and
-    :func:`spell_reduce` do alike behind their own validation: the doy / windows pairing, the :class:`_RowlistCall`, ``out`` / ``status`` / workspace, and the library call ``name`` + ``_f32``
+    """What :func:`edd_ladder_reduce`, :func:`exposure_reduce`, :func:`bin_days_reduce`, :func:`hinge_reduce`,
+    :func:`spell_reduce` and :func:`rolling_reduce` do alike behind their own validation: the doy / windows pairing, the :class:`_RowlistCall`, ``out`` / ``status`` / workspace, and the library call ``name`` + ``_f32``
     or ``_f64`` by the dtype of ``fields`` (one checked (T, n) tensor, or tasmin and tasmax) -- the fields and the arguments
     every grouped entry point begins with (sizes, lists, season, ``offset``), the family's ``middle`` ones, and the ones every
     one ends with (flags, ``out`` and its strides, status, workspace, stream).  ``work_bytes(L, n, P, n_rows, planes)``: the
@@ -1134,6 +1134,46 @@ def spell_reduce(X, row_begin, rows, offset, thresholds, min_length=1, stat="day
     return _grouped_reduce("wagg_spell_reduce", (X,), row_begin, rows, doy, windows, checked, offset,
                            (_np_ptr(thr, C.c_double), len(thr), int(min_length), _SPELL_STATS[stat], 0 if side == "above" else 1),
                            len(thr), lambda L, *a: L.wagg_spell_work_bytes(*a), out, status, False, stream)
+
+
+_ROLL_STATS = {"max": _lib.ROLL_MAX, "min": _lib.ROLL_MIN}
+_ROLL_OF = {"mean": _lib.ROLL_MEAN, "sum": _lib.ROLL_SUM}
+
+
+def rolling_reduce(X, row_begin, rows, offset, lengths, stat="max", of="mean", doy=None, windows=None, checked=False, out=None,
+                   status=None, stream=None):
+    """The greatest (``stat="max"``) or least (``"min"``) running mean (``of="mean"``) or sum (``"sum"``) over ``W`` consecutive
+    days, per period, for every ``W`` of ``lengths`` in ONE launch (``wagg_rolling_reduce_*``).  The window lengths are called
+    ``lengths`` here because ``windows`` is, as in every other row-list call, the vector of packed SEASON windows (with ``doy``).
+    Entry ``i`` of period ``p``'s list is valid for cell ``j`` when its row ``t`` lies in the field, the cell is in season on
+    ``doy[t]`` and ``X[t, j]`` is not NaN; a window of ``W`` days ends at entry ``i`` when the entries ``i - W + 1 .. i`` all lie
+    in this period's list, their row numbers ascend by one and all are valid.  A gap in the row numbers, an out-of-season day, a
+    NaN and the start of the list invalidate every window that would hold them: windows never reach across a period boundary.
+    The sum of a window is formed in fp64 from the raw elements, newest to oldest; ``out[k, p, j]`` is the extreme ``m`` of the
+    sums of the windows of ``lengths[k]`` days as ``m / W + offset`` (mean) or ``m + W * offset`` (sum), rounded once to ``X``'s
+    dtype -- and NaN when the period holds no valid window of that length for the cell.  ``X``: a (T, n) CUDA tensor;
+    ``lengths``: 1 .. ``_lib.ROLL_MAX_WINDOWS`` integers in 1 .. ``_lib.ROLL_WINDOW_MAX`` in any order, duplicates allowed;
+    ``row_begin`` / ``rows`` / ``doy`` / ``windows`` / ``checked`` as for :func:`spell_reduce`.  There is no workspace: a window
+    does not add across the parts of a list, so a period's list is never split.  Returns ``(out, status)``: the (n_win, P, n)
+    tensor and the status word (bit 0: an in-season value was +-inf)."""
+    X = _check_X(X, "TG")
+    try:
+        raw = list(np.atleast_1d(np.asarray(lengths, dtype=object)))
+    except (TypeError, ValueError):
+        raise ValueError("lengths must be a sequence of integers, got %r" % (lengths,)) from None
+    if not 1 <= len(raw) <= _lib.ROLL_MAX_WINDOWS:
+        raise ValueError("1..%d window lengths per call, got %d" % (_lib.ROLL_MAX_WINDOWS, len(raw)))
+    for w in raw:
+        if isinstance(w, (bool, np.bool_)) or not isinstance(w, (int, np.integer)) or not 1 <= w <= _lib.ROLL_WINDOW_MAX:
+            raise ValueError("a window length must be an integer in 1..%d, got %r" % (_lib.ROLL_WINDOW_MAX, w))
+    if stat not in _ROLL_STATS:
+        raise ValueError("stat must be 'max' or 'min', got %r" % (stat,))
+    if of not in _ROLL_OF:
+        raise ValueError("of must be 'mean' or 'sum', got %r" % (of,))
+    w32 = np.ascontiguousarray([int(w) for w in raw], dtype=np.int32)
+    return _grouped_reduce("wagg_rolling_reduce", (X,), row_begin, rows, doy, windows, checked, offset,
+                           (_np_ptr(w32, C.c_int32), len(w32), _ROLL_STATS[stat], _ROLL_OF[of]), len(w32),
+                           lambda L, *a: L.wagg_rolling_work_bytes(*a), out, status, False, stream)
 
 
 def hinge_reduce(X, row_begin, rows, offset, knots, power=1, side="above", tail=None, doy=None, windows=None, checked=False, out=None,

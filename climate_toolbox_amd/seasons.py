@@ -35,6 +35,7 @@ from ._labels import _exact_index
 from ._layout import _flatten_for_device, _is_device_tensor, _result_dims, _spatial_layout, _to_device
 from ._lib import BIN_EDGES_MAX as _BIN_EDGES_MAX, EDD_LADDER_MAX as _EDD_LADDER_MAX, HINGE_MAX as _HINGE_MAX, SEASON_INVERT, SEASON_NULL
 from ._lib import SPELL_MAX as _SPELL_MAX
+from ._lib import ROLL_MAX_WINDOWS as _ROLL_MAX_WINDOWS
 from ._lib import EXPOSURE_EDGES_MAX as _EXPOSURE_EDGES_MAX
 from ._plans import _drop_plan, _plan_for
 from ._prepared import PreparedWeights
@@ -365,7 +366,7 @@ def _plain_variable(ds, variable, what):
 
 def _grouped_totals(ds, variable, aggwt, agglev, weights, backup_aggwt, lists, P, season, grid, time_values, cells, name, of, rule,
                     launches):
-    """The sum-first route of the grouped statistics (ladder, bins, hinges, exposure bins, spells): every launch sums its planes per period
+    """The sum-first route of the grouped statistics (ladder, bins, hinges, exposure bins, spells, rolling extremes): every launch reduces its planes per period
     first, then one apply per launch contracts its planes * P rows on whatever plan serves the table.  ``name`` / ``of``: the statistic in
     the messages ("bin count" / "bins"); ``rule(ds, variable, what)``: ``(second field or None, offset)`` of a variable the
     statistic takes, ValueError for any other; ``launches``: an iterable, consumed as the launches run, of
@@ -473,3 +474,19 @@ def _spell_totals(ds, variable, aggwt, agglev, weights, backup_aggwt, lists, P, 
 
     return _grouped_totals(ds, variable, aggwt, agglev, weights, backup_aggwt, lists, P, season, grid, time_values, cells, "spell count",
                            "spells", _plain_variable, launches())
+
+
+def _rolling_totals(ds, variable, aggwt, agglev, weights, backup_aggwt, lists, P, lengths, stat, of, season, grid, time_values,
+                    cells="all"):
+    """Period extremes of the running ``of`` ("mean" / "sum") of ``variable`` over EVERY window length of ``lengths``
+    (``wagg_rolling_reduce_*``, up to 8 lengths a launch) through :func:`_grouped_totals`.  ``variable``: as for
+    :func:`_bin_totals`.  A window ends with its period's list; a cell without a valid window in a period is NaN there, which the
+    contraction treats as any NaN of a field (it counts 0, its weight stays in the denominator: DESIGN.md, S6).  ``stack`` is the
+    (n_win, P | R, R | P) results in the lengths' order."""
+    def launches():
+        for k0 in range(0, len(lengths), _ROLL_MAX_WINDOWS):
+            part = [int(w) for w in lengths[k0:k0 + _ROLL_MAX_WINDOWS]]
+            yield lambda X, H, rb, rw, offset, **kw: _engine.rolling_reduce(X, rb, rw, offset, part, stat=stat, of=of, **kw)
+
+    return _grouped_totals(ds, variable, aggwt, agglev, weights, backup_aggwt, lists, P, season, grid, time_values, cells,
+                           "rolling extreme", "rolling windows", _plain_variable, launches())

@@ -25,7 +25,7 @@ from . import aggregations as _agg
 
 __all__ = ["tas_poly", "tas_poly_aggregate", "snyder_edd", "snyder_gdd", "snyder_edd_aggregate", "snyder_exposure_aggregate",
            "tas_bins_aggregate",
-           "tas_hinge_aggregate", "tas_rcspline_aggregate", "tas_spell_aggregate",
+           "tas_hinge_aggregate", "tas_rcspline_aggregate", "tas_spell_aggregate", "tas_rolling_aggregate",
            "validate_edd_snyder_agriculture", "ordinal", "remove_leap_days", "convert_kelvin_to_celsius"]
 
 KELVIN = 273.15
@@ -624,6 +624,76 @@ def tas_spell_aggregate(ds, thresholds, aggwt, agglev, weights, min_length=3, st
     out[varname].attrs["min_length"] = min_length
     out[varname].attrs["stat"] = stat
     out[varname].attrs["side"] = side
+    return out
+
+
+def _rolling_windows(windows):
+    """``windows`` as an int64 vector in the caller's order: at least one integer in 1..16 (duplicates allowed; no bool, no
+    float) -- else ValueError"""
+    try:
+        raw = list(windows)
+    except TypeError:
+        raise ValueError("windows must be a sequence of integers in 1..16, got %r" % (windows,)) from None
+    if len(raw) < 1:
+        raise ValueError("windows must be a non-empty sequence of integers in 1..16, got %r" % (windows,))
+    for w in raw:
+        if isinstance(w, (bool, np.bool_)) or not isinstance(w, (int, np.integer)) or not 1 <= w <= 16:
+            raise ValueError("windows must be integers in 1..16 (days), got %r" % (w,))
+    return np.array([int(w) for w in raw], dtype=np.int64)
+
+
+def tas_rolling_aggregate(ds, windows, aggwt, agglev, weights, stat="max", of="mean", tas="tas", varname="tas-rolling",
+                          backup_aggwt="areawt", period="year", season=None, cells="all", leap_days="keep"):
+    """Rolling-window extremes of a cell's daily values per period (and growing season), aggregated to regions: the greatest or
+    least running mean (or sum) over ``W`` consecutive days, for every ``W`` of ``windows`` -- TXx / TNn (``W = 1`` of tasmax /
+    tasmin), the hottest or coldest N-day mean of heat-mortality and energy-peak studies, and with ``tas="pr", of="sum",
+    windows=[1, 5]`` the ETCCDI Rx1day / Rx5day.  Found on the device in ONE pass per 8 window lengths
+    (``wagg_rolling_reduce_*``) instead of a rolling mean, an ``amax`` per period and a full-size temporary per length.
+
+    A window of ``W`` days exists where ``W`` CONSECUTIVE days of one period are all present, in season and not NaN.  WINDOWS
+    NEVER REACH ACROSS A PERIOD BOUNDARY: a 5-day window ending on 2 January does not exist in the new year (it is no window of
+    the old year either); with ``period="month"`` every month starts anew, and with labels that join the Januaries of several
+    years no window reaches from one January into the next.  A missing day, a day out of season and a NaN rule out every window
+    that would hold them.  With ``leap_days="drop"`` 28 February and 1 March are consecutive.
+
+    A CELL WITHOUT A VALID WINDOW in a period (a period shorter than ``W``, a season shorter than ``W``, NaN throughout) has NO
+    VALUE there: it is NaN for that period and window, and the regional mean treats it as it treats any NaN of a field -- the cell
+    adds nothing and its weight stays in the denominator.  This is the one place where "no value" of this family
+    reaches the regional result.
+
+    THE REGIONAL VALUE IS THE WEIGHTED MEAN OF THE PER-CELL EXTREMES, not the extreme of the regional mean: every cell takes its
+    own hottest ``W`` days, which need not be the same days across a region.
+
+    windows   a non-empty sequence of integers in 1..16 (days) in any order, duplicates allowed; a bool, a float or anything
+              outside the range is ValueError.  More than 8 go in several launches.
+    stat      "max" or "min", else ValueError.
+    of        "mean" (the running mean) or "sum" (the running sum), else ValueError.  For a Kelvin-shifted variable the shift
+              is applied once to the result (``W`` times for a sum), never to single days; sums are formed in fp64.
+    tas       the variable: a plain field or a Kelvin-shifted one; a power (``tas_poly``) or a degree-day variable is ValueError.
+    period    "year", "month" or a label per day; required (None is ValueError).
+    season, cells, leap_days   exactly as in :func:`tas_bins_aggregate`.  A counted +-inf raises ValueError.
+
+    Returns one Dataset with the variable ``varname`` of dims ``("window", "period", agglev)`` (the last two in the order the
+    period call gives them), the coordinate ``window`` = the lengths as int64 in the caller's order, ``attrs["units"]`` = the
+    variable's units (``"C"`` when it carries the Kelvin shift), ``attrs["stat"]`` and ``attrs["of"]``; ``results_on_device()`` is
+    honoured."""
+    w = _rolling_windows(windows)
+    if stat not in ("max", "min"):
+        raise ValueError("stat must be 'max' or 'min', got %r" % (stat,))
+    if of not in ("mean", "sum"):
+        raise ValueError("of must be 'mean' or 'sum', got %r" % (of,))
+    re, var, weights, time_values, labels, grid, lists = _period_setup("tas_rolling_aggregate", "a rolling extreme", ds, tas, weights,
+                                                                       period, season, cells, leap_days)
+    from . import seasons
+    res, rdims, coords, was_xr = seasons._rolling_totals(re, tas, aggwt, agglev, weights, backup_aggwt, lists, len(labels), w, stat, of,
+                                                         season, grid, time_values, cells=cells)
+    rdims, coords = _time_as_period(rdims, coords, labels)
+    out = _agg._as_dataset({varname: res}, ("window",) + tuple(rdims), dict(coords, window=w.copy()), was_xr)
+    units = "C" if getattr(var, "_xform", None) is not None else _units(var)
+    if units is not None:
+        out[varname].attrs["units"] = units
+    out[varname].attrs["stat"] = stat
+    out[varname].attrs["of"] = of
     return out
 
 

@@ -84,7 +84,8 @@ typedef struct wagg_plan_info {
 int wagg_version(void);                 /* 10000*major + 100*minor + patch; 0.4.0: sized struct getters, wagg_apply_desc,
                                            wagg_host_stats has 18 fields; 0.5.0: many-plans (wagg_plan_create_many);
                                            0.9.0: packed rows (wagg_pack_rows_*, WAGG_APPLY_COMPACT_ROWS);
-                                           0.13.0: spell statistics (wagg_spell_reduce_*) */
+                                           0.13.0: spell statistics (wagg_spell_reduce_*);
+                                           0.14.0: rolling-window extremes (wagg_rolling_reduce_*) */
 int wagg_device_count(void);            /* number of visible HIP devices (0 if none), never <0  */
 /* Time-axis sharding rule of the multi-GPU form (one process per GPU; climate_toolbox_amd/timeshard.py):
  * rank `rank` of `world` owns rows [*start, *stop) of T; the first T mod world ranks hold one row more. */
@@ -925,6 +926,46 @@ int wagg_spell_reduce_f64(const double *X_dev, int64_t T, int64_t n, int64_t ldx
                           double *out_dev, int64_t ldo, int64_t out_pstride, int32_t *status_dev, void *work_dev, int64_t work_bytes,
                           void *stream);
 int64_t wagg_spell_work_bytes(int64_t n, int32_t P, int64_t n_rows, int n_thr);
+
+/* ---- rolling-window extremes: the greatest / least running sum or mean over W days, per period and season (0.14.0) -------------
+ * TXx / TNn (W = 1), the hottest or coldest N-day mean, Rx1day / Rx5day: the extreme over a period of the sum (or mean) of W
+ * consecutive days, for windows[k] days,  k = 0 .. n_win - 1,  1 <= n_win <= WAGG_ROLL_MAX_WINDOWS,  1 <= windows[k] <=
+ * WAGG_ROLL_WINDOW_MAX -- one launch, the field read once (WAGG_ROLL_GROUP windows a block).  Cell j, period p, window length W:
+ * the entries i of rows[row_begin[p] : row_begin[p + 1]] are walked IN LIST ORDER.  Entry i is VALID when t = rows[i] lies in
+ * [0, T), cell j is in season on doy[t] (when a season is given) and X[t, j] is not NaN.  A WINDOW of length W ends at entry i when
+ * the entries i - W + 1 .. i all lie in this period's list, rows[m + 1] == rows[m] + 1 along them, and all are valid.  A gap in
+ * the row numbers, an out-of-season day, a NaN and the start of the list invalidate every window that would hold them: WINDOWS
+ * NEVER REACH ACROSS A PERIOD BOUNDARY, a 5-day window ending on 2 January does not exist in the new year.  The window's sum is
+ * formed in fp64 from the raw elements, newest to oldest:  s = ((x[i] + x[i-1]) + x[i-2]) + ... + x[i-W+1].
+ *   WAGG_ROLL_MAX   m = -inf, then  m = s > m ? s : m  over the windows in list order;   WAGG_ROLL_MIN   +inf and <
+ *   WAGG_ROLL_MEAN  out[k][p][j] = (T)(m / (double)W + offset)        (division is monotone: the extreme of the means)
+ *   WAGG_ROLL_SUM   out[k][p][j] = (T)(m + (double)W * offset)        (the product formed on the host)
+ * one rounding from fp64 to the element type.  A period WITHOUT A VALID WINDOW for a cell (an empty list, one shorter than W,
+ * all gaps / out of season / NaN) gives NaN for that cell and window.
+ * Arguments as for wagg_spell_reduce_*, except
+ *   windows            n_win host int32 in 1..WAGG_ROLL_WINDOW_MAX, any order, duplicates allowed; plane k of out_dev is windows[k]
+ *   stat, of           WAGG_ROLL_MAX / _MIN, WAGG_ROLL_MEAN / _SUM; offset finite
+ *   work_dev, work_bytes   IGNORED.  A window does not add across the parts of a list, so this family never splits one:
+ *                      wagg_rolling_work_bytes is 0.
+ * An IN-SEASON +-inf sets bit 0 of status_dev; a value out of season is never looked at; a piece none of whose cells is in
+ * season is not read but still invalidates the windows over that day.  Every run gives the same bits, plane k of a many-window
+ * call is the plane of the call with windows[k] alone, and the results equal a NumPy restatement exactly (tests/rolling_ref.py). */
+#define WAGG_ROLL_WINDOW_MAX 16
+#define WAGG_ROLL_MAX_WINDOWS 8
+#define WAGG_ROLL_GROUP 8
+#define WAGG_ROLL_MAX 0
+#define WAGG_ROLL_MIN 1
+#define WAGG_ROLL_MEAN 0
+#define WAGG_ROLL_SUM 1
+int wagg_rolling_reduce_f32(const float *X_dev, int64_t T, int64_t n, int64_t ldx, const int32_t *row_begin_dev,
+                            const int32_t *rows_dev, int32_t P, int64_t n_rows, const int32_t *doy_dev, const int32_t *win_dev,
+                            double offset, const int32_t *windows, int n_win, int stat, int of, int flags, float *out_dev, int64_t ldo,
+                            int64_t out_pstride, int32_t *status_dev, void *work_dev, int64_t work_bytes, void *stream);
+int wagg_rolling_reduce_f64(const double *X_dev, int64_t T, int64_t n, int64_t ldx, const int32_t *row_begin_dev,
+                            const int32_t *rows_dev, int32_t P, int64_t n_rows, const int32_t *doy_dev, const int32_t *win_dev,
+                            double offset, const int32_t *windows, int n_win, int stat, int of, int flags, double *out_dev, int64_t ldo,
+                            int64_t out_pstride, int32_t *status_dev, void *work_dev, int64_t work_bytes, void *stream);
+int64_t wagg_rolling_work_bytes(int64_t n, int32_t P, int64_t n_rows, int n_win);
 
 /* ---- packed rows: only the quads a segment table references, as a device matrix (0.9.0) ---------------------------------------
  * A single segment-table plan with a whole-line chunking (wagg_plan_info.lines) knows the distinct aligned 4-cell QUADS of a
