@@ -17,10 +17,10 @@ constexpr int PK_UNROLL = 4;      // rows whose loads are in flight together
 
 // the chunking whose quads-only map serves element type `elem_bytes` (nullptr: the plan has none)
 const SparsePlanDev *compact_chunking(const wagg_plan *plan, int elem_bytes) {
-    if (plan->is_many() || (plan->flags & (WAGG_PLAN_NO_LC | WAGG_PLAN_NO_STREAM | WAGG_PLAN_LC_MFMA | WAGG_PLAN_NO_LINES))) return nullptr;
-    const bool has = elem_bytes == 4 ? plan->has_lines : plan->has_lines64;
-    const SparsePlanDev &d = elem_bytes == 4 ? plan->dl : plan->dl64;
-    if (!has || d.Gq <= 0 || d.run_len_q.empty() || d.n_groups - d.g0_normal <= 0 || d.g0_normal != 0) return nullptr;
+    if (plan->is_many()) return nullptr;
+    const int ch = route_lcv_lines(route_plan(plan), elem_bytes, false);       // (WAGG_PLAN_NO_LINES: the plan holds none)
+    const SparsePlanDev &d = chunking_of(plan, ch);
+    if (ch == CH_R || d.Gq <= 0 || d.run_len_q.empty() || d.n_groups - d.g0_normal <= 0 || d.g0_normal != 0) return nullptr;
     return &d;
 }
 

@@ -1216,18 +1216,8 @@ static int check_timeout(const wagg_plan *plan) {
     return WAGG_OK;
 }
 
-// ---- which kernel runs what (one table instead of an if-ladder; docs/HISTORY.md (d) carries the same table) -----------------
-// Single-chunk ("normal") groups of a plan, by (element type, data layout, transform):
-//   transform            (time, gridcell) data                          (gridcell, time) data
-//   none / one power     sparse_lcv_kernel<T,VEC,1>      [L32 | L64]    sparse_lcv_kernel<T,VEC,1,false,GT>    [R | L64]
-//   powers p..p+n-1 <= 4 sparse_lcv_kernel<T,VEC,n>      [L32 | L64]    sparse_lcv_kernel<T,VEC,n,false,GT>    [R | L64]
-//   degree days, k <= 4  sparse_lcv_kernel<T,VEC,k,EDD>  [L64 | L64e]   sparse_lcv_kernel<T,VEC,k,EDD,GT>      [L64 | L64e]
-// chunking in brackets, fp32 | fp64: R = region-shaped (<= 64 quads), L32 / L64 = eight whole 128-byte lines of 32 / 16
-// cells, L64e = four lines of 16 cells (both fp64 fields of a chunk in one image row).  Where the chunking named does not
-// exist (WAGG_PLAN_NO_LINES, a grid without a row length, a scattered table) or a WAGG_PLAN_NO_* flag says so: fp32 plain /
-// powers stay on sparse_lcv_kernel with R; everything else takes sparse_stream_kernel (no transform, one power per pass) or
-// the chunk-walking sparse_gather_kernel (degree days, (gridcell, time) data), which also serves every giant group.
-// More than four powers / thresholds: several passes.
+// ---- which kernel runs what: sparse_route (wagg_route.h; the kernel-by-route table stands above it in wagg_route.cpp) decides,
+// launch_sparse below launches what it says ------------------------------------------------------------------------------------
 template <typename T> struct LcvEntry {
     void (*kern)(PlanView<T>, const T *, int64_t, int64_t, int64_t, T *, int64_t, int, long long, unsigned long long *, int, int64_t, T);
     size_t lds;
@@ -1247,111 +1237,94 @@ template <typename T> static const LcvEntry<T> &lcv_pick(bool vec, bool edd, boo
 // the timesteps of one tile of the segment-table kernels (their TB), by element type: what every apply launches with
 template <typename T> constexpr int SEG_TB = sizeof(T) == 4 ? 64 : 32;
 
-template <typename T, int TB>
-static int launch_sparse(const wagg_plan *plan, const T *X, int64_t Ttot, int64_t ldx, int layout,
-                         T *out, int64_t ldo, int out_layout, hipStream_t stream, T xoff = T(0), int xpow = 0,
-                         int nfuse = 1, int64_t pstride = 0, const T *X2 = nullptr, const double *thr = nullptr,
-                         int n_thr = 0, int compact = COMPACT_NONE) {
-    // compact: X holds COMPACT rows of the lines-only host path -- COMPACT_LINES: ldx >= Gc cells, the distinct quads of the
-    // whole-line chunking side by side, read through ucell_c; COMPACT_QUADS: ldx >= Gq cells, only the quads a segment reads,
-    // through ucell_q -- (time, gridcell) data on that chunking
-    // nfuse > 1: powers xpow .. xpow + nfuse - 1 of (x + xoff) in one pass over X (fused tas_poly); the i-th goes to
-    // out + i * pstride.  sparse_lcv_kernel fuses up to four planes (powers or degree-day thresholds) in both element types and
-    // both layouts on the chunkings of the table above; everything it does not serve (giant groups, plans whose flags or
-    // table shape rule its chunkings out) runs once per power with the transform applied on load.
-    const bool lcv_off = (plan->flags & (WAGG_PLAN_NO_LC | WAGG_PLAN_NO_STREAM | WAGG_PLAN_LC_MFMA)) != 0;
-    // degree days in sparse_lcv_kernel: fp32 (time, gridcell) fields on the 128-cell chunking (the fp64 one: 64-byte pieces)
-    const bool edd_lcv = xpow == XF_EDD && (sizeof(T) == 4 ? plan->has_lines64 : plan->has_lines64e) && !lcv_off && n_thr >= 1 && n_thr <= 4;
-    const auto &d_edd = sizeof(T) == 4 ? plan->dl64 : plan->dl64e;     // chunks whose two fields fill one 64 KiB image
-    const bool use_lines = (edd_lcv && layout == WAGG_LAYOUT_TG) || ((sizeof(T) == 4 ? plan->has_lines : plan->has_lines64) && layout == WAGG_LAYOUT_TG &&
-                                       xpow != XF_EDD && (nfuse == 1 || (nfuse <= 4 && !lcv_off)));
-    // (gridcell, time) data in sparse_lcv_kernel: every cell of a chunk is fetched by itself (64 timesteps = two or four whole
-    // lines), so fp32 takes the region-shaped chunks (fewest cells); fp64 the 128-cell whole-line chunking (a region-shaped
-    // chunk holds 256)
-    const bool gt_lcv = layout == WAGG_LAYOUT_GT && !lcv_off && (xpow != XF_EDD || edd_lcv) && nfuse <= 4 &&
-                        (sizeof(T) == 4 || plan->has_lines64);
-    const auto &d = edd_lcv ? d_edd
-                            : (gt_lcv ? (sizeof(T) == 4 ? plan->d : plan->dl64) : (use_lines ? (sizeof(T) == 4 ? plan->dl : plan->dl64) : plan->d));
-    if (int rc = check_timeout(plan)) return rc;
-    const int64_t Gcomp = compact == COMPACT_QUADS ? d.Gq : d.Gc;
-    WAGG_REQUIRE(!compact || (use_lines && !lcv_off && nfuse <= 4 && (xpow != XF_EDD || edd_lcv) && Gcomp > 0 && ldx >= Gcomp),
-                 "compact rows need the whole-line chunking of this plan and data type");
-    const int64_t Gk = compact ? Gcomp : (int64_t)plan->info.G;        // cells of a row as the kernels see it
-    if (nfuse > 1) {
-        // fused: fp32 in either loader/consumer kernel; fp64 in sparse_lcv_kernel on its whole-line chunking
-        const bool lc_ok = ((layout == WAGG_LAYOUT_TG && (sizeof(T) == 4 || (use_lines && !lcv_off))) || gt_lcv) &&
-                           !(plan->flags & (WAGG_PLAN_NO_STREAM | WAGG_PLAN_NO_LC)) && (int)d.n_groups - d.g0_normal > 0 && Ttot > 0;
-        if (!lc_ok || nfuse > 4) {
-            for (int i = 0; i < nfuse; ++i) {
-                const int rc = launch_sparse<T, TB>(plan, X, Ttot, ldx, layout, out + (int64_t)i * pstride, ldo,
-                                                    out_layout, stream, xoff, xpow + i, 1, 0, nullptr, nullptr, 0, compact);
-                if (rc != WAGG_OK) return rc;
-            }
-            return WAGG_OK;
-        }
-    }
+// the arrays of a chunking that exist once per element type
+template <typename T> static const T *seg_w_of(const SparsePlanDev &d) { if constexpr (sizeof(T) == 4) return d.seg_w32.p; else return d.seg_w64.p; }
+template <typename T> static const T *den_of(const SparsePlanDev &d) { if constexpr (sizeof(T) == 4) return d.den32.p; else return d.den64.p; }
+template <typename T> static const T *ent_den_of(const SparsePlanDev &d) { if constexpr (sizeof(T) == 4) return d.ent_den32.p; else return d.ent_den64.p; }
+
+// chunking `d` as the kernels see it, its cells read through the map `compact` names; no transform, every group
+template <typename T> static PlanView<T> plan_view(const SparsePlanDev &d, int compact) {
     PlanView<T> pv;
-    pv.xoff = xoff; pv.xpow = xpow; pv.X2 = X2;
-    pv.n_thr = n_thr > 0 ? n_thr : 1;
-    for (int k = 0; k < 4; ++k) pv.edd_thr[k] = (T)(thr && k < n_thr ? thr[k] : 0.0);
-    // planes of output: powers of the fused tas_poly, or thresholds of one degree-day pass
-    const int nplanes = xpow == XF_EDD ? pv.n_thr : nfuse;
+    std::memset(&pv, 0, sizeof(pv));
+    pv.n_thr = 1;
     pv.grp_chunk_begin = d.grp_chunk_begin.p; pv.grp_giant = d.grp_giant.p;
     pv.chunk_u_begin = d.chunk_u_begin.p; pv.chunk_e_begin = d.chunk_e_begin.p;
-    pv.ucell = compact == COMPACT_QUADS ? d.ucell_q.p : (compact ? d.ucell_c.p : d.ucell.p); pv.ent_region = d.ent_region.p; pv.ent_seg_begin = d.ent_seg_begin.p;
-    pv.seg_u = d.seg_u.p;
-    if constexpr (sizeof(T) == 4) { pv.seg_w = d.seg_w32.p; pv.den = d.den32.p; pv.ent_den = d.ent_den32.p; }
-    else { pv.seg_w = d.seg_w64.p; pv.den = d.den64.p; pv.ent_den = d.ent_den64.p; }
+    pv.ucell = compact == COMPACT_QUADS ? d.ucell_q.p : (compact ? d.ucell_c.p : d.ucell.p);
+    pv.ent_region = d.ent_region.p; pv.ent_seg_begin = d.ent_seg_begin.p; pv.seg_u = d.seg_u.p;
+    pv.seg_w = seg_w_of<T>(d); pv.ent_den = ent_den_of<T>(d);
     // whole-line plan: an entry's "region" is its partial row and nothing is divided before the rows are combined
     // (ent_den holds one 1.0 per entry = per partial row)
-    if (d.n_part > 0) pv.den = pv.ent_den;
+    pv.den = d.n_part > 0 ? pv.ent_den : den_of<T>(d);
+    pv.chunk_desc = d.chunk_desc.p; pv.g0_normal = d.g0_normal; pv.c0_normal = d.c0_normal;
     pv.n_groups = (int)d.n_groups;
+    return pv;
+}
+
+// the kernels' aligned fast path: 16-byte aligned rows
+template <typename T> static bool rows_aligned16(const T *X, int64_t ldx) {
+    return (reinterpret_cast<uintptr_t>(X) & 15) == 0 && (ldx * sizeof(T)) % 16 == 0;
+}
+
+// One apply as launch_sparse takes it.  xf: powers first .. first + count - 1 of (x + xoff) in one pass over X (fused tas_poly),
+// the i-th to out + i * pstride; degree days of (X = tasmin, X2 = tasmax) + xoff at thr[0 .. count - 1], likewise.
+// compact: X holds COMPACT rows of the lines-only host path -- COMPACT_LINES: ldx >= Gc cells, the distinct quads of the
+// whole-line chunking side by side, read through ucell_c; COMPACT_QUADS: ldx >= Gq cells, only the quads a segment reads,
+// through ucell_q -- (time, gridcell) data on that chunking
+template <typename T> struct SparseCall {
+    const T *X;
+    int64_t Ttot, ldx;
+    int layout;
+    T *out;
+    int64_t ldo;
+    int out_layout;
+    hipStream_t stream;
+    T xoff = T(0);
+    RouteTransform xf{};
+    int64_t pstride = 0;
+    const T *X2 = nullptr;
+    const double *thr = nullptr;
+    int compact = COMPACT_NONE;
+};
+
+// one pass of route `r` (of a single power where r.per_power): fill the view, launch what the route says
+template <typename T, int TB>
+static int run_route(const wagg_plan *plan, const SparseCall<T> &c, const SparseRoute &r) {
+    const SparsePlanDev &d = chunking_of(plan, r.chunking);
+    const T *X = c.X;
+    const int64_t Ttot = c.Ttot, ldx = c.ldx, pstride = c.pstride;
+    const hipStream_t stream = c.stream;
+    const bool edd = c.xf.kind == RX_EDD;
+    const int xpow = edd ? XF_EDD : (c.xf.kind == RX_POWERS ? c.xf.first : 0), nfuse = c.xf.kind == RX_POWERS ? c.xf.count : 1;
+    const int nplanes = r.nplanes;            // powers of the fused tas_poly, or thresholds of one degree-day pass
+    PlanView<T> pv = plan_view<T>(d, c.compact);
+    pv.xoff = c.xoff; pv.xpow = xpow; pv.X2 = c.X2;
+    if (edd) pv.n_thr = nplanes;
+    for (int k = 0; k < 4; ++k) pv.edd_thr[k] = (T)(edd && c.thr && k < c.xf.count ? c.thr[k] : 0.0);
     if (Ttot == 0) return WAGG_OK;
+    const int64_t Gk = c.compact ? (c.compact == COMPACT_QUADS ? d.Gq : d.Gc) : (int64_t)plan->info.G;        // cells of a row as the kernels see it
     const int64_t n_tb = (Ttot + TB - 1) / TB;
-    // (T x R) results: gather kernel writes region-major into a stream-ordered workspace, then
-    // one transpose; (R x T) results go straight to the caller's buffer
+    // (T x R) results: the kernels write region-major into a stream-ordered workspace, then one transpose; whole-line plans:
+    // PARTIAL rows into the workspace whatever the output layout (wagg_route.cpp); everything else straight to the caller's buffer
     T *ws = nullptr;
     int64_t ldws = 0;
-    T *kout = out;
-    int64_t kldo = ldo;
-    // whole-line plans: the kernels write PARTIAL rows (one per (chunk, region) entry) into the workspace whatever the
-    // output layout; combine_parts_kernel sums a region's rows, divides and (for (T x R)) transposes
-    const bool lines = d.n_part > 0;
-    const bool via_ws = (out_layout == WAGG_OUT_TR || lines) && d.n_groups > 0;
-    const int64_t ws_rows = lines ? d.n_part : (int64_t)plan->info.R;
+    T *kout = c.out;
+    int64_t kldo = c.ldo;
     int64_t kpstride = pstride;
-    if (via_ws) {
+    if (r.via_ws) {
         ldws = (Ttot + 63) / 64 * 64;
-        ws = static_cast<T *>(plan->staging(stream, sizeof(T) * (size_t)(ldws * ws_rows) * (size_t)nplanes));
-        if (!ws) { set_error("staging buffer of %.1f MB: allocation failed", (double)(sizeof(T) * ldws * ws_rows * nplanes) * 1e-6); return WAGG_ENOMEM; }
+        ws = static_cast<T *>(plan->staging(stream, sizeof(T) * (size_t)(ldws * r.ws_rows) * (size_t)nplanes));
+        if (!ws) { set_error("staging buffer of %.1f MB: allocation failed", (double)(sizeof(T) * ldws * r.ws_rows * nplanes) * 1e-6); return WAGG_ENOMEM; }
         kout = ws;
         kldo = ldws;
-        kpstride = ldws * ws_rows;
+        kpstride = ldws * r.ws_rows;
     }
-    pv.chunk_desc = d.chunk_desc.p; pv.g0_normal = d.g0_normal; pv.c0_normal = d.c0_normal;
-    // aligned fast path: 16-byte aligned rows
-    const bool vec = ((reinterpret_cast<uintptr_t>(X) & 15) == 0) && ((ldx * sizeof(T)) % 16 == 0) &&
-                     (xpow != XF_EDD || (reinterpret_cast<uintptr_t>(X2) & 15) == 0);
-    // sparse_stream_kernel and sparse_gather_kernel fetch a quad as FOUR elements in one load: 32 bytes of a fp64 row, whose
-    // 16-byte alignment says nothing about G % 4.  With ldx == G and G % 4 == 2 the region-shaped chunking's last quad
-    // (cells G - 2, G - 1) would be read two elements past the end of the last row: such grids take the clamped arm.
-    // (fp32: aligned rows have ldx % 4 == 0, so a quad never leaves its row.  sparse_lcv_kernel loads 16-byte pieces.)
-    const bool vec_quad = vec && (sizeof(T) == 4 || plan->info.G % 4 == 0);
-    // degree days (two fields): fp32 (time, gridcell) data in the loader/consumer kernel, everything else in the
-    // chunk-walking kernel
-    const bool edd = xpow == XF_EDD;
-    const bool stream_path = (layout == WAGG_LAYOUT_TG || gt_lcv) && !(plan->flags & WAGG_PLAN_NO_STREAM) && (!edd || sizeof(T) == 4 || edd_lcv);
     const int n_norm = (int)d.n_groups - d.g0_normal;
-    bool lc_done = false;
-    // plain aggregation: loaders + vector-ALU consumers (sparse_lcv_kernel).  fp32 on either chunking, fp64 on its
-    // whole-line chunking only (a region-shaped chunk of 64 quads is 2 KiB of a fp64 row: twice the image row)
-    if (!lc_done && stream_path && n_norm > 0 && !(plan->flags & (WAGG_PLAN_NO_LC | WAGG_PLAN_LC_MFMA)) && (!edd || edd_lcv) && nfuse <= 4 &&
-        (sizeof(T) == 4 || lines)) {
+    if (r.main == MAIN_LCV) {                 // loaders + vector-ALU consumers, one workgroup per CU
         const int ncu = plan->ncu;
         const long long n_items = (long long)n_norm * ((Ttot + LV_TB - 1) / LV_TB);
         long long nw = n_items < ncu ? n_items : ncu;
         if (const int v = diag_env("WAGG_LCV_NW")) { if (v >= 1 && v < nw) nw = v; }      // (diagnostic build: fewer workgroups = CUs)
-        const LcvEntry<T> &ke = lcv_pick<T>(vec, edd_lcv, gt_lcv, edd_lcv ? pv.n_thr : nfuse);
+        const LcvEntry<T> &ke = lcv_pick<T>(r.vec, r.edd, r.gt, r.planes);
         const auto kern = ke.kern;
         const size_t lds_bytes = ke.lds;
         // |y| below this can be raised to the highest power of the pass inside T
@@ -1365,26 +1338,23 @@ static int launch_sparse(const wagg_plan *plan, const T *X, int64_t Ttot, int64_
 #ifdef WAGG_DIAG
         if (lc_stamps) { if (int rc = report_lc_stamps(lc_stamps, nw, n_items, stream)) return rc; }
 #endif
-        pv.n_groups = d.g0_normal;
-        lc_done = true;
     }
 #ifdef WAGG_DIAG
     if constexpr (sizeof(T) == 4) {
         // (diagnostic build, wagg_sparse_diag.hip) plans created with WAGG_PLAN_LC_MFMA: the MFMA-consumer kernel
-        if (stream_path && n_norm > 0 && !lc_done && (plan->flags & WAGG_PLAN_LC_MFMA) && !(plan->flags & WAGG_PLAN_NO_LC)) {
-            if (int rc = launch_lc_mfma(plan, pv, X, Ttot, ldx, kout, kldo, n_norm, vec, edd, xpow, nfuse, kpstride, stream)) return rc;
-            pv.n_groups = d.g0_normal;
-            lc_done = true;
-        }
+        if (r.main == MAIN_LC_MFMA)
+            if (int rc = launch_lc_mfma(plan, pv, X, Ttot, ldx, kout, kldo, n_norm, r.vec, edd, xpow, nfuse, kpstride, stream)) return rc;
     }
+#else
+    WAGG_REQUIRE(r.main != MAIN_LC_MFMA, "WAGG_PLAN_LC_MFMA: the MFMA-consumer kernel lives in the diagnostic build (libwagg_diag.so) only");
 #endif
-    if (stream_path && n_norm > 0 && !lc_done && !edd) {
+    if (r.main == MAIN_STREAM) {
         // persistent pipelined kernel over the single-chunk groups; two workgroups per CU
         const int ncu = plan->ncu;
         const long long n_items = (long long)n_norm * n_tb;
         const long long nw = n_items < 2LL * ncu ? n_items : 2LL * ncu;
         const size_t shmem = SparseLds<T, TB>::total;
-        auto kern = vec_quad ? sparse_stream_kernel<T, TB, true> : sparse_stream_kernel<T, TB, false>;
+        auto kern = r.vec ? sparse_stream_kernel<T, TB, true> : sparse_stream_kernel<T, TB, false>;
         unsigned long long *stamps = nullptr;
         const bool do_stamp = diag_set("WAGG_SPARSE_STAMP");
 #ifdef WAGG_DIAG
@@ -1409,13 +1379,12 @@ static int launch_sparse(const wagg_plan *plan, const T *X, int64_t Ttot, int64_
                     n_items, nw, sum[0] / stages, sum[1] / stages, sum[6] / stages, sum[7] / stages, sum[8] / stages, sum[2] / stages,
                     sum[3] / stages, (sum[4] + sum[9]) / stages, sum[9] / stages, sum[5] / stages);
         }
-        pv.n_groups = d.g0_normal;          // what is left for the chunk-walking kernel: giant groups
-        lc_done = true;                     // (a dominant kernel has been launched and timed)
     }
-    const bool main_done = lc_done;
-    WAGG_REQUIRE(!compact || (lc_done && pv.n_groups == 0), "compact rows: the whole-line kernel did not take the whole plan");
+    const bool main_done = r.main != MAIN_NONE;       // (a dominant kernel has been launched and timed)
+    WAGG_REQUIRE(r.refuse != REFUSE_COMPACT_NOT_WHOLE, "%s", route_refusal_text(r.refuse));
+    pv.n_groups = r.gather_groups;            // what is left for the chunk-walking kernel: giant groups, or every group
     pv.thr_pstride = kpstride;
-    for (int pz = 0; pz < nfuse; ++pz) {      // per power: the groups the kernels above left over (giant ones)
+    for (int pz = 0; pz < nfuse; ++pz) {      // per power: the groups the kernels above left over
     if (nfuse > 1) pv.xpow = xpow + pz;
     if (pv.n_groups > 0) {
         const int64_t nblk = (int64_t)pv.n_groups * n_tb;
@@ -1425,47 +1394,60 @@ static int launch_sparse(const wagg_plan *plan, const T *X, int64_t Ttot, int64_
 #define WAGG_LAUNCH(L, O, V)                                                                    \
         do {                                                                                     \
             auto kern = sparse_gather_kernel<T, TB, L, O, V>;                                    \
-            if (xpow == XF_EDD && pv.n_thr > 1) kern = sparse_gather_kernel<T, TB, L, O, V, 0, 4>; \
+            if (r.gather_nthr == 4) kern = sparse_gather_kernel<T, TB, L, O, V, 0, 4>;           \
             WAGG_DIAG_GATHER_VARIANTS(L, O, V)                                                   \
             WAGG_HIP(allow_dynamic_lds((const void *)kern, shmem));                              \
             launch_timed(!main_done, kern, grid, block, shmem, stream, pv, X, Ttot, ldx,         \
                          (int64_t)plan->info.G, kout + (int64_t)pz * kpstride, kldo);            \
         } while (0)
-        if (layout == WAGG_LAYOUT_TG) { if (vec_quad) WAGG_LAUNCH(WAGG_LAYOUT_TG, WAGG_OUT_RT, true); else WAGG_LAUNCH(WAGG_LAYOUT_TG, WAGG_OUT_RT, false); }
+        if (c.layout == WAGG_LAYOUT_TG) { if (r.gather_vec) WAGG_LAUNCH(WAGG_LAYOUT_TG, WAGG_OUT_RT, true); else WAGG_LAUNCH(WAGG_LAYOUT_TG, WAGG_OUT_RT, false); }
         else WAGG_LAUNCH(WAGG_LAYOUT_GT, WAGG_OUT_RT, false);
 #undef WAGG_LAUNCH
         WAGG_HIP(hipGetLastError());
     }
     }
-    if (via_ws && lines) {                    // all planes in one launch (regions without rows come out as 0 / den there)
+    if (r.finish & FIN_COMBINE) {             // all planes in one launch (regions without rows come out as 0 / den there)
         dim3 tg((unsigned)((plan->info.R + 63) / 64), (unsigned)((Ttot + 63) / 64), (unsigned)nplanes);
-        const T *den;
-        if constexpr (sizeof(T) == 4) den = d.den32.p; else den = d.den64.p;
-        if (out_layout == WAGG_OUT_TR)
-            hipLaunchKernelGGL((combine_parts_kernel<T, true>), tg, dim3(CB_THREADS), 0, stream, (const T *)ws, ldws,
-                               (const int32_t *)d.part_begin.p, den, (int64_t)plan->info.R, Ttot, out, ldo, kpstride, pstride);
-        else
-            hipLaunchKernelGGL((combine_parts_kernel<T, false>), tg, dim3(CB_THREADS), 0, stream, (const T *)ws, ldws,
-                               (const int32_t *)d.part_begin.p, den, (int64_t)plan->info.R, Ttot, out, ldo, kpstride, pstride);
+        auto ck = c.out_layout == WAGG_OUT_TR ? combine_parts_kernel<T, true> : combine_parts_kernel<T, false>;
+        hipLaunchKernelGGL(ck, tg, dim3(CB_THREADS), 0, stream, (const T *)ws, ldws, (const int32_t *)d.part_begin.p, den_of<T>(d),
+                           (int64_t)plan->info.R, Ttot, c.out, c.ldo, kpstride, pstride);
         WAGG_HIP(hipGetLastError());
         return WAGG_OK;
     }
     for (int pz = 0; pz < nplanes; ++pz) {    // per plane: transpose, regions without any kept row
-    if (via_ws) {
+    if (r.finish & FIN_TRANSPOSE) {
         dim3 tg((unsigned)((plan->info.R + 63) / 64), (unsigned)((Ttot + 63) / 64));
         hipLaunchKernelGGL((transpose_rt_to_tr_kernel<T>), tg, dim3(256), 0, stream, ws + (int64_t)pz * kpstride, ldws,
-                           (int64_t)plan->info.R, Ttot, out + (int64_t)pz * pstride, ldo);
+                           (int64_t)plan->info.R, Ttot, c.out + (int64_t)pz * pstride, c.ldo);
         WAGG_HIP(hipGetLastError());
     }
-    if (d.n_empty > 0) {
+    if (r.finish & FIN_FILL) {
         const int64_t n = d.n_empty * Ttot;
-        const T *den;
-        if constexpr (sizeof(T) == 4) den = d.den32.p; else den = d.den64.p;
         hipLaunchKernelGGL((fill_empty_kernel<T>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
-                           stream, d.empty_regions.p, (int)d.n_empty, den, Ttot, out + (int64_t)pz * pstride, ldo,
-                           out_layout);
+                           stream, d.empty_regions.p, (int)d.n_empty, den_of<T>(d), Ttot, c.out + (int64_t)pz * pstride, c.ldo,
+                           c.out_layout);
         WAGG_HIP(hipGetLastError());
     }
+    }
+    return WAGG_OK;
+}
+
+template <typename T, int TB>
+static int launch_sparse(const wagg_plan *plan, const SparseCall<T> &c) {
+    RouteCall rc;
+    rc.elem = (int)sizeof(T); rc.layout = c.layout; rc.out_layout = c.out_layout; rc.xf = c.xf; rc.compact = c.compact;
+    rc.ldx = c.ldx; rc.Ttot = c.Ttot;
+    rc.aligned16 = rows_aligned16(c.X, c.ldx) && (c.xf.kind != RX_EDD || (reinterpret_cast<uintptr_t>(c.X2) & 15) == 0);
+    const SparseRoute r = sparse_route(route_plan(plan), rc);
+    if (int err = check_timeout(plan)) return err;
+    WAGG_REQUIRE(r.refuse != REFUSE_COMPACT_CHUNKING, "%s", route_refusal_text(r.refuse));
+    if (!r.per_power) return run_route<T, TB>(plan, c, r);
+    SparseCall<T> one = c;                    // the fused kernels do not take this call: one pass per power
+    one.xf.count = 1; one.pstride = 0;
+    for (int i = 0; i < c.xf.count; ++i) {
+        one.xf.first = c.xf.first + i; one.out = c.out + (int64_t)i * c.pstride;
+        if (int err = check_timeout(plan)) return err;
+        if (int err = run_route<T, TB>(plan, one, r)) return err;
     }
     return WAGG_OK;
 }
@@ -1540,9 +1522,7 @@ template <typename T> static LcvEntry<T> lcv_many_pick(bool vec, int nw) {
 // the weightings of a many-plan share one pass over X: (time, gridcell) data on the whole-line chunking of T, the
 // loader/consumer kernel allowed by the plan's flags.  Anything else runs the single-plan path once per weighting.
 template <typename T> static bool many_fused(const wagg_plan *plan, int layout) {
-    const wagg_plan *p0 = plan->many_w[0];
-    return layout == WAGG_LAYOUT_TG && (sizeof(T) == 4 ? p0->has_lines : p0->has_lines64) &&
-           !(p0->flags & (WAGG_PLAN_NO_LC | WAGG_PLAN_NO_STREAM | WAGG_PLAN_LC_MFMA));
+    return layout == WAGG_LAYOUT_TG && route_lcv_lines(route_plan(plan->many_w[0]), (int)sizeof(T), false) != CH_R;
 }
 
 // out: the concatenated result (plane (l, k) at column / row many_col(l, k)); compact: as in launch_sparse
@@ -1557,38 +1537,29 @@ static int launch_many(const wagg_plan *plan, const T *X, int64_t Ttot, int64_t 
             set_error("many-plan with derived levels: they need %s (time, gridcell) data on the plan's whole-line chunking%s",
                       sizeof(T) == 4 ? "fp32" : "fp64",
                       layout != WAGG_LAYOUT_TG ? " -- this is (gridcell, time) data"
-                      : (p0->flags & (WAGG_PLAN_NO_LC | WAGG_PLAN_NO_STREAM | WAGG_PLAN_LC_MFMA)) ? " -- the plan's flags rule its kernel out"
+                      : route_lcv_off(p0->flags) ? " -- the plan's flags rule its kernel out"
                                                                                                   : " -- the table has none (no row length, or too scattered)");
             return WAGG_EUNSUPPORTED;
         }
         WAGG_REQUIRE(!compact, "compact rows need the whole-line chunking of this plan and data type");
         for (int k = 0; k < K; ++k)     // the single-plan kernels with weighting k's weights and den: the same bits as its own plan
-            if (int rc = launch_sparse<T, TB>(plan->many_w[k], X, Ttot, ldx, layout, plane(0, k), ldo, out_layout, stream)) return rc;
+            if (int rc = launch_sparse<T, TB>(plan->many_w[k], {X, Ttot, ldx, layout, plane(0, k), ldo, out_layout, stream})) return rc;
         return WAGG_OK;
     }
     if (Ttot == 0) return WAGG_OK;
-    auto chunking = [&](const wagg_plan *p) -> const SparsePlanDev & { return sizeof(T) == 4 ? p->dl : p->dl64; };
-    const SparsePlanDev &d = chunking(p0);
+    const int ch = route_lcv_lines(route_plan(p0), (int)sizeof(T), false);
+    const SparsePlanDev &d = chunking_of(p0, ch);
     WAGG_REQUIRE(d.n_part > 0, "many-plan: the whole-line chunking has no partial rows");
     const int64_t Gcomp = compact == COMPACT_QUADS ? d.Gq : d.Gc;
     WAGG_REQUIRE(!compact || (Gcomp > 0 && ldx >= Gcomp && d.g0_normal == 0), "compact rows: the whole-line kernel does not take the whole plan");
     const int64_t Gk = compact ? Gcomp : (int64_t)p0->info.G;
-    auto wts = [&](int k) -> const T * { if constexpr (sizeof(T) == 4) return chunking(plan->many_w[k]).seg_w32.p; else return chunking(plan->many_w[k]).seg_w64.p; };
-    auto den_fine = [&](int k) -> const T * { if constexpr (sizeof(T) == 4) return chunking(plan->many_w[k]).den32.p; else return chunking(plan->many_w[k]).den64.p; };
-    PlanView<T> pv;
-    std::memset(&pv, 0, sizeof(pv));
-    pv.xoff = T(0); pv.xpow = 0; pv.X2 = nullptr; pv.n_thr = 1;
-    pv.grp_chunk_begin = d.grp_chunk_begin.p; pv.grp_giant = d.grp_giant.p;
-    pv.chunk_u_begin = d.chunk_u_begin.p; pv.chunk_e_begin = d.chunk_e_begin.p;
-    pv.ucell = compact == COMPACT_QUADS ? d.ucell_q.p : (compact ? d.ucell_c.p : d.ucell.p);
-    pv.ent_region = d.ent_region.p; pv.ent_seg_begin = d.ent_seg_begin.p; pv.seg_u = d.seg_u.p;
-    if constexpr (sizeof(T) == 4) pv.ent_den = d.ent_den32.p; else pv.ent_den = d.ent_den64.p;
-    pv.den = pv.ent_den;               // partial rows: nothing is divided before the rows are combined (ent_den = 1.0)
-    pv.chunk_desc = d.chunk_desc.p; pv.g0_normal = d.g0_normal; pv.c0_normal = d.c0_normal;
+    auto wts = [&](int k) { return seg_w_of<T>(chunking_of(plan->many_w[k], ch)); };
+    auto den_fine = [&](int k) { return den_of<T>(chunking_of(plan->many_w[k], ch)); };
+    PlanView<T> pv = plan_view<T>(d, compact);          // (partial rows: den = ent_den = 1.0; seg_w: per pass, below)
     const int64_t ldws = (Ttot + 63) / 64 * 64, kpstride = ldws * d.n_part;
     T *ws = static_cast<T *>(plan->staging(stream, sizeof(T) * (size_t)kpstride * (size_t)K));
     if (!ws) { set_error("staging buffer of %.1f MB: allocation failed", (double)(sizeof(T) * kpstride * K) * 1e-6); return WAGG_ENOMEM; }
-    const bool vec = ((reinterpret_cast<uintptr_t>(X) & 15) == 0) && ((ldx * sizeof(T)) % 16 == 0);
+    const bool vec = rows_aligned16(X, ldx);
     const int n_norm = (int)d.n_groups - d.g0_normal;
     if (n_norm > 0) {
         const long long n_items = (long long)n_norm * ((Ttot + LV_TB - 1) / LV_TB);
@@ -1898,7 +1869,7 @@ int entry::apply(const wagg_plan *plan, const T *X, int64_t Tn, int64_t ldx, int
                  void *stream) {
     int rc = check_apply_args(plan, X, Tn, ldx, layout, out, ldo, out_layout);
     if (rc != WAGG_OK) return rc;
-    return launch_sparse<T, SEG_TB<T>>(plan, X, Tn, ldx, layout, out, ldo, out_layout, (hipStream_t)stream);
+    return launch_sparse<T, SEG_TB<T>>(plan, {X, Tn, ldx, layout, out, ldo, out_layout, (hipStream_t)stream});
 }
 
 // WAGG_APPLY_COMPACT_ROWS: device-resident PACKED rows (wagg_pack.hip; ldx >= Gq) through the kernel of the lines-only host
@@ -1907,9 +1878,9 @@ template <typename T>
 int entry::apply_compact(const wagg_plan *plan, const T *X, int64_t Tn, int64_t ldx, T *out, int64_t ldo, void *stream) {
     WAGG_REQUIRE(plan != nullptr, "plan is NULL");
     WAGG_REQUIRE(Tn >= 0, "T < 0");
-    const SparsePlanDev &d = sizeof(T) == 4 ? plan->dl : plan->dl64;
-    const bool lcv_off = (plan->flags & (WAGG_PLAN_NO_LC | WAGG_PLAN_NO_STREAM | WAGG_PLAN_LC_MFMA)) != 0;
-    if (plan->is_many() || lcv_off || !(sizeof(T) == 4 ? plan->has_lines : plan->has_lines64) || d.Gq <= 0 || d.g0_normal != 0) {
+    const int ch = route_lcv_lines(route_plan(plan), (int)sizeof(T), false);
+    const SparsePlanDev &d = chunking_of(plan, ch);
+    if (plan->is_many() || ch == CH_R || d.Gq <= 0 || d.g0_normal != 0) {
         set_error("wagg_apply: WAGG_APPLY_COMPACT_ROWS needs a single segment-table plan with the quads-only compact row of this element type");
         return WAGG_EUNSUPPORTED;
     }
@@ -1917,8 +1888,9 @@ int entry::apply_compact(const wagg_plan *plan, const T *X, int64_t Tn, int64_t 
     WAGG_REQUIRE(X != nullptr && out != nullptr, "X/out is NULL");
     WAGG_REQUIRE(ldx >= d.Gq, "ldx %lld too small for packed rows of %lld cells", (long long)ldx, (long long)d.Gq);
     WAGG_REQUIRE(ldo >= (int64_t)plan->info.R, "ldo %lld too small", (long long)ldo);
-    return launch_sparse<T, SEG_TB<T>>(plan, X, Tn, ldx, WAGG_LAYOUT_TG, out, ldo, WAGG_OUT_TR, (hipStream_t)stream, T(0), 0, 1, 0, nullptr,
-                                       nullptr, 0, COMPACT_QUADS);
+    SparseCall<T> c{X, Tn, ldx, WAGG_LAYOUT_TG, out, ldo, WAGG_OUT_TR, (hipStream_t)stream};
+    c.compact = COMPACT_QUADS;
+    return launch_sparse<T, SEG_TB<T>>(plan, c);
 }
 
 // (x + offset)^p for p = 1..n_pow, each aggregated like wagg_apply.  Power p lands at
@@ -1937,8 +1909,8 @@ int entry::apply_poly(const wagg_plan *plan, const T *X, int64_t Tn, int64_t ldx
                  (long long)out_pstride);
     for (int i = 0; i < n_pow && rc == WAGG_OK; i += 4) {     // one pass over X per four powers
         const int n = n_pow - i < 4 ? n_pow - i : 4;
-        rc = launch_sparse<T, TB>(plan, X, Tn, ldx, layout, out + (int64_t)i * out_pstride, ldo, out_layout, st,
-                                  (T)offset, pow_first + i, n, out_pstride);
+        rc = launch_sparse<T, TB>(plan, {X, Tn, ldx, layout, out + (int64_t)i * out_pstride, ldo, out_layout, st, (T)offset,
+                                         {RX_POWERS, pow_first + i, n}, out_pstride});
     }
     return rc;
 }
@@ -1972,8 +1944,9 @@ static int host_rows_pipeline(const wagg_plan *plan, const T *X, int64_t Tn, int
     // cross PCIe (c2-real: 64 % of a fp32 row, 47 % of a fp64 row).  Taken when asked for, when the plan has that
     // chunking for T, when the row shrinks to <= 80 % and the field is large enough to be worth a thread team; a team
     // that cannot start (ring in use by a concurrent call, too few usable CPUs) means the plain pipeline below
-    const SparsePlanDev &dc = dc_given ? (dc_ ? *dc_ : plan->d) : (sizeof(T) == 4 ? plan->dl : plan->dl64);
-    const bool has_c = (dc_given ? dc_ != nullptr : (sizeof(T) == 4 ? plan->has_lines : plan->has_lines64)) && dc.Gc > 0 && !dc.run_len.empty();
+    const int ch_own = dc_given ? CH_R : route_lines_chunking(route_plan(plan), (int)sizeof(T), false);
+    const SparsePlanDev &dc = dc_given && dc_ ? *dc_ : chunking_of(plan, ch_own);
+    const bool has_c = (dc_given ? dc_ != nullptr : ch_own != CH_R) && dc.Gc > 0 && !dc.run_len.empty();
     // ... and of those lines only the QUADS (16 bytes) that hold a referenced cell ("quads only", round 6; c2-real: 33.5 % of a
     // fp32 row instead of 63.6 %, 10.2 instead of 18.1 ms for packing + copy in tools/host_granule_gonogo.sh) when the packing
     // team is large enough for the shorter runs (116 instead of 455 bytes on average: twelve threads stay ahead of PCIe,
@@ -2038,8 +2011,9 @@ int entry::apply_host_ex(const wagg_plan *plan, const T *X, int64_t Tn, int64_t 
         rc = host_rows_pipeline<T>(plan, X, Tn, ldx, out, ldo, flags, 1, 0,
                                    [&](const T *xd, int64_t rows, int64_t ldx_dev, T *od, hipStream_t st, int compact) {
                                        if (!compact) return entry::apply<T>(plan, xd, rows, ldx_dev, WAGG_LAYOUT_TG, od, ldo, WAGG_OUT_TR, (void *)st);
-                                       return launch_sparse<T, SEG_TB<T>>(plan, xd, rows, ldx_dev, WAGG_LAYOUT_TG, od, ldo, WAGG_OUT_TR, st, T(0), 0, 1, 0,
-                                                                          nullptr, nullptr, 0, compact);
+                                       SparseCall<T> c{xd, rows, ldx_dev, WAGG_LAYOUT_TG, od, ldo, WAGG_OUT_TR, st};
+                                       c.compact = compact;
+                                       return launch_sparse<T, SEG_TB<T>>(plan, c);
                                    });
         if (rc != WAGG_OK) return rc;
         return check_timeout(plan);
@@ -2068,8 +2042,8 @@ int entry::apply_poly_host(const wagg_plan *plan, const T *X, int64_t Tn, int64_
                                    int r2 = WAGG_OK;
                                    const int64_t ps = rows * ldo;                 // planes of one block lie side by side
                                    for (int i = 0; i < n_pow && r2 == WAGG_OK; i += 4)      // one pass over the block per four powers
-                                       r2 = launch_sparse<T, TB>(plan, xd, rows, ldx_dev, WAGG_LAYOUT_TG, od + (int64_t)i * ps, ldo, WAGG_OUT_TR, st,
-                                                                 (T)offset, pow_first + i, n_pow - i < 4 ? n_pow - i : 4, ps, nullptr, nullptr, 0, compact);
+                                       r2 = launch_sparse<T, TB>(plan, {xd, rows, ldx_dev, WAGG_LAYOUT_TG, od + (int64_t)i * ps, ldo, WAGG_OUT_TR, st, (T)offset,
+                                                                        {RX_POWERS, pow_first + i, n_pow - i < 4 ? n_pow - i : 4}, ps, nullptr, nullptr, compact});
                                    return r2;
                                });
     if (rc != WAGG_OK) return rc;
@@ -2092,9 +2066,9 @@ int entry::apply_edd_host(const wagg_plan *plan, const T *tmin, const T *tmax, i
     if (Tn == 0) return WAGG_OK;
     if ((rc = check_plan_device(plan)) != WAGG_OK) return rc;
     constexpr int TB = SEG_TB<T>;
-    const bool lcv_off = (plan->flags & (WAGG_PLAN_NO_LC | WAGG_PLAN_NO_STREAM | WAGG_PLAN_LC_MFMA)) != 0;
-    const bool edd_lcv = (sizeof(T) == 4 ? plan->has_lines64 : plan->has_lines64e) && !lcv_off;
-    const SparsePlanDev *dc = edd_lcv ? (sizeof(T) == 4 ? &plan->dl64 : &plan->dl64e) : nullptr;
+    // (the chunking sparse_route reads for every batch of one to four thresholds below)
+    const int ch = route_lcv_lines(route_plan(plan), (int)sizeof(T), true);
+    const SparsePlanDev *dc = ch != CH_R ? &chunking_of(plan, ch) : nullptr;
     rc = host_rows_pipeline<T>(plan, tmin, Tn, ldx, out, ldo, flags, n_thr, out_pstride,
                                [&](const T *xd, int64_t rows, int64_t ldx_dev, T *od, hipStream_t st, int compact) {
                                    // whole rows: tasmax's block behind tasmin's; packed rows: one row = tasmin's lines, then tasmax's
@@ -2104,8 +2078,8 @@ int entry::apply_edd_host(const wagg_plan *plan, const T *tmin, const T *tmax, i
                                    const int64_t ps = rows * ldo;
                                    int r2 = WAGG_OK;
                                    for (int i = 0; i < n_thr && r2 == WAGG_OK; i += 4)
-                                       r2 = launch_sparse<T, TB>(plan, xd, rows, ld, WAGG_LAYOUT_TG, od + (int64_t)i * ps, ldo, WAGG_OUT_TR, st,
-                                                                 (T)offset, XF_EDD, 1, ps, x2, thr + i, n_thr - i < 4 ? n_thr - i : 4, compact);
+                                       r2 = launch_sparse<T, TB>(plan, {xd, rows, ld, WAGG_LAYOUT_TG, od + (int64_t)i * ps, ldo, WAGG_OUT_TR, st, (T)offset,
+                                                                        {RX_EDD, 0, n_thr - i < 4 ? n_thr - i : 4}, ps, x2, thr + i, compact});
                                    return r2;
                                },
                                dc, true, tmax);
@@ -2157,8 +2131,8 @@ int entry::apply_edd(const wagg_plan *plan, const T *tmin, const T *tmax, int64_
     WAGG_REQUIRE(n_thr == 1 || out_pstride >= orows * ldo, "out_pstride %lld overlaps the previous threshold",
                  (long long)out_pstride);
     for (int i = 0; i < n_thr && rc == WAGG_OK; i += 4)         // both fields are read once per four thresholds
-        rc = launch_sparse<T, TB>(plan, tmin, Tn, ldx, layout, out + (int64_t)i * out_pstride, ldo, out_layout, st,
-                                  (T)offset, XF_EDD, 1, out_pstride, tmax, thr + i, n_thr - i < 4 ? n_thr - i : 4);
+        rc = launch_sparse<T, TB>(plan, {tmin, Tn, ldx, layout, out + (int64_t)i * out_pstride, ldo, out_layout, st, (T)offset,
+                                         {RX_EDD, 0, n_thr - i < 4 ? n_thr - i : 4}, out_pstride, tmax, thr + i});
     return rc;
 }
 }  // namespace wagg
@@ -2351,8 +2325,8 @@ int entry::apply_many_host(const wagg_plan *plan, const T *X, int64_t Tn, int64_
     constexpr int TB = SEG_TB<T>;
     if (layout == WAGG_LAYOUT_TG && out_layout == WAGG_OUT_TR && !(flags & WAGG_HOST_WHOLE)) {
         const wagg_plan *p0 = plan->many_w[0];
-        const bool fused = many_fused<T>(plan, layout);
-        const SparsePlanDev *dc = fused ? (sizeof(T) == 4 ? &p0->dl : &p0->dl64) : nullptr;
+        const int ch = route_lcv_lines(route_plan(p0), (int)sizeof(T), false);
+        const SparsePlanDev *dc = ch != CH_R ? &chunking_of(p0, ch) : nullptr;
         return host_rows_pipeline<T>(plan, X, Tn, ldx, out, ldo, flags, 1, 0,
                                      [&](const T *xd, int64_t rows, int64_t ldx_dev, T *od, hipStream_t st, int compact) {
                                          return launch_many<T, TB>(plan, xd, rows, ldx_dev, WAGG_LAYOUT_TG, od, ldo, WAGG_OUT_TR, st, compact);

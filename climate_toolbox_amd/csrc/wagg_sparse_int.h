@@ -6,6 +6,7 @@
 
 #include "wagg_chunk.h"
 #include "wagg_host.h"
+#include "wagg_route.h"
 
 namespace wagg {
 
@@ -66,7 +67,7 @@ struct SparsePlanDev {
     std::vector<int32_t> run_len_q;
     int64_t Gq = 0;
 };
-constexpr int COMPACT_NONE = 0, COMPACT_LINES = 1, COMPACT_QUADS = 2;       // which row launch_sparse is handed
+// (COMPACT_NONE / COMPACT_LINES / COMPACT_QUADS, which row launch_sparse is handed: wagg_route.h)
 
 // What a many-plan (wagg_plan_create_many) adds: K weightings of one table and n_levels coarse levels derived from the fine
 // one.  The weightings are K plans built from the same kept rows (a row another weighting keeps has weight 0 where this one is
@@ -164,6 +165,22 @@ struct wagg_plan {
 };
 
 namespace wagg {
+
+// chunking CH_* of a plan, and the scalars of the plan the route reads (wagg_route.h)
+inline const SparsePlanDev &chunking_of(const wagg_plan *plan, int ch) {
+    return ch == CH_L32 ? plan->dl : ch == CH_L64 ? plan->dl64 : ch == CH_L64E ? plan->dl64e : plan->d;
+}
+inline RoutePlan route_plan(const wagg_plan *plan) {
+    RoutePlan p;
+    p.flags = plan->flags;
+    p.has_lines = plan->has_lines; p.has_lines64 = plan->has_lines64; p.has_lines64e = plan->has_lines64e;
+    p.G = plan->info.G; p.R = plan->info.R;
+    for (int ch = 0; ch < 4; ++ch) {
+        const SparsePlanDev &d = chunking_of(plan, ch);
+        p.ch[ch] = {d.n_groups, d.g0_normal, d.n_part, d.n_empty, d.Gc, d.Gq};
+    }
+    return p;
+}
 
 template <typename T> struct PlanView {
     const int32_t *grp_chunk_begin, *grp_giant, *chunk_u_begin, *chunk_e_begin, *ucell;

@@ -3,15 +3,12 @@ sparse_gather_kernel (degree days with NTHR = 1 / 4 and several passes, (gridcel
 region-shaped chunks, the giant arm beside each of them, and fill_empty_kernel on every plane -- each against the fp64 oracle on
 the transformed grid and against the default plan (whole-line chunkings) on the same data.
 
-Routes (one SparsePlan each; the kernel is the one the table above lcv_pick in csrc/wagg_sparse.hip sends the case to):
-  A   flags = 0, no row_len            fp32 plain / powers: sparse_lcv_kernel on region-shaped chunks; fp64 plain / one power
-                                       (fused powers: one pass per power): sparse_stream_kernel; degree days, fp64 and
-                                       degree-day (gridcell, time) data: sparse_gather_kernel
+Routes (one SparsePlan each; which kernel a route sends a case to: the table above sparse_route in csrc/wagg_route.cpp, pinned
+case by case by tests/golden/routes.json):
+  A   flags = 0, no row_len            no whole-line chunking
   B   row_len, WAGG_PLAN_NO_LINES      as A, through the other arm of the constructor
-  C   WAGG_PLAN_NO_LC                  sparse_stream_kernel (fp32 too); degree days and (gridcell, time) data: gather
-  D   WAGG_PLAN_NO_STREAM              sparse_gather_kernel for everything
-  EC, ED   C, D with WAGG_PLAN_NO_LINES
-  F   row_len, flags = 0               sparse_lcv_kernel on whole lines: the partner of the cross-check
+  C   WAGG_PLAN_NO_LC                  D   WAGG_PLAN_NO_STREAM                  EC, ED   C, D with WAGG_PLAN_NO_LINES
+  F   row_len, flags = 0               whole lines: the partner of the cross-check
 Every table carries a giant region (a contiguous run plus scattered cells, more than 64 quads): the gather kernel's giant arm
 runs beside every main kernel.
 
