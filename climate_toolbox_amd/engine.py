@@ -1,5 +1,14 @@
 """Device-side objects over the C-ABI (include/wagg.h).  torch supplies device memory and streams
-only; every number is produced by the HIP kernels in climate_toolbox_amd/csrc/."""
+only; every number is produced by the HIP kernels in climate_toolbox_amd/csrc/.
+
+``stream=``: a call that takes it queues ALL its device work there -- the kernels, the zero-fill of a new status word, the
+relayout of a non-contiguous operand -- whichever stream is torch's current one, and waits for no other stream.  Two kinds of
+call do wait, and say so: those that take HOST integers and upload them (row lists, ``doy`` / ``windows``, the index of
+:func:`take_axis`) do that with a blocking copy on torch's CURRENT stream, complete when the call returns; and ``status`` /
+``saw_inf`` / :func:`any_less` synchronise ``stream`` itself.  The tensors a call allocates (results, status word, workspace)
+are allocated with ``stream`` current, so they belong to that stream in torch's caching allocator like anything made under
+``with torch.cuda.stream(stream)``: use them there, or order the other stream behind it AND tell the allocator
+(``other.wait_stream(stream)``, ``result.record_stream(other)``).  tests/test_gpu_stream_order.py pins this per call."""
 from __future__ import annotations
 
 import ctypes as C
@@ -52,6 +61,15 @@ def _stream_handle(stream):
     import torch
     s = stream if stream is not None else torch.cuda.current_stream()
     return C.c_void_p(s.cuda_stream)
+
+
+def _on_stream(stream):
+    """``with _on_stream(s):`` -- ``s`` is torch's current stream inside (None: leave it as it is).  What torch allocates, fills
+    or uploads for a call is done in there, so that it is ordered on the stream the library call runs on and comes from that
+    stream's blocks of the caching allocator -- not from those of whichever stream the caller happens to have current, which
+    work queued there may still be writing."""
+    import torch
+    return torch.cuda.stream(stream)
 
 
 def _elem(dtype):
@@ -154,7 +172,8 @@ class SparsePlan:
         return cache[eb]
 
     def apply(self, X, layout="TG", out=None, out_layout="TR", stream=None, compact=False):
-        """out[t, r] on the device; asynchronous on torch's current stream (or `stream`).  ``compact=True``: the rows of X are
+        """out[t, r] on the device; asynchronous on torch's current stream (or `stream`: a new ``out`` then belongs to that stream in
+        torch's allocator -- the module's docstring says what that asks of a caller who reads it on another).  ``compact=True``: the rows of X are
         PACKED rows (:func:`pack_rows`; at least ``len(compact_cells(X.dtype))`` columns, of which the first ``Gq`` are read)
         -- ``WAGG_APPLY_COMPACT_ROWS``: "TG" in, "TR" out only; the same bits as the plain apply of the unpacked rows."""
         import torch
@@ -173,7 +192,8 @@ class SparsePlan:
             raise ValueError("X has %d grid cells, plan expects %d" % (n_g, self.G))
         shape = (T, self.R) if out_layout == "TR" else (self.R, T)
         if out is None:
-            out = torch.empty(shape, dtype=X.dtype, device=X.device)
+            with _on_stream(stream):
+                out = torch.empty(shape, dtype=X.dtype, device=X.device)
         elif tuple(out.shape) != shape or out.dtype != X.dtype or (shape[1] > 1 and out.stride(1) != 1):
             raise ValueError("out must be a %s %s tensor with contiguous rows" % (shape, X.dtype))
         _lib.run("wagg_apply", plan_kind=_lib.PLAN_SEGMENT, plan=self._h, elem=_elem(X.dtype), source=_lib.SRC_DEVICE,
@@ -192,7 +212,8 @@ class SparsePlan:
             raise ValueError("X has %d grid cells, plan expects %d" % (n_g, self.G))
         shape = (int(n_pow),) + ((T, self.R) if out_layout == "TR" else (self.R, T))
         if out is None:
-            out = torch.empty(shape, dtype=X.dtype, device=X.device)
+            with _on_stream(stream):
+                out = torch.empty(shape, dtype=X.dtype, device=X.device)
         elif tuple(out.shape) != shape or out.dtype != X.dtype or not out.is_contiguous():
             raise ValueError("out must be a contiguous %s %s tensor" % (shape, X.dtype))
         _lib.run("wagg_apply (poly)", plan_kind=_lib.PLAN_SEGMENT, plan=self._h, elem=_elem(X.dtype), source=_lib.SRC_DEVICE,
@@ -215,7 +236,8 @@ class SparsePlan:
         thr = np.ascontiguousarray(np.atleast_1d(thresholds), dtype=np.float64)
         shape = (len(thr),) + ((T, self.R) if out_layout == "TR" else (self.R, T))
         if out is None:
-            out = torch.empty(shape, dtype=tasmin.dtype, device=tasmin.device)
+            with _on_stream(stream):
+                out = torch.empty(shape, dtype=tasmin.dtype, device=tasmin.device)
         elif tuple(out.shape) != shape or out.dtype != tasmin.dtype or not out.is_contiguous():
             raise ValueError("out must be a contiguous %s %s tensor" % (shape, tasmin.dtype))
         _lib.run("wagg_apply (edd)", plan_kind=_lib.PLAN_SEGMENT, plan=self._h, elem=_elem(tasmin.dtype), source=_lib.SRC_DEVICE,
@@ -376,7 +398,8 @@ class ManyPlan:
         return [[full[o:o + Rl] for o in offs] for offs, Rl in zip(self.offsets, self.level_R)]
 
     def apply(self, X, layout="TG", out_layout="TR", out=None, stream=None):
-        """Every plane from one pass over the device tensor X; asynchronous on torch's current stream (or `stream`).
+        """Every plane from one pass over the device tensor X; asynchronous on torch's current stream (or `stream`: a new ``out``
+        then belongs to that stream in torch's allocator, see the module's docstring).
         ``out``: the concatenated (T, out_cols) / (out_cols, T) result to fill (else a new one)."""
         import torch
         X = _check_X(X, layout)
@@ -385,7 +408,8 @@ class ManyPlan:
             raise ValueError("X has the wrong number of grid cells (plan expects %d)" % self.G)
         shape = (T, self.out_cols) if out_layout == "TR" else (self.out_cols, T)
         if out is None:
-            out = torch.empty(shape, dtype=X.dtype, device=X.device)
+            with _on_stream(stream):
+                out = torch.empty(shape, dtype=X.dtype, device=X.device)
         elif tuple(out.shape) != shape or out.dtype != X.dtype or (shape[1] > 1 and out.stride(1) != 1):
             raise ValueError("out must be a %s %s tensor with contiguous rows" % (shape, X.dtype))
         _lib.run("wagg_apply (many)", plan_kind=_lib.PLAN_SEGMENT, plan=self._h, elem=_elem(X.dtype), source=_lib.SRC_DEVICE,
@@ -554,7 +578,7 @@ class DensePlan:
 
     __del__ = close
 
-    def _prep(self, X, out):
+    def _prep(self, X, out, stream=None):
         import torch
         X = _check_X(X, "TG")
         want = torch.float64 if self.dtype == "float64" else torch.float32
@@ -564,7 +588,8 @@ class DensePlan:
             raise ValueError("X has %d grid cells, plan expects %d" % (X.shape[1], self.G))
         T = X.shape[0]
         if out is None:
-            out = torch.empty((T, self.R), dtype=want, device=X.device)
+            with _on_stream(stream):
+                out = torch.empty((T, self.R), dtype=want, device=X.device)
         elif tuple(out.shape) != (T, self.R) or out.dtype != want or (self.R > 1 and out.stride(1) != 1):
             raise ValueError("out must be a (%d, %d) %s tensor with contiguous rows" % (T, self.R, self.dtype))
         return X, T, out
@@ -574,8 +599,9 @@ class DensePlan:
 
     def apply(self, X, out=None, ksplit=0, stream=None, exact=False):
         """``exact=True``: an fp32 full-form plan runs the fp32 MFMA kernel instead of the default split form
-        (``WAGG_APPLY_EXACT_F32``; the same for apply_poly / apply_edd / apply_host)."""
-        X, T, out = self._prep(X, out)
+        (``WAGG_APPLY_EXACT_F32``; the same for apply_poly / apply_edd / apply_host).  Asynchronous on torch's current stream
+        or ``stream``; a new ``out`` then belongs to that stream in torch's allocator (the module's docstring)."""
+        X, T, out = self._prep(X, out, stream)
         self._run("wagg_apply (dense)", plan=self._h, source=_lib.SRC_DEVICE, x=X.data_ptr(), T=T, ldx=_ld(X), out=out.data_ptr(),
                   ldo=_ld(out), ksplit=int(ksplit), stream=_stream_handle(stream), flags=_exact_flag(exact))
         return out
@@ -583,7 +609,7 @@ class DensePlan:
     def apply_poly(self, X, offset, power, out=None, ksplit=0, stream=None, exact=False):
         """Aggregate of (X + offset) ** power (``wagg_dense_apply_poly_*``): the transform of
         tas_poly (transformations.py:188) is evaluated while X is packed."""
-        X, T, out = self._prep(X, out)
+        X, T, out = self._prep(X, out, stream)
         self._run("wagg_apply (dense, poly)", plan=self._h, source=_lib.SRC_DEVICE, transform=_lib.XF_POLY, offset=float(offset),
                   pow_first=int(power), n_pow=1, x=X.data_ptr(), T=T, ldx=_ld(X), out=out.data_ptr(), ldo=_ld(out), ksplit=int(ksplit),
                   stream=_stream_handle(stream), flags=_exact_flag(exact))
@@ -592,7 +618,7 @@ class DensePlan:
     def apply_edd(self, tasmin, tasmax, threshold, offset=0.0, out=None, ksplit=0, stream=None, exact=False):
         """Aggregate of snyder_edd(tasmin + offset, tasmax + offset, threshold)
         (``wagg_dense_apply_edd_*``; transformations.py:64-87 evaluated while the fields are packed)."""
-        tasmin, T, out = self._prep(tasmin, out)
+        tasmin, T, out = self._prep(tasmin, out, stream)
         tasmax = _check_X(tasmax, "TG")
         if tasmax.shape != tasmin.shape or tasmax.dtype != tasmin.dtype or _ld(tasmax) != _ld(tasmin):
             raise ValueError("tasmin and tasmax must have the same shape, dtype and row stride")
@@ -699,7 +725,8 @@ class ShardGroup:
 
 
 def gather(X, cell_idx_dev, layout="TG", out_layout="TR", stream=None):
-    """Materialised pointwise gather (aggregations.py:27) on the device."""
+    """Materialised pointwise gather (aggregations.py:27) on the device; with ``stream=`` the result belongs to that stream in
+    torch's allocator (the module's docstring)."""
     import torch
     X = _check_X(X, layout)
     if not (cell_idx_dev.is_cuda and cell_idx_dev.dtype == torch.int32 and cell_idx_dev.is_contiguous()):
@@ -707,7 +734,8 @@ def gather(X, cell_idx_dev, layout="TG", out_layout="TR", stream=None):
     T = X.shape[0] if layout == "TG" else X.shape[1]
     n = cell_idx_dev.numel()
     shape = (T, n) if out_layout == "TR" else (n, T)
-    out = torch.empty(shape, dtype=X.dtype, device=X.device)
+    with _on_stream(stream):
+        out = torch.empty(shape, dtype=X.dtype, device=X.device)
     L = _lib.load()
     fn = L.wagg_gather_f32 if X.dtype == torch.float32 else L.wagg_gather_f64
     _lib.check(fn(C.c_void_p(X.data_ptr()), T, _ld(X), _LAYOUTS[layout],
@@ -725,7 +753,8 @@ def pack_rows(plan, X, X2=None, stream=None):
     """The rows of a (T, G) field with only the quads the plan's table references: a (T, Gq) CUDA tensor, column ``j`` being cell
     ``plan.compact_cells(X.dtype)[j]`` (``wagg_pack_rows_*``).  With ``X2`` (tasmax beside tasmin; same shape, dtype and row
     stride) a (T, 2 Gq) tensor: field 0 in ``[:, :Gq]``, field 1 in ``[:, Gq:]``.  ``X`` / ``X2``: CUDA tensors (asynchronous on
-    torch's current stream, or ``stream``) or NumPy arrays -- then host threads pack the quads and only they cross PCIe
+    torch's current stream, or ``stream`` -- the result then belongs to that stream in torch's allocator, see the module's
+    docstring) or NumPy arrays -- then host threads pack the quads and only they cross PCIe
     (``wagg_pack_rows_host_*``; blocking) where the library takes that way (a field of >= 64 MiB whose packed row is <= 80 % of
     the row, enough CPUs), and the field is uploaded whole and packed on the device where it does not.  ``PACK_STATS`` counts
     the ways taken.  WaggError for a plan without a compact row."""
@@ -766,7 +795,8 @@ def pack_rows(plan, X, X2=None, stream=None):
         else:
             if X2 is not None and _ld(X2) != _ld(X):
                 raise ValueError("X and X2 must share one row stride")
-            out = torch.empty((T, nf * len(cells)), dtype=X.dtype, device=X.device)
+            with _on_stream(stream):
+                out = torch.empty((T, nf * len(cells)), dtype=X.dtype, device=X.device)
             PACK_STATS["device"] += 1
         fn = L.wagg_pack_rows_f32 if f32 else L.wagg_pack_rows_f64
         _lib.check(fn(plan._h, C.c_void_p(X.data_ptr()), None if X2 is None else C.c_void_p(X2.data_ptr()), T, _ld(X),
@@ -778,19 +808,21 @@ def pack_rows(plan, X, X2=None, stream=None):
     return out
 
 
-def _flat_dev(t):
+def _flat_dev(t, stream=None):
+    """``t`` itself when it is contiguous, else its contiguous copy made on ``stream`` (:func:`relayout`)"""
     import torch
     if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype in (torch.float32, torch.float64)):
         raise TypeError("expected a float32/float64 CUDA tensor")
-    return t if t.is_contiguous() else relayout(t)
+    return t if t.is_contiguous() else relayout(t, stream=stream)
 
 
 def transform_poly(X, offset, power, stream=None):
     """(X + offset) ** power elementwise on the device (``wagg_transform_poly_*``; the arithmetic of
     tas_poly, transformations.py:188, as the fused kernels evaluate it)."""
     import torch
-    X = _flat_dev(X)
-    out = torch.empty_like(X)
+    X = _flat_dev(X, stream)
+    with _on_stream(stream):
+        out = torch.empty_like(X)
     L = _lib.load()
     fn = L.wagg_transform_poly_f32 if X.dtype == torch.float32 else L.wagg_transform_poly_f64
     _lib.check(fn(C.c_void_p(X.data_ptr()), X.numel(), float(offset), int(power), C.c_void_p(out.data_ptr()),
@@ -802,12 +834,13 @@ def transform_edd(tasmin, tasmax, offset, terms, stream=None):
     """sum_k coef_k * snyder_edd(tasmin + offset, tasmax + offset, threshold_k) elementwise on the
     device (``wagg_transform_edd_*``; transformations.py:64-87, :138-140)."""
     import torch
-    lo, hi = _flat_dev(tasmin), _flat_dev(tasmax)
+    lo, hi = _flat_dev(tasmin, stream), _flat_dev(tasmax, stream)
     if lo.shape != hi.shape or lo.dtype != hi.dtype:
         raise ValueError("tasmin and tasmax must have the same shape and dtype")
     coefs = np.ascontiguousarray([c for c, _ in terms], dtype=np.float64)
     thr = np.ascontiguousarray([e for _, e in terms], dtype=np.float64)
-    out = torch.empty_like(lo)
+    with _on_stream(stream):
+        out = torch.empty_like(lo)
     L = _lib.load()
     fn = L.wagg_transform_edd_f32 if lo.dtype == torch.float32 else L.wagg_transform_edd_f64
     _lib.check(fn(C.c_void_p(lo.data_ptr()), C.c_void_p(hi.data_ptr()), lo.numel(), float(offset),
@@ -825,7 +858,8 @@ def combine_planes(stack, coefs, stream=None):
     cf = np.ascontiguousarray(coefs, dtype=np.float64)
     if len(cf) != stack.shape[0]:
         raise ValueError("one coefficient per plane")
-    out = torch.empty(stack.shape[1:], dtype=stack.dtype, device=stack.device)
+    with _on_stream(stream):
+        out = torch.empty(stack.shape[1:], dtype=stack.dtype, device=stack.device)
     L = _lib.load()
     fn = L.wagg_combine_planes_f32 if stack.dtype == torch.float32 else L.wagg_combine_planes_f64
     n = out.numel()
@@ -890,19 +924,21 @@ class _RowlistCall:
         if self.P < 0:
             raise ValueError("row_begin must hold P + 1 offsets")
 
-    def alloc(self, work_bytes, planes, out, status, workspace=True):
+    def alloc(self, work_bytes, planes, out, status, workspace=True, stream=None):
         """``(out, status, work pointer, work bytes)``; ``work_bytes``: the library's ``*_work_bytes`` for this call
-        (``workspace=False``: the library gets no scratch and sums every period's list in one part)"""
+        (``workspace=False``: the library gets no scratch and sums every period's list in one part).  ``stream``: the stream the
+        library call will run on -- the zero-fill of a new status word is queued there, ahead of the kernel that sets its bits"""
         import torch
         X, shape = self.X, (planes, self.P, self.n)
-        if out is None:
-            out = torch.empty(shape, dtype=X.dtype, device=X.device)
-        elif tuple(out.shape) != shape or out.dtype != X.dtype or not out.is_contiguous():
+        if out is not None and (tuple(out.shape) != shape or out.dtype != X.dtype or not out.is_contiguous()):
             raise ValueError("out must be a contiguous %s %s tensor" % (shape, X.dtype))
-        if status is None:
-            status = torch.zeros(1, dtype=torch.int32, device=X.device)
         wb = int(work_bytes(self.n, self.P, self.n_rows, planes)) if workspace else 0
-        self.work = torch.empty(wb // 8, dtype=torch.float64, device=X.device) if wb else None
+        with _on_stream(stream):
+            if out is None:
+                out = torch.empty(shape, dtype=X.dtype, device=X.device)
+            if status is None:
+                status = torch.zeros(1, dtype=torch.int32, device=X.device)
+            self.work = torch.empty(wb // 8, dtype=torch.float64, device=X.device) if wb else None
         return out, status, None if self.work is None else C.c_void_p(self.work.data_ptr()), wb
 
     def done(self, stream):
@@ -943,13 +979,15 @@ def period_reduce(X, row_begin, rows, X2=None, poly=None, edd=None, keep_nan=Fal
     ``workspace=False``: no scratch for the library, so a period's list is never cut into parts -- the split then does not depend
     on ``n``, and a column's sum has the same bits whatever matrix it sits in (here and in the two calls below).
     Returns ``(out, status)``: the (planes, P, n) tensor and the one-word int32 CUDA tensor ``status`` (zeroed here unless
-    handed in), bit 0 of which the kernel sets when a transformed value was +-inf -- reading it waits for the kernel."""
+    handed in), bit 0 of which the kernel sets when a transformed value was +-inf -- reading it waits for the kernel.  With
+    ``stream=`` everything runs there, the zero-fill of ``status`` included, and the tensors allocated here belong to that
+    stream in torch's allocator (the module's docstring; the same for every row-list call below)."""
     import torch
     X = _check_X(X, "TG")
     c = _RowlistCall(X, row_begin, rows, checked)
     transform, offset, pow_first, n_pow, thr, planes, X2 = _rowlist_transform(X, X2, poly, edd)
     L = _lib.load()
-    out, status, work, wb = c.alloc(L.wagg_period_reduce_work_bytes, planes, out, status, workspace)
+    out, status, work, wb = c.alloc(L.wagg_period_reduce_work_bytes, planes, out, status, workspace, stream)
     fn = L.wagg_period_reduce_f32 if X.dtype == torch.float32 else L.wagg_period_reduce_f64
     _lib.check(fn(C.c_void_p(X.data_ptr()), C.c_void_p(X2.data_ptr()) if edd is not None else None, c.T, c.n, _ld(X),
                   C.c_void_p(c.row_begin.data_ptr()), C.c_void_p(c.rows.data_ptr()), c.P, c.n_rows, transform, offset, pow_first, n_pow,
@@ -974,7 +1012,7 @@ def season_reduce(X, row_begin, rows, doy, windows, X2=None, poly=None, edd=None
     c = _RowlistCall(X, row_begin, rows, checked, (doy, windows))
     transform, offset, pow_first, n_pow, thr, planes, X2 = _rowlist_transform(X, X2, poly, edd)
     L = _lib.load()
-    out, status, work, wb = c.alloc(L.wagg_season_reduce_work_bytes, planes, out, status, workspace)
+    out, status, work, wb = c.alloc(L.wagg_season_reduce_work_bytes, planes, out, status, workspace, stream)
     fn = L.wagg_season_reduce_f32 if X.dtype == torch.float32 else L.wagg_season_reduce_f64
     _lib.check(fn(C.c_void_p(X.data_ptr()), C.c_void_p(X2.data_ptr()) if edd is not None else None, c.T, c.n, _ld(X),
                   C.c_void_p(c.row_begin.data_ptr()), C.c_void_p(c.rows.data_ptr()), c.P, c.n_rows, C.c_void_p(c.doy.data_ptr()),
@@ -1000,7 +1038,7 @@ def _grouped_reduce(name, fields, row_begin, rows, doy, windows, checked, offset
     X = fields[0]
     c = _RowlistCall(X, row_begin, rows, checked, None if doy is None else (doy, windows))
     L = _lib.load()
-    out, status, work, wb = c.alloc(lambda *a: work_bytes(L, *a), planes, out, status, workspace)
+    out, status, work, wb = c.alloc(lambda *a: work_bytes(L, *a), planes, out, status, workspace, stream)
     fn = getattr(L, name + ("_f32" if X.dtype == torch.float32 else "_f64"))
     _lib.check(fn(*[C.c_void_p(f.data_ptr()) for f in fields], c.T, c.n, _ld(X), C.c_void_p(c.row_begin.data_ptr()),
                   C.c_void_p(c.rows.data_ptr()), c.P, c.n_rows, None if doy is None else C.c_void_p(c.doy.data_ptr()),
@@ -1219,7 +1257,8 @@ def season_mask(doy, windows, stream=None):
     windows = _season_vector(windows, len(windows), "windows", dev)
     if doy.device != windows.device:
         raise ValueError("doy and windows must live on one device")
-    out = torch.empty((int(windows.numel()), int(doy.numel())), dtype=torch.float64, device=doy.device)
+    with _on_stream(stream):
+        out = torch.empty((int(windows.numel()), int(doy.numel())), dtype=torch.float64, device=doy.device)
     _lib.check(_lib.load().wagg_season_mask(C.c_void_p(doy.data_ptr()), int(doy.numel()), C.c_void_p(windows.data_ptr()),
                                             int(windows.numel()), C.c_void_p(out.data_ptr()), _stream_handle(stream)), "wagg_season_mask")
     if stream is not None:
@@ -1230,7 +1269,9 @@ def season_mask(doy, windows, stream=None):
 
 def take_axis(t, axis, index, stream=None):
     """``t`` with only the positions ``index`` (host integers) kept / re-ordered along ``axis`` (``wagg_take_axis``):
-    the leap-day drop and the lon re-ordering of a device-resident field, without a torch kernel."""
+    the leap-day drop and the lon re-ordering of a device-resident field, without a torch kernel.  The index is uploaded by a
+    blocking copy on torch's CURRENT stream (so the call waits for what is queued there); everything else runs on ``stream``,
+    to which the result then belongs in torch's allocator (the module's docstring)."""
     import torch
     if not isinstance(t, torch.Tensor):
         raise TypeError("expected a torch tensor")
@@ -1241,11 +1282,12 @@ def take_axis(t, axis, index, stream=None):
     if not t.is_cuda:                                # host tensor: a host copy, nothing for the device to do
         return torch.from_numpy(np.take(t.numpy(), idx, axis=axis))
     if t.dtype not in (torch.float32, torch.float64):
-        t = to_float64(t)                            # (rows of 1- and 2-byte elements are not whole words: promote first, S8)
-    t = relayout(t) if not t.is_contiguous() else t
+        t = to_float64(t, stream=stream)             # (rows of 1- and 2-byte elements are not whole words: promote first, S8)
+    t = relayout(t, stream=stream) if not t.is_contiguous() else t
     outer = int(np.prod(t.shape[:axis], dtype=np.int64))
     inner_bytes = int(np.prod(t.shape[axis + 1:], dtype=np.int64)) * t.element_size()
-    out = torch.empty(tuple(t.shape[:axis]) + (len(idx),) + tuple(t.shape[axis + 1:]), dtype=t.dtype, device=t.device)
+    with _on_stream(stream):
+        out = torch.empty(tuple(t.shape[:axis]) + (len(idx),) + tuple(t.shape[axis + 1:]), dtype=t.dtype, device=t.device)
     idx_dev = torch.from_numpy(idx).to(t.device)
     _lib.check(_lib.load().wagg_take_axis(C.c_void_p(t.data_ptr()), outer, int(t.shape[axis]), inner_bytes,
                                           C.c_void_p(idx_dev.data_ptr()), len(idx), C.c_void_p(out.data_ptr()),
@@ -1271,7 +1313,9 @@ def upload(a):
 
 def relayout(t, order=None, stream=None):
     """A contiguous copy of ``t`` (float32/float64 CUDA tensor, any strides), its dims in ``order`` if given
-    (``wagg_relayout_*``): what ``permute(order).contiguous()`` would do, in the library's own kernel."""
+    (``wagg_relayout_*``): what ``permute(order).contiguous()`` would do, in the library's own kernel.  With ``stream=`` the
+    copy belongs to that stream in torch's allocator (the module's docstring; the same for :func:`to_float64` and the
+    ``transform_*`` / :func:`combine_planes` results)."""
     import torch
     if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype in (torch.float32, torch.float64)):
         raise TypeError("device-resident fields must be float32 or float64 CUDA tensors, got %s" % getattr(t, "dtype", type(t)))
@@ -1280,7 +1324,8 @@ def relayout(t, order=None, stream=None):
         raise ValueError("1..6 dimensions")
     shape = [int(t.shape[i]) for i in order]
     strides = [int(t.stride(i)) for i in order]
-    out = torch.empty(shape, dtype=t.dtype, device=t.device)
+    with _on_stream(stream):
+        out = torch.empty(shape, dtype=t.dtype, device=t.device)
     sh = (C.c_int64 * len(shape))(*shape)
     st = (C.c_int64 * len(shape))(*strides)
     L = _lib.load()
@@ -1307,7 +1352,8 @@ def to_float64(t, order=None, stream=None):
         raise ValueError("1..6 dimensions")
     shape = [int(t.shape[i]) for i in order]
     strides = [int(t.stride(i)) for i in order]
-    out = torch.empty(shape, dtype=torch.float64, device=t.device)
+    with _on_stream(stream):
+        out = torch.empty(shape, dtype=torch.float64, device=t.device)
     sh = (C.c_int64 * len(shape))(*shape)
     st = (C.c_int64 * len(shape))(*strides)
     _lib.check(_lib.load().wagg_relayout_to_f64(C.c_void_p(t.data_ptr()), code, len(shape), sh, st, C.c_void_p(out.data_ptr()),
@@ -1319,7 +1365,7 @@ def any_less(a, b, stream=None):
     """True iff some a[i] < b[i] (``wagg_any_less_*``: the tasmax < tasmin check of
     transformations.py:62); blocks."""
     import torch
-    a, b = _flat_dev(a), _flat_dev(b)
+    a, b = _flat_dev(a, stream), _flat_dev(b, stream)
     if a.shape != b.shape or a.dtype != b.dtype:
         raise ValueError("operands must have the same shape and dtype")
     res = C.c_int(0)
