@@ -33,13 +33,14 @@
 #include <type_traits>
 
 #include "wagg_dense_int.h"
+#include "wagg_dense_route.h"
 #include "wagg_entry.h"
 
 namespace wagg {
 
-constexpr int D_MT = 23;                 // most 16-row MFMA tiles per workgroup (fp32; T = 365 -> 23)
-constexpr int D_BN = 256;                // 8 waves x 32 columns
-constexpr int D_ROWB = 128;              // bytes of one tile row = 8 pieces of 16 bytes: 32 floats or 16 doubles of k
+constexpr int D_MT = DENSE_MT_MAX_F32;    // most 16-row MFMA tiles per workgroup (fp32; T = 365 -> 23)
+constexpr int D_BN = DENSE_BN;           // 8 waves x 32 columns
+constexpr int D_ROWB = DENSE_ROWB;       // bytes of one tile row = 8 pieces of 16 bytes: 32 floats or 16 doubles of k
 constexpr int D_THREADS = 512;
 constexpr int D_WTB = D_BN * D_ROWB;     // bytes per packed W tile (32,768 B)
 constexpr int D_WSLOTS = D_WTB / 16;     // 16-byte slots per W tile (2,048)
@@ -65,14 +66,14 @@ template <typename T> struct DT;
 template <> struct DT<float> {
     typedef f32x4 vec;                                   // one 16-byte piece
     typedef f32x4 acc;
-    static constexpr int EPP = 4, BK = 32, MT_MAX = 23;  // elements per piece, k per tile, row blocks
+    static constexpr int EPP = 4, BK = 32, MT_MAX = DENSE_MT_MAX_F32;  // elements per piece, k per tile, row blocks
     static __device__ __forceinline__ acc mfma(float a, float b, acc c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
     static __device__ __forceinline__ int crow(int kq, int reg) { return kq * 4 + reg; }   // C/D: row = 4 (lane >> 4) + reg
 };
 template <> struct DT<double> {
     typedef f64x2 vec;
     typedef f64x4 acc;
-    static constexpr int EPP = 2, BK = 16, MT_MAX = 11;
+    static constexpr int EPP = 2, BK = 16, MT_MAX = DENSE_MT_MAX_F64;
     static __device__ __forceinline__ acc mfma(double a, double b, acc c) { return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0); }
     static __device__ __forceinline__ int crow(int kq, int reg) { return kq + 4 * reg; }   // f64 C/D: row = (lane >> 4) + 4 reg
 };
@@ -519,76 +520,13 @@ static int tile_pieces_for(wagg_dense *d, int n_mb, hipStream_t st, const wagg_d
     } catch (const std::bad_alloc &) { set_error("host allocation failed"); return WAGG_ENOMEM; }
 }
 
-// Generated tables (wagg_dense_create_synth*): below this share of non-zeros a scattered W goes to the entry-list form.
-constexpr double SPMM_MAX_FILL = 0.10;
-
-// ---- which form a caller's table takes (wagg_dense_create_from_csr* / _from_segments*) ---------------------------------
-// The reference knows one weights type (aggregations.py:64-73) and so does the caller here: the form is the library's
-// business.  It is chosen by the estimated time per row of X of the three forms, each priced at the rate its kernel was
-// MEASURED at on the c5 grid (tools/form_crossover.py -> profiles/r05_form_crossover.txt; docs/HISTORY.md (b) has the table):
-//   full matrix     2 x (all tiles x BK x 256) flop     at the full-form MFMA rate (padding of G and R to whole tiles included)
-//   tile-sparse     2 x (stored tiles x BK x 256) flop  at the tile-sparse MFMA rate (a little lower: the tile list is walked)
-//   entry lists     2 x walked entries flop at the entry-loop rate of their mean list length, but never faster than the X
-//                   stream that every one of the n_rb region blocks pulls through the LDS-DMA path (b G n_rb bytes per row)
-// Rates in flop/s and byte/s; fp32 / fp64.
-struct FormRates { double full, tiled, entries_scale, dma; };
-// fp32: full 204.3 ms for 2,282 rows x 8,100 x 96 tiles on the fp32 pipe (142 TF), since the split form (f16 pipe, row maxima
-// and split pack included) 2.99x that: c2-dense 42.6 against 127.3 ms a step on one box, A/B -> 420 TF (re-derived for the
-// W-in-registers pipeline from the form guard's forced full-form times, 424-446 TF, then 445-470 TF: kept); tile-sparse (a
-// workgroup walks an equal share of the stored tiles: dense_pieces_kernel) 144 TF on the stored tiles' flops (c5-block:
-// 8.39 ms), fp64 73 TF (16.58 ms); c5-uniform-f64 of bench.py for the fp64 entry-list scale
-constexpr FormRates FORM_RATES_F32 = {420e12, 144e12, 1.0, 10.1e12};
-constexpr FormRates FORM_RATES_F64 = {70e12, 73e12, 0.44, 10.1e12};
-// The entry loop slows down as the lists grow (the first 16 groups of a wave's list are preloaded across the previous chunk;
-// what follows is fetched inside the loop): flop/s on the WALKED entries against the mean list length per wave and chunk,
-// fp32, measured at uniform fills of 1, 3, 6, 10, 15 and 30 % (mean lengths 54 ... 1625)
-static double entry_loop_rate(double mean_list) {
-    static const double L[] = {170, 325, 541, 812, 1625}, Rt[] = {30e12, 23e12, 19.5e12, 17.3e12, 15.9e12};
-    if (mean_list <= L[0]) return Rt[0];
-    for (int i = 1; i < 5; ++i)
-        if (mean_list <= L[i]) return Rt[i - 1] + (Rt[i] - Rt[i - 1]) * (mean_list - L[i - 1]) / (L[i] - L[i - 1]);
-    return Rt[4];
-}
-
-struct FormCost { double t_full, t_tiled, t_entries; };
-// seconds per row of X.  The MFMA forms multiply whole (BK x 256) tiles, padding included; the entry-list kernel walks
-// `walked` entries (spmm_list_cost: 16 x the longest per-wave list of every item, in whole groups) spread over n_lists
-// (region block, chunk, wave) lists.
-static FormCost table_form_cost(int64_t G, int elem_bytes, int64_t n_tiles_stored, int64_t n_tiles_all, int64_t walked, int n_rb,
-                                int64_t n_lists, int n_nt) {
-    const FormRates &rt = elem_bytes == 8 ? FORM_RATES_F64 : FORM_RATES_F32;
-    const double tile_flop = 2.0 * (128.0 / elem_bytes) * 256.0;        // BK = 32 / 16 cells x 256 regions
-    FormCost c;
-    // (full form with few column tiles: a launch has at most n_nt x 64 k-slices of workgroups per row block -- R = 600 fills
-    //  192 of 256 CUs; the tile-sparse form hands every CU an equal share of the stored tiles whatever their layout)
-    // (pick_ksplit keeps >= 32 k tiles per slice: a short K has fewer than 64 slices -- G = 700: 8 -- and at the split form's
-    //  rate that, not the MFMA pipe, is what a small full-form launch is paid by)
-    const int64_t n_kt = n_tiles_all / (n_nt > 0 ? n_nt : 1);
-    const double s_max = n_kt / 32 >= 64 ? 64.0 : (n_kt / 32 >= 16 ? (double)(n_kt / 32 / 8 * 8) : 8.0);
-    const double util = n_nt * s_max < 256.0 ? n_nt * s_max / 256.0 : 1.0;
-    c.t_full = tile_flop * (double)n_tiles_all / (rt.full * util);
-    c.t_tiled = tile_flop * (double)n_tiles_stored / rt.tiled;
-    const double rate = rt.entries_scale * entry_loop_rate((double)walked / (double)(n_lists > 0 ? n_lists : 1));
-    const double t_loop = 2.0 * (double)walked / rate, t_stream = (double)elem_bytes * (double)G * (double)n_rb / rt.dma;
-    c.t_entries = t_loop > t_stream ? t_loop : t_stream;
-    return c;
-}
-static void pick_table_form(const FormCost &c, bool *tiled, bool *entries) {
-    *entries = c.t_entries < c.t_full && c.t_entries < c.t_tiled;
-    *tiled = !*entries && c.t_tiled < c.t_full;
-}
-
-static int pick_ksplit(int64_t items, int n_kt) {
-    int best = 8;
-    double best_eff = 0.0;
-    for (int S = 8; S <= 64; S += 8) {
-        if (S > 8 && n_kt / S < 32) break;             // keep >= 32 LDS tiles per slice
-        const double w = (double)items * S / 256.0;
-        const double eff = w / std::ceil(w);
-        if (eff > best_eff + 1e-9) { best_eff = eff; best = S; }
-        if (eff >= 0.985) break;
-    }
-    return best;
+// what the schedule of an apply (wagg_dense_route.h) reads of a plan
+static DensePlanScalars dense_plan_scalars(const wagg_dense *d) {
+    DensePlanScalars p;
+    p.elem = d->f64 ? 8 : 4; p.n_nt = d->n_nt; p.n_kt = d->n_kt; p.G = d->G;
+    p.tiled = d->tiled; p.spmm = d->spmm;
+    p.has_maxima = d->wmax.p != nullptr; p.has_image = d->wimg.p != nullptr;
+    return p;
 }
 
 // The f16 hi/lo image of a full-form fp32 W (wagg_dense_split.inc: dense_split_image_kernel), built in stream order behind the
@@ -597,12 +535,11 @@ static int pick_ksplit(int64_t items, int n_kt) {
 // of the plan's largest launch group (one row block of MT_MAX x 16 rows: packed X, slabs at pick_ksplit's S, row maxima);
 // without it the apply splits in registers as before.  WAGG_DENSE_NO_W_IMAGE=1 turns it off (parity tests, A/B runs).
 static void dense_build_image(wagg_dense *d, hipStream_t st) {
-    if (d->f64 || d->tiled || d->spmm || !d->wmax.p || d->n_tiles <= 0) return;
+    const DenseRoute big = dense_largest_group_route(dense_plan_scalars(d));
+    if (big.form != DENSE_FORM_SPLIT || d->n_tiles <= 0) return;
     const char *off = getenv("WAGG_DENSE_NO_W_IMAGE");
     if (off && off[0] && off[0] != '0') return;
-    constexpr size_t bm = (size_t)DT<float>::MT_MAX * 16;
-    const size_t S = (size_t)pick_ksplit(d->n_nt, d->n_kt);
-    const size_t workspace = (size_t)d->n_kt * bm * D_ROWB + (size_t)d->n_nt * S * bm * D_BN * sizeof(float) + bm * sizeof(float);
+    const size_t workspace = (big.xp_words + big.slabs_words + big.xmax_words) * sizeof(float);
     const size_t bytes = (size_t)d->w_slots() * 16;
     size_t free_b = 0, total_b = 0;
     if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); return; }
@@ -908,78 +845,56 @@ static const void *mfma_kernel_ptr() {
     if constexpr (TILED) return (const void *)dense_pieces_kernel<T, MT, RM>;        // tile-sparse form: a workgroup walks pieces
     else return (const void *)dense_mfma_kernel<T, 0, false, MT, RM>;
 }
-// full form, pack-free: instantiated for the tall row blocks only (fp32 MT >= 20, fp64 MT >= 10), where the packing
+// The kernel switches: one case per MT of the lists in wagg_dense_route.h (WAGG_DENSE_MTS_F32 / _F64), which is where
+// dense_pick_mt takes its answers from -- an MT the schedule hands out has its kernels.
+#define WAGG_PICK_SWITCH(T, MT)                                                           \
+    if constexpr (sizeof(T) == 4) { switch (MT) { WAGG_DENSE_MTS_F32(WAGG_PICK) default: return nullptr; } } \
+    else { switch (MT) { WAGG_DENSE_MTS_F64(WAGG_PICK) default: return nullptr; } }
+
+// full form, pack-free: instantiated for the tall row blocks only (dense_full_pack_free_mt), where the packing
 // pass is worth skipping; rm = first pass reading X in place, !rm = its gated packed second pass (DBG = 256)
 template <typename T>
 static const void *pick_full_rm_kernel(int MT, bool rm) {
-#define WAGG_PICK(M) case M: return rm ? (const void *)dense_mfma_kernel<T, 0, false, M, true> \
-                                       : (const void *)dense_mfma_kernel<T, 256, false, M, false>
-    if constexpr (sizeof(T) == 4) {
-        switch (MT) { WAGG_PICK(20); WAGG_PICK(21); WAGG_PICK(22); WAGG_PICK(23); default: return nullptr; }
-    } else {
-        switch (MT) { WAGG_PICK(10); WAGG_PICK(11); default: return nullptr; }
-    }
+#define WAGG_PICK(M) case M:                                                                                          \
+        if constexpr (dense_full_pack_free_mt((int)sizeof(T), M))                                                     \
+            return rm ? (const void *)dense_mfma_kernel<T, 0, false, M, true> : (const void *)dense_mfma_kernel<T, 256, false, M, false>; \
+        else return nullptr;
+    WAGG_PICK_SWITCH(T, MT)
 #undef WAGG_PICK
 }
 
-// the kernel instantiated for MT row blocks (fp32: 1..6, 8, 10, ..., 20, 21, 22, 23; fp64: 1..6, 8, 10, 11)
+// the kernel instantiated for MT row blocks
 template <typename T>
 static const void *pick_mfma_kernel(int MT, bool tiled, bool rm = false) {
 #define WAGG_PICK(M) case M: return tiled ? (rm ? mfma_kernel_ptr<T, true, M, true>() : mfma_kernel_ptr<T, true, M>()) \
-                                          : mfma_kernel_ptr<T, false, M>()
-    if constexpr (sizeof(T) == 4) {
-        switch (MT) {
-            WAGG_PICK(1); WAGG_PICK(2); WAGG_PICK(3); WAGG_PICK(4); WAGG_PICK(5); WAGG_PICK(6); WAGG_PICK(8);
-            WAGG_PICK(10); WAGG_PICK(12); WAGG_PICK(14); WAGG_PICK(16); WAGG_PICK(18); WAGG_PICK(20);
-            WAGG_PICK(21); WAGG_PICK(22); WAGG_PICK(23);
-            default: return nullptr;
-        }
-    } else {
-        switch (MT) {
-            WAGG_PICK(1); WAGG_PICK(2); WAGG_PICK(3); WAGG_PICK(4); WAGG_PICK(5); WAGG_PICK(6); WAGG_PICK(8);
-            WAGG_PICK(10); WAGG_PICK(11);
-            default: return nullptr;
-        }
-    }
+                                          : mfma_kernel_ptr<T, false, M>();
+    WAGG_PICK_SWITCH(T, MT)
 #undef WAGG_PICK
 }
 
-// split form (fp32 full-form plans, the default): MT from the same set as the fp32 kernel; img = W comes from the plan's image
+// split form (fp32 full-form plans, the default): MT from the fp32 set; img = W comes from the plan's image
 static const void *pick_split_kernel(int MT, bool img) {
-#define WAGG_PICK(M) case M: return img ? (const void *)dense_split_kernel<M, 0, true> : (const void *)dense_split_kernel<M>
-    switch (MT) {
-        WAGG_PICK(1); WAGG_PICK(2); WAGG_PICK(3); WAGG_PICK(4); WAGG_PICK(5); WAGG_PICK(6); WAGG_PICK(8);
-        WAGG_PICK(10); WAGG_PICK(12); WAGG_PICK(14); WAGG_PICK(16); WAGG_PICK(18); WAGG_PICK(20);
-        WAGG_PICK(21); WAGG_PICK(22); WAGG_PICK(23);
-        default: return nullptr;
-    }
+#define WAGG_PICK(M) case M: return img ? (const void *)dense_split_kernel<M, 0, true> : (const void *)dense_split_kernel<M>;
+    WAGG_PICK_SWITCH(float, MT)
 #undef WAGG_PICK
 }
+#undef WAGG_PICK_SWITCH
 
-// One launch group of the split form (rows already cut into n_mb row blocks of MT x 16): row maxima, split pack, the
+// One launch group of the split form (n_mb row blocks of MT x 16 rows, route `r`): row maxima, split pack, the
 // f16-pipe contraction, the reduce that takes the scales off.  No pack-free pass: the split needs the packed copy.
-static int dense_apply_split(wagg_dense *d, const float *X_dev, int64_t Tn, int64_t ldx, const PackXfT<float> &xf,
-                             float *out_dev, int64_t ldo, int MT, int n_mb, int S, hipStream_t st) {
+static int dense_launch_split(wagg_dense *d, const float *X_dev, int64_t Tn, int64_t ldx, const PackXfT<float> &xf, float *out_dev,
+                              int64_t ldo, int MT, int n_mb, const DenseRoute &r, int aligned, hipStream_t st) {
     const int n_nt = d->n_nt, n_kt = d->n_kt, bm = MT * 16;
-    const int kt_per_slice = (n_kt + S - 1) / S;
-    const int64_t nblk = (int64_t)n_nt * n_mb * S;
-    WAGG_REQUIRE(nblk < (int64_t)0x7fffffff, "grid too large");
-    const size_t need = (size_t)nblk * bm * D_BN;
-    if (d->slabs.n < need) WAGG_HIP(d->slabs.alloc(need));
-    const int64_t x_slots = (int64_t)n_mb * n_kt * bm * 8;
-    if (d->xp.n < (size_t)x_slots * 4) WAGG_HIP(d->xp.alloc((size_t)x_slots * 4));
-    if (d->xmax.n < (size_t)Tn) WAGG_HIP(d->xmax.alloc((size_t)Tn));
-    // the image serves launches of ONE row block.  With several, every W tile is contracted once per row block and all but
-    // the first read are L2 hits; there the image measured no gain (c4's share, four row blocks: 0.6 % slower in every
-    // alternation, profiles/split_image_ab.txt), so those launches split in registers as before.
-    bool img = d->wimg.p != nullptr && n_mb == 1;
+    WAGG_REQUIRE(r.nblk < (int64_t)0x7fffffff, "grid too large");
+    if (d->slabs.n < r.slabs_words) WAGG_HIP(d->slabs.alloc(r.slabs_words));
+    if (d->xp.n < r.xp_words) WAGG_HIP(d->xp.alloc(r.xp_words));
+    if (d->xmax.n < r.xmax_words) WAGG_HIP(d->xmax.alloc(r.xmax_words));
+    bool img = r.image;
 #ifdef WAGG_DIAG      // WAGG_SPLIT_IMG=0: split in registers although the plan holds an image (A/B in one process)
     if (const char *e = getenv("WAGG_SPLIT_IMG")) img = img && e[0] != '0';
 #endif
     const void *kern = pick_split_kernel(MT, img);
     if (!kern) { set_error("no split kernel for MT=%d", MT); return WAGG_EINVAL; }
-    const int aligned = ((ldx * sizeof(float)) % 16 == 0) && ((reinterpret_cast<uintptr_t>(X_dev) & 15) == 0) &&
-                        (xf.mode != XF_EDD || (reinterpret_cast<uintptr_t>(xf.X2) & 15) == 0);
 #ifdef WAGG_DIAG      // ablation variants (timing only; results are wrong with any bit set): tools/split_ablate.sh
     if (const char *dbg = MT == D_MT ? getenv("WAGG_SPLIT_DBG") : nullptr) {
         switch (atoi(dbg)) {     // (bit3 is the split's own knob: those variants read the fp32 W)
@@ -998,127 +913,53 @@ static int dense_apply_split(wagg_dense *d, const float *X_dev, int64_t Tn, int6
     WAGG_HIP(hipMemsetAsync(xmax, 0, sizeof(unsigned) * (size_t)Tn, st));
     const int64_t gx = (d->G + 4095) / 4096 < 64 ? (d->G + 4095) / 4096 : 64;
     hipLaunchKernelGGL(dense_rowmax_kernel, dim3((unsigned)gx, (unsigned)Tn), dim3(256), 0, st, X_dev, ldx, d->G, xf, xmax);
-    hipLaunchKernelGGL(dense_pack_x_split_kernel, dim3(256 * 16), dim3(256), 0, st, X_dev, Tn, ldx, d->G, n_kt, bm, x_slots, aligned,
+    hipLaunchKernelGGL(dense_pack_x_split_kernel, dim3(256 * 16), dim3(256), 0, st, X_dev, Tn, ldx, d->G, n_kt, bm, r.x_slots, aligned,
                        (const unsigned *)xmax, reinterpret_cast<f16x8 *>(d->xp.p), xf, d->inf_dev);
     WAGG_HIP(hipGetLastError());
     const f16x8 *xp = reinterpret_cast<const f16x8 *>(d->xp.p);
     const float *wp = img ? d->wimg.p : d->W.p, *wmax = d->wmax.p;
     float *slabs = d->slabs.p;
-    int n_kt_a = n_kt, n_nt_a = n_nt, n_mb_a = n_mb, S_a = S, kps = kt_per_slice;
+    int n_kt_a = n_kt, n_nt_a = n_nt, n_mb_a = n_mb, S_a = r.S, kps = r.kt_per_slice;
     void *args[] = {&xp, &wp, &wmax, &n_kt_a, &n_nt_a, &n_mb_a, &S_a, &kps, &slabs};
-    WAGG_HIP(launch_timed_ptr(true, kern, dim3((unsigned)nblk), dim3(D_THREADS), args, shmem, st));
+    WAGG_HIP(launch_timed_ptr(true, kern, dim3((unsigned)r.nblk), dim3(D_THREADS), args, shmem, st));
     hipLaunchKernelGGL(dense_reduce_split_kernel, dim3((unsigned)((d->R + 255) / 256), (unsigned)Tn), dim3(256), 0, st,
-                       (const float *)slabs, n_nt, S, bm, d->R, (const float *)d->den32.p, (const unsigned *)xmax, wmax, out_dev, ldo);
+                       (const float *)slabs, n_nt, r.S, bm, d->R, (const float *)d->den32.p, (const unsigned *)xmax, wmax, out_dev, ldo);
     WAGG_HIP(hipGetLastError());
     return WAGG_OK;
 }
 
+// One launch group of the exact forms (full or tile-sparse, route `r`): the pack-free first pass where the route has one,
+// then pack, the MFMA contraction and the reduce -- gated on the first pass's non-finite note when there was one.
 template <typename T>
-static int dense_apply(wagg_dense *d, const T *X_dev, int64_t Tn, int64_t ldx, const PackXfT<T> &xf,
-                       T *out_dev, int64_t ldo, int ksplit, void *stream, bool exact = false) {
+static int dense_launch_mfma(wagg_dense *d, const T *X_dev, int64_t Tn, int64_t ldx, const PackXfT<T> &xf, T *out_dev, int64_t ldo,
+                             int MT, int n_mb, const DenseRoute &r, int aligned, hipStream_t st) {
     typedef typename DT<T>::vec vec_t;
-    WAGG_REQUIRE(d != nullptr, "dense plan is NULL");
-    WAGG_REQUIRE(d->f64 == (sizeof(T) == 8), "this plan holds %s weights: use the matching wagg_dense_apply_*",
-                 d->f64 ? "fp64" : "fp32");
-    WAGG_REQUIRE(Tn >= 0, "T < 0");
-    if (Tn == 0) return WAGG_OK;
-    WAGG_REQUIRE(X_dev && out_dev, "X/out is NULL");
-    WAGG_REQUIRE(xf.mode != XF_EDD || xf.X2 != nullptr, "tasmax is NULL");
-    WAGG_REQUIRE(ldx >= d->G && ldo >= d->R, "ldx/ldo too small");
-    WAGG_REQUIRE(ksplit >= 0 && ksplit % 8 == 0, "ksplit must be 0 or a multiple of 8");
-    if (d->spmm) return spmm_apply<T>(d, X_dev, Tn, ldx, xf, out_dev, ldo, (hipStream_t)stream);
-    // Long batches (ensemble x time rows of a small grid: 50 members x 30 years = 547,500 rows) go through in groups of
-    // whole row blocks: the reduce kernel's grid has one y block per row (<= 65,535), and the packed copy of X and the
-    // partial slabs are sized by the rows of one launch.  Same stream, same workspaces, one group after the other.
-    constexpr int64_t ROWS_MAX = (int64_t)(65535 / (DT<T>::MT_MAX * 16)) * (DT<T>::MT_MAX * 16);
-    if (Tn > ROWS_MAX) {
-        for (int64_t t0 = 0; t0 < Tn; t0 += ROWS_MAX) {
-            PackXfT<T> xg = xf;
-            if (xg.X2) xg.X2 += t0 * ldx;
-            const int64_t rows = Tn - t0 < ROWS_MAX ? Tn - t0 : ROWS_MAX;
-            if (int rc = dense_apply<T>(d, X_dev + t0 * ldx, rows, ldx, xg, out_dev + t0 * ldo, ldo, ksplit, stream, exact)) return rc;
-        }
-        return WAGG_OK;
-    }
-    const int n_nt = d->n_nt, n_kt = d->n_kt;
-    // row blocks: as few as possible (<= MT_MAX x 16 rows each), evenly filled, 16 MT rows with MT from the
-    // instantiated set -- fp32: T = 365 -> one block of 23 x 16; T = 1369 -> four of 22 x 16; T = 31 -> 2 x 16
-    constexpr int BM_MAX = DT<T>::MT_MAX * 16;
-    const int n_mb = (int)((Tn + BM_MAX - 1) / BM_MAX);
-    const int rows = (int)((Tn + n_mb - 1) / n_mb);
-    static const int mts32[] = {1, 2, 3, 4, 5, 6, 8, 10, 12, 14, 16, 18, 20, 21, 22, 23};
-    static const int mts64[] = {1, 2, 3, 4, 5, 6, 8, 10, 11};
-    int MT = DT<T>::MT_MAX;
-    if constexpr (sizeof(T) == 4) { for (int m : mts32) if (m * 16 >= rows) { MT = m; break; } }
-    else { for (int m : mts64) if (m * 16 >= rows) { MT = m; break; } }
-    const int bm = MT * 16;
-    // A ragged batch: with equal row blocks the padding of EVERY block is paid (c4's rank shard: 1,369 rows = 4 x 343 -> 4 blocks
-    // of 22 x 16 = 1,408 rows, 2.8 % of the MFMA work on zero rows).  Full blocks first, the remainder as a launch of its own with
-    // the smallest row-block count that holds it (3 x 352 + 313 -> 22, 22, 22, 20: 1,376 rows) -- when that saves at least two
-    // sixteen-row units and the remainder is tall enough to stay MFMA-bound against its own pass over W.
-    if (n_mb >= 2) {
-        const int64_t head = (int64_t)(n_mb - 1) * bm, tail = Tn - head;
-        if (tail > 0) {
-            int MT_tail = DT<T>::MT_MAX;
-            if constexpr (sizeof(T) == 4) { for (int m : mts32) if ((int64_t)m * 16 >= tail) { MT_tail = m; break; } }
-            else { for (int m : mts64) if ((int64_t)m * 16 >= tail) { MT_tail = m; break; } }
-            if (MT_tail >= 4 && MT - MT_tail >= 2) {
-                PackXfT<T> xt = xf;
-                if (xt.X2) xt.X2 += head * ldx;
-                if (int rc = dense_apply<T>(d, X_dev, head, ldx, xf, out_dev, ldo, ksplit, stream, exact)) return rc;
-                return dense_apply<T>(d, X_dev + head * ldx, tail, ldx, xt, out_dev + head * ldo, ldo, ksplit, stream, exact);
-            }
-        }
-    }
-    int S = ksplit ? ksplit : pick_ksplit((int64_t)n_nt * n_mb, n_kt);
-    // fp32 full form: the split form unless the caller asked for the exact kernel (WAGG_APPLY_EXACT_F32)
-    if constexpr (sizeof(T) == 4) {
-        if (!d->tiled && !exact && d->wmax.p != nullptr) return dense_apply_split(d, X_dev, Tn, ldx, xf, out_dev, ldo, MT, n_mb, S, (hipStream_t)stream);
-    }
-    // tile-sparse form: no k-slices -- the launch walks PIECES, an equal share of all stored tiles per workgroup (see the kernel)
+    const int n_nt = d->n_nt, n_kt = d->n_kt, bm = MT * 16;
+    const bool tiled = r.form == DENSE_FORM_TILED;
+    // tile-sparse form: the workgroups and slabs of the launch are those of its piece table
     const wagg_dense::TilePieces *tp = nullptr;
-    if (d->tiled) {
-        if (int rc = tile_pieces_for(d, n_mb, (hipStream_t)stream, &tp)) return rc;
-        S = 1;
-    }
-    const int kt_per_slice = (n_kt + S - 1) / S;
-    const int64_t nblk = tp ? (int64_t)tp->n_wg : (int64_t)n_nt * n_mb * S;
+    if (tiled) { if (int rc = tile_pieces_for(d, n_mb, st, &tp)) return rc; }
+    const int64_t nblk = tp ? (int64_t)tp->n_wg : r.nblk;
     WAGG_REQUIRE(nblk < (int64_t)0x7fffffff, "grid too large");
-    const size_t n_slabs = tp ? (size_t)tp->n_slabs : (size_t)n_nt * n_mb * S;
-    const size_t need = (n_slabs ? n_slabs : 1) * bm * D_BN * (sizeof(T) / 4);      // DevBuf<float>: 4-byte units
+    const size_t need = tp ? (size_t)(tp->n_slabs ? tp->n_slabs : 1) * r.slab_words : r.slabs_words;
     if (d->slabs.n < need) WAGG_HIP(d->slabs.alloc(need));   // first call (or larger T) only
-    const int64_t x_slots = (int64_t)n_mb * n_kt * bm * 8;
-    if (d->xp.n < (size_t)x_slots * 4) WAGG_HIP(d->xp.alloc((size_t)x_slots * 4));
-    const int aligned = ((ldx * sizeof(T)) % 16 == 0) && ((reinterpret_cast<uintptr_t>(X_dev) & 15) == 0) &&
-                        (xf.mode != XF_EDD || (reinterpret_cast<uintptr_t>(xf.X2) & 15) == 0);
+    if (d->xp.n < r.xp_words) WAGG_HIP(d->xp.alloc(r.xp_words));
     const size_t shmem = 2 * (size_t)d_buf_bytes(MT);
-    hipStream_t st = (hipStream_t)stream;
-    const void *kern = pick_mfma_kernel<T>(MT, d->tiled);
-    if (!kern) { set_error("no kernel for MT=%d", MT); return WAGG_EINVAL; }
-    // pack-free first pass (plain aggregation of 16-byte-aligned rows, grid = whole k tiles):
-    // the MFMA kernel reads X where it lies; the packed pass below then runs only if a numerator came out
-    // non-finite (NaN / +-inf somewhere in the data), gated on the device so the stream never waits for the host
-    // ... and only while no earlier pack-free pass of this plan met such data: fields with NaN in them (ocean cells of
-    // land-only variables) tend to stay that way, and for them the first pass is pure overhead.  The note is a
-    // host-mapped word written by the reduce kernel; reading it here without synchronising is a heuristic only.
-    // (G must be a whole number of k tiles: the last tile is then read from inside every row, whatever the caller's
-    // pitch and however short the buffer behind the last row is)
-    bool rm = xf.mode == 0 && aligned && d->G % DT<T>::BK == 0 && ((volatile int *)d->inf_host)[1] == 0;
-    const void *kern_rm = nullptr;
-    if (rm && d->tiled) kern_rm = pick_mfma_kernel<T>(MT, true, true);
-    // (full form: only with two or more row blocks -- with one, A/B on one GPU shows the step unchanged: the kernel
-    // loses reading in place what the skipped packing pass saves)
-    else if (rm && n_mb >= 2 && (kern_rm = pick_full_rm_kernel<T>(MT, true)) != nullptr) kern = pick_full_rm_kernel<T>(MT, false);
-    rm = kern_rm != nullptr;
+    int pack_free = r.pack_free;
+#ifdef WAGG_DIAG      // WAGG_DENSE_PACKED=1 (or any WAGG_DENSE_DBG variant): always take the packed pass, for A/B runs on one GPU
+    if (getenv("WAGG_DENSE_PACKED") || (!tiled && getenv("WAGG_DENSE_DBG"))) pack_free = PACK_FREE_NONE;
+#endif
+    // the first pass reads X where it lies (a host-mapped word written by its reduce kernel is the route's `nonfinite_met`:
+    // read without synchronising, a heuristic only); PACK_FREE_FULL: the second pass is the gated packed kernel
+    const void *kern_rm = pack_free == PACK_FREE_TILED  ? pick_mfma_kernel<T>(MT, true, true)
+                          : pack_free == PACK_FREE_FULL ? pick_full_rm_kernel<T>(MT, true) : nullptr;
+    const void *kern = pack_free == PACK_FREE_FULL ? pick_full_rm_kernel<T>(MT, false) : pick_mfma_kernel<T>(MT, tiled);
+    const bool rm = pack_free != PACK_FREE_NONE;
+    if (!kern || (rm && !kern_rm)) { set_error("no kernel for MT=%d", MT); return WAGG_EINVAL; }
     if (rm) WAGG_HIP(allow_dynamic_lds(kern_rm, shmem));
 #ifdef WAGG_DIAG      // ablation variants (timing only; results are wrong with bit0 or bit2): tools/dense_ablate.sh
-    // WAGG_DENSE_PACKED=1 (or any WAGG_DENSE_DBG variant): always take the packed pass, for A/B runs on one GPU
-    if (getenv("WAGG_DENSE_PACKED") || (!d->tiled && getenv("WAGG_DENSE_DBG"))) {
-        rm = false; kern_rm = nullptr;
-        kern = pick_mfma_kernel<T>(MT, d->tiled);
-    }
     if constexpr (sizeof(T) == 4) {
-        if (const char *dbg = (d->tiled || MT != D_MT) ? nullptr : getenv("WAGG_DENSE_DBG")) {
+        if (const char *dbg = (tiled || MT != D_MT) ? nullptr : getenv("WAGG_DENSE_DBG")) {
             switch (atoi(dbg)) {
                 case 1: kern = (const void *)dense_mfma_kernel<float, 1>; break;
                 case 4: kern = (const void *)dense_mfma_kernel<float, 4>; break;
@@ -1140,7 +981,7 @@ static int dense_apply(wagg_dense *d, const T *X_dev, int64_t Tn, int64_t ldx, c
     WAGG_HIP(allow_dynamic_lds(kern, shmem));
     const T *xp = reinterpret_cast<const T *>(d->xp.p), *wp = reinterpret_cast<const T *>(d->W.p);
     T *slabs = reinterpret_cast<T *>(d->slabs.p);
-    int n_kt_a = n_kt, n_nt_a = n_nt, n_mb_a = n_mb, S_a = S, kps = kt_per_slice;
+    int n_kt_a = n_kt, n_nt_a = n_nt, n_mb_a = n_mb, S_a = r.S, kps = r.kt_per_slice;
     const int32_t *tkt = d->tile_kt.p;
     const int32_t *toff = tp ? tp->tab.p : nullptr;                       // tile-sparse: the launch's piece table
     const int32_t *slab_first = tp ? tp->tab.p + tp->slab_first_at : nullptr;
@@ -1156,18 +997,66 @@ static int dense_apply(wagg_dense *d, const T *X_dev, int64_t Tn, int64_t ldx, c
         const int *no_gate = nullptr;
         void *args_rm[] = {&X_dev, &wp, &n_kt_a, &n_nt_a, &n_mb_a, &S_a, &kps, &slabs, &tkt, &toff, &ldxB, &Tn_a, &no_gate};
         WAGG_HIP(launch_timed_ptr(true, kern_rm, dim3((unsigned)nblk), dim3(D_THREADS), args_rm, shmem, st));
-        hipLaunchKernelGGL((dense_reduce_kernel<T>), rgrid, dim3(256), 0, st, (const T *)slabs, n_nt, S, bm, Tn, d->R, den,
+        hipLaunchKernelGGL((dense_reduce_kernel<T>), rgrid, dim3(256), 0, st, (const T *)slabs, n_nt, r.S, bm, Tn, d->R, den,
                            out_dev, ldo, d->nonfinite.p, (const int *)nullptr, d->inf_dev + 1, slab_first);
         WAGG_HIP(hipGetLastError());
     }
-    hipLaunchKernelGGL((dense_pack_x_kernel<T>), dim3(256 * 16), dim3(256), 0, st, X_dev, Tn, ldx, d->G, n_kt, bm, x_slots,
+    hipLaunchKernelGGL((dense_pack_x_kernel<T>), dim3(256 * 16), dim3(256), 0, st, X_dev, Tn, ldx, d->G, n_kt, bm, r.x_slots,
                        aligned, reinterpret_cast<vec_t *>(d->xp.p), xf, d->inf_dev, gate);
     WAGG_HIP(hipGetLastError());
     void *args[] = {&xp, &wp, &n_kt_a, &n_nt_a, &n_mb_a, &S_a, &kps, &slabs, &tkt, &toff, &ldxB, &Tn_a, &gate};
     WAGG_HIP(launch_timed_ptr(!rm, kern, dim3((unsigned)nblk), dim3(D_THREADS), args, shmem, st));
-    hipLaunchKernelGGL((dense_reduce_kernel<T>), rgrid, dim3(256), 0, st, (const T *)slabs, n_nt, S, bm, Tn, d->R, den,
+    hipLaunchKernelGGL((dense_reduce_kernel<T>), rgrid, dim3(256), 0, st, (const T *)slabs, n_nt, r.S, bm, Tn, d->R, den,
                        out_dev, ldo, (int *)nullptr, gate, (int *)nullptr, slab_first);
     WAGG_HIP(hipGetLastError());
+    return WAGG_OK;
+}
+
+// The launch itself: the batch goes through in groups of dense_rows_max rows, each as the one or two row groups of
+// dense_row_groups, each of those by the route dense_launch_route gives it (wagg_dense_route.h) -- same stream, same
+// workspaces, one launch group after the other.
+template <typename T>
+static int dense_apply(wagg_dense *d, const T *X_dev, int64_t Tn, int64_t ldx, const PackXfT<T> &xf,
+                       T *out_dev, int64_t ldo, int ksplit, void *stream, bool exact = false) {
+    WAGG_REQUIRE(d != nullptr, "dense plan is NULL");
+    WAGG_REQUIRE(d->f64 == (sizeof(T) == 8), "this plan holds %s weights: use the matching wagg_dense_apply_*",
+                 d->f64 ? "fp64" : "fp32");
+    WAGG_REQUIRE(Tn >= 0, "T < 0");
+    if (Tn == 0) return WAGG_OK;
+    WAGG_REQUIRE(X_dev && out_dev, "X/out is NULL");
+    WAGG_REQUIRE(xf.mode != XF_EDD || xf.X2 != nullptr, "tasmax is NULL");
+    WAGG_REQUIRE(ldx >= d->G && ldo >= d->R, "ldx/ldo too small");
+    WAGG_REQUIRE(ksplit >= 0 && ksplit % 8 == 0, "ksplit must be 0 or a multiple of 8");
+    hipStream_t st = (hipStream_t)stream;
+    if (d->spmm) return spmm_apply<T>(d, X_dev, Tn, ldx, xf, out_dev, ldo, st);
+    constexpr int elem = (int)sizeof(T);
+    constexpr int64_t rows_max = dense_rows_max(elem);
+    const DensePlanScalars plan = dense_plan_scalars(d);
+    for (int64_t t0 = 0; t0 < Tn; t0 += rows_max) {
+        const DenseRowGroups groups = dense_row_groups(elem, Tn - t0 < rows_max ? Tn - t0 : rows_max);
+        for (int i = 0; i < groups.n; ++i) {
+            const DenseRowGroup &g = groups.g[i];
+            const T *Xg = X_dev + (t0 + g.row0) * ldx;
+            T *og = out_dev + (t0 + g.row0) * ldo;
+            PackXfT<T> xg = xf;
+            if (xg.X2) xg.X2 += (t0 + g.row0) * ldx;
+            DenseCall c;
+            c.MT = g.MT; c.n_mb = g.n_mb; c.rows = g.rows;
+            c.ksplit = ksplit; c.exact = exact; c.xf_mode = xg.mode;
+            c.aligned16 = ((ldx * sizeof(T)) % 16 == 0) && ((reinterpret_cast<uintptr_t>(Xg) & 15) == 0) &&
+                          (xg.mode != XF_EDD || (reinterpret_cast<uintptr_t>(xg.X2) & 15) == 0);
+            c.nonfinite_met = ((volatile int *)d->inf_host)[1] != 0;
+            const DenseRoute r = dense_launch_route(plan, c);
+            int rc;
+            if constexpr (elem == 4) {
+                rc = r.form == DENSE_FORM_SPLIT ? dense_launch_split(d, Xg, g.rows, ldx, xg, og, ldo, g.MT, g.n_mb, r, c.aligned16, st)
+                                                : dense_launch_mfma<T>(d, Xg, g.rows, ldx, xg, og, ldo, g.MT, g.n_mb, r, c.aligned16, st);
+            } else {
+                rc = dense_launch_mfma<T>(d, Xg, g.rows, ldx, xg, og, ldo, g.MT, g.n_mb, r, c.aligned16, st);
+            }
+            if (rc != WAGG_OK) return rc;
+        }
+    }
     return WAGG_OK;
 }
 
