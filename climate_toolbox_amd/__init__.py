@@ -1,7 +1,7 @@
 """MI355X-native weighted grid->region aggregation engine: a drop-in for the aggregation path of
 ClimateImpactLab/climate_toolbox (``climate_toolbox.aggregations``).  See DESIGN.md."""
 
-__version__ = "0.14.0"
+__version__ = "0.15.0"
 
 from .aggregations import (  # noqa: F401
     weighted_aggregate_grid_to_regions,
@@ -41,5 +41,6 @@ from .transformations import (  # noqa: F401  (tas_poly fused into 
     tas_rcspline_aggregate,
     tas_spell_aggregate,
     tas_rolling_aggregate,
+    tas_quantile_aggregate,
     validate_edd_snyder_agriculture,
 )

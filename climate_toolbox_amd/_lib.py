@@ -54,6 +54,7 @@ EXPORTS = (
     "wagg_exposure_reduce_f32", "wagg_exposure_reduce_f64", "wagg_exposure_work_bytes",
     "wagg_spell_reduce_f32", "wagg_spell_reduce_f64", "wagg_spell_work_bytes",
     "wagg_rolling_reduce_f32", "wagg_rolling_reduce_f64", "wagg_rolling_work_bytes",
+    "wagg_quantile_select_f32", "wagg_quantile_select_f64",
     "wagg_plan_compact_info", "wagg_plan_compact_cells", "wagg_pack_rows_f32", "wagg_pack_rows_f64",
     "wagg_pack_rows_host_f32", "wagg_pack_rows_host_f64",
 )
@@ -80,6 +81,8 @@ SPELL_DAYS, SPELL_EVENTS, SPELL_LONGEST = 0, 1, 2        # ... and the statistic
 ROLL_WINDOW_MAX, ROLL_MAX_WINDOWS, ROLL_GROUP = 16, 8, 8 # WAGG_ROLL_*: the longest window in days / windows a call takes / a block serves
 ROLL_MAX, ROLL_MIN = 0, 1                        # ... the extreme of a call
 ROLL_MEAN, ROLL_SUM = 0, 1                       # ... and what it is the extreme of
+QUANT_MAX, QUANT_ROWS_MAX = 16, 1024             # WAGG_QUANT_*: quantiles a call takes / the longest period list (128 B of LDS an entry)
+QUANT_LINEAR, QUANT_LOWER, QUANT_HIGHER = 0, 1, 2        # ... and the method of a call
 
 
 class HostStats(C.Structure):
@@ -322,6 +325,9 @@ def load():
                                      C.c_int, C.c_int, C.c_int, vp, C.c_int64, C.c_int64, vp, vp, C.c_int64, vp]
     L.wagg_rolling_work_bytes.argtypes = [C.c_int64, C.c_int32, C.c_int64, C.c_int]
     L.wagg_rolling_work_bytes.restype = C.c_int64
+    for name in ("wagg_quantile_select_f32", "wagg_quantile_select_f64"):
+        getattr(L, name).argtypes = [vp, C.c_int64, C.c_int64, C.c_int64, vp, vp, C.c_int32, C.c_int64, vp, vp, C.c_double, f64p, C.c_int,
+                                     C.c_int, C.c_int32, C.c_int, vp, C.c_int64, C.c_int64, vp, vp, C.c_int64, vp]
     for name in ("wagg_hinge_reduce_f32", "wagg_hinge_reduce_f64"):
         getattr(L, name).argtypes = [vp, C.c_int64, C.c_int64, C.c_int64, vp, vp, C.c_int32, C.c_int64, vp, vp, C.c_double, f64p, C.c_int,
                                      C.c_int, C.c_int, f64p, f64p, f64p, C.c_int, vp, C.c_int64, C.c_int64, vp, vp, C.c_int64, vp]

@@ -900,8 +900,8 @@ def _season_vector(a, length, what, device):
 
 
 class _RowlistCall:
-    """What the eight row-list calls -- :func:`period_reduce`, :func:`season_reduce` and, through :func:`_grouped_reduce`,
-    :func:`edd_ladder_reduce`, :func:`exposure_reduce`, :func:`bin_days_reduce`, :func:`hinge_reduce`, :func:`spell_reduce` and :func:`rolling_reduce` -- do alike around
+    """What the nine row-list calls -- :func:`period_reduce`, :func:`season_reduce` and, through :func:`_grouped_reduce`,
+    :func:`edd_ladder_reduce`, :func:`exposure_reduce`, :func:`bin_days_reduce`, :func:`hinge_reduce`, :func:`spell_reduce`, :func:`rolling_reduce` and :func:`quantile_select` -- do alike around
     their library call, in the order they do it: the row lists (and, with ``season = (doy, windows)``, those two vectors) as int32 CUDA tensors and ``P``;
     then ``out``, ``status`` and the workspace; at the end what must outlive the kernels on the caller's stream."""
 
@@ -1027,7 +1027,7 @@ def season_reduce(X, row_begin, rows, doy, windows, X2=None, poly=None, edd=None
 def _grouped_reduce(name, fields, row_begin, rows, doy, windows, checked, offset, middle, planes, work_bytes, out, status, workspace,
                     stream):
     """What :func:`edd_ladder_reduce`, :func:`exposure_reduce`, :func:`bin_days_reduce`, :func:`hinge_reduce`,
-    :func:`spell_reduce` and :func:`rolling_reduce` do alike behind their own validation: the doy / windows pairing, the :class:`_RowlistCall`, ``out`` / ``status`` / workspace, and the library call ``name`` + ``_f32``
+    :func:`spell_reduce`, :func:`rolling_reduce` and :func:`quantile_select` do alike behind their own validation: the doy / windows pairing, the :class:`_RowlistCall`, ``out`` / ``status`` / workspace, and the library call ``name`` + ``_f32``
     or ``_f64`` by the dtype of ``fields`` (one checked (T, n) tensor, or tasmin and tasmax) -- the fields and the arguments
     every grouped entry point begins with (sizes, lists, season, ``offset``), the family's ``middle`` ones, and the ones every
     one ends with (flags, ``out`` and its strides, status, workspace, stream).  ``work_bytes(L, n, P, n_rows, planes)``: the
@@ -1212,6 +1212,63 @@ def rolling_reduce(X, row_begin, rows, offset, lengths, stat="max", of="mean", d
     return _grouped_reduce("wagg_rolling_reduce", (X,), row_begin, rows, doy, windows, checked, offset,
                            (_np_ptr(w32, C.c_int32), len(w32), _ROLL_STATS[stat], _ROLL_OF[of]), len(w32),
                            lambda L, *a: L.wagg_rolling_work_bytes(*a), out, status, False, stream)
+
+
+_QUANT_METHODS = {"linear": _lib.QUANT_LINEAR, "lower": _lib.QUANT_LOWER, "higher": _lib.QUANT_HIGHER}
+
+
+def _quantile_levels(q):
+    """``q`` as a float64 vector in the caller's order: 1 .. ``_lib.QUANT_MAX`` finite numbers in [0, 1] (no bool) -- else ValueError"""
+    try:
+        raw = list(np.atleast_1d(np.asarray(q, dtype=object)))
+    except (TypeError, ValueError):
+        raise ValueError("q must be a sequence of numbers in [0, 1], got %r" % (q,)) from None
+    if not 1 <= len(raw) <= _lib.QUANT_MAX:
+        raise ValueError("1..%d quantiles per call, got %d" % (_lib.QUANT_MAX, len(raw)))
+    for v in raw:
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)) or not 0.0 <= float(v) <= 1.0:
+            raise ValueError("a quantile must be a finite number in [0, 1], got %r" % (v,))
+    return np.ascontiguousarray([float(v) for v in raw], dtype=np.float64)
+
+
+def quantile_select(X, row_begin, rows, offset, q, method="linear", max_rows=None, doy=None, windows=None, checked=False, out=None,
+                    status=None):
+    """Per-cell quantiles of the daily values of every period, for every level of ``q`` in ONE launch
+    (``wagg_quantile_select_*``).  Entry ``i`` of period ``p``'s list is valid for cell ``j`` when its row ``t`` lies in the
+    field, the cell is in season on ``doy[t]`` and ``X[t, j]`` is not NaN; order and gaps do not matter, a row listed twice
+    counts twice, an in-season +-inf is valid.  With ``m`` valid entries and ``v[0] <= ... <= v[m - 1]`` their raw elements
+    sorted: ``h = (m - 1) * q[k]`` in fp64, ``lo = floor(h)``, ``g = h - lo``; ``method="linear"``: ``v[lo] + (v[lo + 1] - v[lo])
+    * g`` in fp64 without a fused multiply-add (``v[lo]`` itself where ``g == 0``), ``"lower"``: ``v[lo]``, ``"higher"``:
+    ``v[lo + 1]`` (``v[lo]`` where ``g == 0``).  ``out[k, p, j]`` is that plus ``offset``, rounded once to ``X``'s dtype, and NaN
+    where the period holds no valid entry for the cell.  ``X``: a (T, n) CUDA tensor; ``q``: 1 .. ``_lib.QUANT_MAX`` finite
+    numbers in [0, 1] in any order, duplicates allowed (a bool, a NaN or a value outside is ValueError); ``row_begin`` / ``rows``
+    / ``doy`` / ``windows`` / ``checked`` as for :func:`rolling_reduce`.  ``max_rows``: the caller's bound on the longest list, 1
+    .. ``_lib.QUANT_ROWS_MAX`` -- a block holds its period's whole list in 128 * ``max_rows`` bytes of LDS; None takes the
+    longest list itself: from host integers at no cost, FROM DEVICE LISTS WITH ONE ``row_begin.diff().max()`` THAT BLOCKS.  A
+    list longer than ``max_rows`` is an error of the library's look at the lists; with ``checked=True`` (no look) the kernel
+    writes NaN for that period and sets bit 1 of the status word.  There is no workspace: a list is never split.  THERE IS NO
+    ``stream=`` KEYWORD YET: the call runs on torch's current stream; the keyword comes together with its stream-order probe.
+    Returns ``(out, status)``: the (n_q, P, n) tensor and the status word (bit 0: an in-season value was +-inf; bit 1: a list
+    was longer than ``max_rows``)."""
+    import torch
+    X = _check_X(X, "TG")
+    qv = _quantile_levels(q)
+    if method not in _QUANT_METHODS:
+        raise ValueError("method must be 'linear', 'lower' or 'higher', got %r" % (method,))
+    if max_rows is None:
+        if isinstance(row_begin, torch.Tensor):
+            longest = int(row_begin.diff().max().item()) if row_begin.numel() > 1 else 0        # (blocks)
+        else:
+            rb = np.asarray(row_begin, dtype=np.int64)
+            longest = int(np.diff(rb).max()) if rb.ndim == 1 and len(rb) > 1 else 0
+        if longest > _lib.QUANT_ROWS_MAX:
+            raise ValueError("a period lists %d rows; a quantile call holds at most %d" % (longest, _lib.QUANT_ROWS_MAX))
+        max_rows = max(1, longest)
+    if isinstance(max_rows, (bool, np.bool_)) or not isinstance(max_rows, (int, np.integer)) or not 1 <= max_rows <= _lib.QUANT_ROWS_MAX:
+        raise ValueError("max_rows must be an integer in 1..%d, got %r" % (_lib.QUANT_ROWS_MAX, max_rows))
+    return _grouped_reduce("wagg_quantile_select", (X,), row_begin, rows, doy, windows, checked, offset,
+                           (_np_ptr(qv, C.c_double), len(qv), _QUANT_METHODS[method], int(max_rows)), len(qv),
+                           lambda L, *a: 0, out, status, False, None)
 
 
 def hinge_reduce(X, row_begin, rows, offset, knots, power=1, side="above", tail=None, doy=None, windows=None, checked=False, out=None,

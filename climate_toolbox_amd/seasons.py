@@ -36,6 +36,7 @@ from ._layout import _flatten_for_device, _is_device_tensor, _result_dims, _spat
 from ._lib import BIN_EDGES_MAX as _BIN_EDGES_MAX, EDD_LADDER_MAX as _EDD_LADDER_MAX, HINGE_MAX as _HINGE_MAX, SEASON_INVERT, SEASON_NULL
 from ._lib import SPELL_MAX as _SPELL_MAX
 from ._lib import ROLL_MAX_WINDOWS as _ROLL_MAX_WINDOWS
+from ._lib import QUANT_MAX as _QUANT_MAX
 from ._lib import EXPOSURE_EDGES_MAX as _EXPOSURE_EDGES_MAX
 from ._plans import _drop_plan, _plan_for
 from ._prepared import PreparedWeights
@@ -366,7 +367,7 @@ def _plain_variable(ds, variable, what):
 
 def _grouped_totals(ds, variable, aggwt, agglev, weights, backup_aggwt, lists, P, season, grid, time_values, cells, name, of, rule,
                     launches):
-    """The sum-first route of the grouped statistics (ladder, bins, hinges, exposure bins, spells, rolling extremes): every launch reduces its planes per period
+    """The sum-first route of the grouped statistics (ladder, bins, hinges, exposure bins, spells, rolling extremes, period quantiles): every launch reduces its planes per period
     first, then one apply per launch contracts its planes * P rows on whatever plan serves the table.  ``name`` / ``of``: the statistic in
     the messages ("bin count" / "bins"); ``rule(ds, variable, what)``: ``(second field or None, offset)`` of a variable the
     statistic takes, ValueError for any other; ``launches``: an iterable, consumed as the launches run, of
@@ -490,3 +491,19 @@ def _rolling_totals(ds, variable, aggwt, agglev, weights, backup_aggwt, lists, P
 
     return _grouped_totals(ds, variable, aggwt, agglev, weights, backup_aggwt, lists, P, season, grid, time_values, cells,
                            "rolling extreme", "rolling windows", _plain_variable, launches())
+
+
+def _quantile_totals(ds, variable, aggwt, agglev, weights, backup_aggwt, lists, P, q, method, max_rows, season, grid, time_values,
+                     cells="all"):
+    """Per-cell quantiles of ``variable`` over the days of every period at EVERY level of ``q`` (``wagg_quantile_select_*``, up
+    to 16 levels a launch) through :func:`_grouped_totals`.  ``variable``: as for :func:`_bin_totals`; ``max_rows``: the longest
+    period list, which the caller knows from the host lists.  A cell without a valid day in a period is NaN there, which the
+    contraction treats as any NaN of a field (it counts 0, its weight stays in the denominator: DESIGN.md, S6).  ``stack`` is the
+    (n_q, P | R, R | P) results in the levels' order."""
+    def launches():
+        for k0 in range(0, len(q), _QUANT_MAX):
+            part = [float(v) for v in q[k0:k0 + _QUANT_MAX]]
+            yield lambda X, H, rb, rw, offset, **kw: _engine.quantile_select(X, rb, rw, offset, part, method=method, max_rows=max_rows, **kw)
+
+    return _grouped_totals(ds, variable, aggwt, agglev, weights, backup_aggwt, lists, P, season, grid, time_values, cells,
+                           "period quantile", "quantiles", _plain_variable, launches())

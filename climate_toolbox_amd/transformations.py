@@ -26,6 +26,7 @@ from . import aggregations as _agg
 __all__ = ["tas_poly", "tas_poly_aggregate", "snyder_edd", "snyder_gdd", "snyder_edd_aggregate", "snyder_exposure_aggregate",
            "tas_bins_aggregate",
            "tas_hinge_aggregate", "tas_rcspline_aggregate", "tas_spell_aggregate", "tas_rolling_aggregate",
+           "tas_quantile_aggregate",
            "validate_edd_snyder_agriculture", "ordinal", "remove_leap_days", "convert_kelvin_to_celsius"]
 
 KELVIN = 273.15
@@ -258,6 +259,7 @@ def _period_lists(ds, period, season):
             cache[str(device)] = periods._engine.period_lists(row_begin, rows, len(time_values), device=device)
         return cache[str(device)]
 
+    lists.row_begin = np.asarray(row_begin, dtype=np.int64)          # (the host offsets: a caller that needs the lists' lengths)
     return time_values, labels, grid, lists
 
 
@@ -694,6 +696,77 @@ def tas_rolling_aggregate(ds, windows, aggwt, agglev, weights, stat="max", of="m
         out[varname].attrs["units"] = units
     out[varname].attrs["stat"] = stat
     out[varname].attrs["of"] = of
+    return out
+
+
+def _quantile_levels(q):
+    """``q`` as a float64 vector in the caller's order: at least one finite number in [0, 1] (duplicates allowed; no bool) --
+    else ValueError"""
+    try:
+        raw = list(q)
+    except TypeError:
+        raise ValueError("q must be a sequence of numbers in [0, 1], got %r" % (q,)) from None
+    if len(raw) < 1:
+        raise ValueError("q must be a non-empty sequence of numbers in [0, 1], got %r" % (q,))
+    for v in raw:
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)) or not 0.0 <= float(v) <= 1.0:
+            raise ValueError("q must be finite numbers in [0, 1], got %r" % (v,))
+    return np.array([float(v) for v in raw], dtype=np.float64)
+
+
+def tas_quantile_aggregate(ds, q, aggwt, agglev, weights, method="linear", tas="tas", varname="tas-quantile", backup_aggwt="areawt",
+                           period="year", season=None, cells="all", leap_days="keep"):
+    """Per-cell quantiles of the daily values of a period (and growing season), aggregated to regions: the annual (monthly,
+    in-season) median, the 5th / 95th / 99th percentile of a cell's days, with ``tas="pr"`` the R95p / R99p thresholds, the
+    "typical hot day" of mortality and energy studies -- the order statistics between the extremes of
+    :func:`tas_rolling_aggregate` (``windows=[1]``).  Selected exactly on the device in ONE pass per 16 levels
+    (``wagg_quantile_select_*``) instead of a ``torch.quantile`` or ``torch.sort`` of a full (T, G) field per period.
+
+    For a cell and a period, the VALID days are those of the period that are present, in season and not NaN; their order does not
+    matter.  With ``m`` valid days sorted ``v[0] <= ... <= v[m - 1]``, level ``q`` sits at ``h = (m - 1) * q``: ``lo = floor(h)``,
+    ``g = h - lo``, and the value is ``v[lo] + (v[lo + 1] - v[lo]) * g`` (``method="linear"``, NumPy's default), ``v[lo]``
+    (``"lower"``) or ``v[lo + 1]`` (``"higher"``; ``v[lo]`` where ``g == 0``), formed in fp64 from the raw elements; a Kelvin shift
+    is applied once to the result, never to single days.
+
+    THE REGIONAL VALUE IS THE WEIGHTED MEAN OF THE PER-CELL QUANTILES, not a quantile of the regional mean: every cell takes its
+    own 95th-percentile day, which need not be the same day across a region.
+
+    A CELL WITHOUT A VALID DAY in a period (NaN throughout, a season that misses the period) has NO VALUE there: it is NaN for
+    that period at every level, and the regional mean treats it as it treats any NaN of a field -- the cell adds nothing and its
+    weight stays in the denominator.  A counted +-inf raises ValueError.
+
+    q         a non-empty sequence of finite numbers in [0, 1] in any order, duplicates allowed; a bool, a NaN or anything outside
+              is ValueError.  More than 16 go in several launches.
+    method    "linear", "lower" or "higher", else ValueError.
+    tas       the variable: a plain field or a Kelvin-shifted one; a power (``tas_poly``) or a degree-day variable is ValueError.
+    period    "year", "month" or a label per day; required (None is ValueError).  A PERIOD OF MORE THAN 1024 DAYS is ValueError:
+              a cell's whole period is held on the chip at once.
+    season, cells, leap_days   exactly as in :func:`tas_bins_aggregate`.
+
+    Returns one Dataset with the variable ``varname`` of dims ``("quantile", "period", agglev)`` (the last two in the order the
+    period call gives them), the coordinate ``quantile`` = ``q`` as float64 in the caller's order, ``attrs["units"]`` = the
+    variable's units (``"C"`` when it carries the Kelvin shift) and ``attrs["method"]``; ``results_on_device()`` is honoured."""
+    from ._lib import QUANT_ROWS_MAX
+    qv = _quantile_levels(q)
+    if method not in ("linear", "lower", "higher"):
+        raise ValueError("method must be 'linear', 'lower' or 'higher', got %r" % (method,))
+    re, var, weights, time_values, labels, grid, lists = _period_setup("tas_quantile_aggregate", "a period quantile", ds, tas, weights,
+                                                                       period, season, cells, leap_days)
+    counts = np.diff(lists.row_begin)
+    if len(counts) and int(counts.max()) > QUANT_ROWS_MAX:
+        worst = int(np.argmax(counts))
+        raise ValueError("tas_quantile_aggregate: period %s lists %d days; a period quantile holds at most %d days of a period"
+                         % (labels[worst], int(counts[worst]), QUANT_ROWS_MAX))
+    max_rows = max(1, int(counts.max()) if len(counts) else 1)
+    from . import seasons
+    res, rdims, coords, was_xr = seasons._quantile_totals(re, tas, aggwt, agglev, weights, backup_aggwt, lists, len(labels), qv, method,
+                                                          max_rows, season, grid, time_values, cells=cells)
+    rdims, coords = _time_as_period(rdims, coords, labels)
+    out = _agg._as_dataset({varname: res}, ("quantile",) + tuple(rdims), dict(coords, quantile=qv.copy()), was_xr)
+    units = "C" if getattr(var, "_xform", None) is not None else _units(var)
+    if units is not None:
+        out[varname].attrs["units"] = units
+    out[varname].attrs["method"] = method
     return out
 
 

@@ -85,7 +85,8 @@ int wagg_version(void);                 /* 10000*major + 100*minor + patch; 0.4.
                                            wagg_host_stats has 18 fields; 0.5.0: many-plans (wagg_plan_create_many);
                                            0.9.0: packed rows (wagg_pack_rows_*, WAGG_APPLY_COMPACT_ROWS);
                                            0.13.0: spell statistics (wagg_spell_reduce_*);
-                                           0.14.0: rolling-window extremes (wagg_rolling_reduce_*) */
+                                           0.14.0: rolling-window extremes (wagg_rolling_reduce_*);
+                                           0.15.0: period quantiles (wagg_quantile_select_*) */
 int wagg_device_count(void);            /* number of visible HIP devices (0 if none), never <0  */
 /* Time-axis sharding rule of the multi-GPU form (one process per GPU; climate_toolbox_amd/timeshard.py):
  * rank `rank` of `world` owns rows [*start, *stop) of T; the first T mod world ranks hold one row more. */
@@ -966,6 +967,44 @@ int wagg_rolling_reduce_f64(const double *X_dev, int64_t T, int64_t n, int64_t l
                             double offset, const int32_t *windows, int n_win, int stat, int of, int flags, double *out_dev, int64_t ldo,
                             int64_t out_pstride, int32_t *status_dev, void *work_dev, int64_t work_bytes, void *stream);
 int64_t wagg_rolling_work_bytes(int64_t n, int32_t P, int64_t n_rows, int n_win);
+
+/* ---- period quantiles: per-cell order statistics of the daily values of a period and season (0.15.0) --------------------------
+ * The median, the 5th / 95th / 99th percentile, R95p thresholds: for q[k],  k = 0 .. n_q - 1,  1 <= n_q <= WAGG_QUANT_MAX, in one
+ * launch.  Cell j, period p, the entries i of rows[row_begin[p] : row_begin[p + 1]]: entry i is VALID when t = rows[i] lies in
+ * [0, T), cell j is in season on doy[t] (when a season is given) and X[t, j] is not NaN.  Order and gaps do not matter, a row
+ * listed twice counts twice, an in-season +-inf is valid (and sets bit 0 of status_dev).  Let m be the number of valid entries
+ * and v[0] <= ... <= v[m - 1] their raw elements sorted (-0.0 ahead of +0.0: equal as numbers).  For every q[k]:
+ *   h = (double)(m - 1) * q[k]   (one fp64 product),   lo = (int)floor(h),   g = h - (double)lo
+ *   WAGG_QUANT_LINEAR   r = g == 0 ? (double)v[lo] : (double)v[lo] + ((double)v[lo + 1] - (double)v[lo]) * g
+ *                       (difference, product and sum each rounded: no fused multiply-add)
+ *   WAGG_QUANT_LOWER    r = v[lo]
+ *   WAGG_QUANT_HIGHER   r = v[g == 0 ? lo : lo + 1]
+ *   out[k][p][j] = (T)(r + offset), rounded once;  m == 0 gives NaN.
+ * Arguments as for wagg_rolling_reduce_*, except
+ *   q, n_q             n_q host doubles in [0, 1], any order, duplicates allowed; plane k of out_dev is q[k]
+ *   method             WAGG_QUANT_LINEAR / _LOWER / _HIGHER; offset finite
+ *   max_rows           1 .. WAGG_QUANT_ROWS_MAX: the caller's bound on the longest list; a block holds its period's whole list in
+ *                      128 * max_rows bytes of LDS.  Without WAGG_PERIOD_ROWS_CHECKED the blocking look at the lists also
+ *                      rejects a list longer than max_rows (WAGG_EINVAL).  With the flag the kernel confines itself: a period
+ *                      whose list is longer writes NaN in every plane and sets bit 1 of status_dev.
+ *   work_dev, work_bytes   IGNORED.  An order statistic does not add across the parts of a list, so a list is never split;
+ *                      there is no *_work_bytes.
+ * Every bad argument is WAGG_EINVAL with a message, decided before any device call.  A value out of season is never looked at.
+ * The selection is exact: the results equal a NumPy restatement bit for bit (tests/quantile_ref.py), plane k of a many-quantile
+ * call is the plane of the call with q[k] alone, and q = 1 / q = 0 are wagg_rolling_reduce_*'s W = 1 maximum / minimum. */
+#define WAGG_QUANT_MAX 16
+#define WAGG_QUANT_ROWS_MAX 1024
+#define WAGG_QUANT_LINEAR 0
+#define WAGG_QUANT_LOWER 1
+#define WAGG_QUANT_HIGHER 2
+int wagg_quantile_select_f32(const float *X_dev, int64_t T, int64_t n, int64_t ldx, const int32_t *row_begin_dev,
+                             const int32_t *rows_dev, int32_t P, int64_t n_rows, const int32_t *doy_dev, const int32_t *win_dev,
+                             double offset, const double *q, int n_q, int method, int32_t max_rows, int flags, float *out_dev,
+                             int64_t ldo, int64_t out_pstride, int32_t *status_dev, void *work_dev, int64_t work_bytes, void *stream);
+int wagg_quantile_select_f64(const double *X_dev, int64_t T, int64_t n, int64_t ldx, const int32_t *row_begin_dev,
+                             const int32_t *rows_dev, int32_t P, int64_t n_rows, const int32_t *doy_dev, const int32_t *win_dev,
+                             double offset, const double *q, int n_q, int method, int32_t max_rows, int flags, double *out_dev,
+                             int64_t ldo, int64_t out_pstride, int32_t *status_dev, void *work_dev, int64_t work_bytes, void *stream);
 
 /* ---- packed rows: only the quads a segment table references, as a device matrix (0.9.0) ---------------------------------------
  * A single segment-table plan with a whole-line chunking (wagg_plan_info.lines) knows the distinct aligned 4-cell QUADS of a
