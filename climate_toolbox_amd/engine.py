@@ -1232,7 +1232,7 @@ def _quantile_levels(q):
 
 
 def quantile_select(X, row_begin, rows, offset, q, method="linear", max_rows=None, doy=None, windows=None, checked=False, out=None,
-                    status=None):
+                    status=None, stream=None):
     """Per-cell quantiles of the daily values of every period, for every level of ``q`` in ONE launch
     (``wagg_quantile_select_*``).  Entry ``i`` of period ``p``'s list is valid for cell ``j`` when its row ``t`` lies in the
     field, the cell is in season on ``doy[t]`` and ``X[t, j]`` is not NaN; order and gaps do not matter, a row listed twice
@@ -1246,8 +1246,10 @@ def quantile_select(X, row_begin, rows, offset, q, method="linear", max_rows=Non
     .. ``_lib.QUANT_ROWS_MAX`` -- a block holds its period's whole list in 128 * ``max_rows`` bytes of LDS; None takes the
     longest list itself: from host integers at no cost, FROM DEVICE LISTS WITH ONE ``row_begin.diff().max()`` THAT BLOCKS.  A
     list longer than ``max_rows`` is an error of the library's look at the lists; with ``checked=True`` (no look) the kernel
-    writes NaN for that period and sets bit 1 of the status word.  There is no workspace: a list is never split.  THERE IS NO
-    ``stream=`` KEYWORD YET: the call runs on torch's current stream; the keyword comes together with its stream-order probe.
+    writes NaN for that period and sets bit 1 of the status word.  There is no workspace: a list is never split.  ``stream=``
+    as for :func:`rolling_reduce`: the kernel, the zero-fill of ``status`` and the tensors allocated here are ordered on it --
+    but the ``row_begin.diff().max()`` of ``max_rows=None`` on device lists runs on torch's CURRENT stream and blocks, so a
+    caller who wants a non-blocking call on ``stream`` passes ``max_rows``.
     Returns ``(out, status)``: the (n_q, P, n) tensor and the status word (bit 0: an in-season value was +-inf; bit 1: a list
     was longer than ``max_rows``)."""
     import torch
@@ -1268,7 +1270,7 @@ def quantile_select(X, row_begin, rows, offset, q, method="linear", max_rows=Non
         raise ValueError("max_rows must be an integer in 1..%d, got %r" % (_lib.QUANT_ROWS_MAX, max_rows))
     return _grouped_reduce("wagg_quantile_select", (X,), row_begin, rows, doy, windows, checked, offset,
                            (_np_ptr(qv, C.c_double), len(qv), _QUANT_METHODS[method], int(max_rows)), len(qv),
-                           lambda L, *a: 0, out, status, False, None)
+                           lambda L, *a: 0, out, status, False, stream)
 
 
 def hinge_reduce(X, row_begin, rows, offset, knots, power=1, side="above", tail=None, doy=None, windows=None, checked=False, out=None,

@@ -1,9 +1,11 @@
-"""Layouts for calling the row-list reductions (wagg_*_reduce_f32 / _f64, include/wagg.h) as the C-ABI allows them and the
-binding never does: a pitched result (ldo > n, out_pstride > P * ldo) at an odd base, fields that are views into poisoned
-buffers, a field base that is one element off a 16-byte boundary, a workspace smaller than the family's own *_work_bytes.
+"""Layouts for calling the row-list reductions (wagg_*_reduce_f32 / _f64 and wagg_quantile_select_f32 / _f64, include/wagg.h) as
+the C-ABI allows them and the binding never does: a pitched result (ldo > n, out_pstride > P * ldo) at an odd base, fields that
+are views into poisoned buffers, a field base that is one element off a 16-byte boundary, a workspace smaller than the family's
+own *_work_bytes -- or, for the family that has none and promises to ignore the argument, a workspace that must stay untouched.
 Nothing here needs a GPU: tests/test_rowlist_layout_host.py checks this module, tests/test_gpu_rowlist_layout.py runs it.
 
-FAMILIES is the case table: one row per family with the middle of its argument list, its planes, its engine twin and its
+FAMILIES is the case table: one row per family -- nine: eight reductions and the period quantiles -- with its entry symbol, the
+middle of its argument list, its planes, its engine twin and its
 reference -- the plain restatements the families' own tests use, imported, on the unpoisoned logical field.
 
 The field of a call: GUARD elements, the (T, ldx) body, GUARD elements.  Listed, in-season cells hold the logical values; the
@@ -17,6 +19,7 @@ import ctypes as C
 import numpy as np
 
 from tests import exposure_ref as ER
+from tests.quantile_ref import quantile_ref
 from tests.rolling_ref import rolling_ref
 from tests.spell_ref import in_season, spell_ref
 from tests.test_gpu_bins import _restate
@@ -136,6 +139,19 @@ def per_part(planes, P, n):
     return 8 * planes * P * n
 
 
+def full_work_bytes(L, fam, v, n, P, n_rows):
+    """the "full" workspace of a call: the family's own *_work_bytes -- or, for a family without one (fam.work_bytes is None: it
+    ignores work / work_bytes), a fixed non-zero size, three parts, every byte of which must keep its sentinel"""
+    if fam.work_bytes is None:
+        return 3 * per_part(v.planes, P, n)
+    return int(getattr(L, fam.work_bytes)(n, P, n_rows, work_count(fam, v)))
+
+
+def symbol(fam, dtype):
+    """the family's entry point for an element type"""
+    return "%s_%s" % (fam.entry, "f32" if np.dtype(dtype) == np.dtype(F32) else "f64")
+
+
 def work_bytes_of(kind, full, planes, P, n):
     return {"full": full, "three": 3 * per_part(planes, P, n), "one": per_part(planes, P, n) + 8, "none": 0}[kind]
 
@@ -203,12 +219,13 @@ def _dp(a):
 
 
 Variant = collections.namedtuple("Variant", "id two_fields planes p")
-# name: wagg_<name>_reduce_f32 / _f64; work_bytes: the export; count_extra: what *_work_bytes takes beyond the planes (edges);
+# name: the family; entry: its symbol without _f32 / _f64 (wagg_<name>_reduce for all but the quantiles); work_bytes: the export, or
+# None for a family that has none and ignores work / work_bytes (it never splits: splits is False); count_extra: what *_work_bytes takes beyond the planes (edges);
 # season_args: "none" (no doy / win in the list), "always", "optional"; splits: does a list ever go through the workspace;
-# counting: integers, the same bits under every split; middle(v): the arguments between the common head and the common tail
-# (the arrays they point into are returned too and must outlive the call); twin(engine, X, X2, d, v): the binding's call;
+# counting: the same bits under every split (integers, or never split); middle(v, p): the arguments between the common head and
+# the common tail, p being build_args' dict (the arrays they point into are returned too and must outlive the call); twin(engine, X, X2, d, v): the binding's call;
 # check(got, d, v): asserts the (planes, P, n) result against the reference
-Family = collections.namedtuple("Family", "name work_bytes count_extra four_plane season_args splits counting variants middle twin check")
+Family = collections.namedtuple("Family", "name entry work_bytes count_extra four_plane season_args splits counting variants middle twin check")
 
 THR2 = [12.5, 3.0]
 THR9 = [float(t) for t in np.linspace(-10.0, 30.0, 9)]
@@ -224,7 +241,7 @@ def _season_kw(d):
     return {"doy": d.doy, "windows": d.win} if d.seasoned else {}
 
 
-def _mid_four(v):
+def _mid_four(v, p=None):
     import climate_toolbox_amd._lib as _lib
     if v.id == "poly":
         return [_lib.XF_POLY, KELVIN, 1, v.planes, None, 0], ()
@@ -262,7 +279,7 @@ def exact(got, want, what):
         what, len(bad), tuple(bad[0]), got[tuple(bad[0])], want[tuple(bad[0])])
 
 
-def _mid_list(v):
+def _mid_list(v, p=None):
     a = _dbl(v.p)
     return [_dp(a), len(a)], (a,)
 
@@ -276,7 +293,7 @@ def _hinge_p(v):
     return power, side, ((TAIL_KNOTS, TAIL_A, TAIL_B) if tail else None)
 
 
-def _mid_hinge(v):
+def _mid_hinge(v, p=None):
     import climate_toolbox_amd._lib as _lib
     power, side, tail = _hinge_p(v)
     k = _dbl(KNOTS9)
@@ -309,7 +326,7 @@ def _check_exposure(got, d, v):
     assert (want[1:, :, 2] == 0).all() and (want[:-1, :, 3] == 0).all() and (want[0, :, 2] == D[:, 2]).all() and (want[-1, :, 3] == D[:, 3]).all()
 
 
-def _mid_spell(v):
+def _mid_spell(v, p=None):
     import climate_toolbox_amd._lib as _lib
     L, stat, side = v.p
     a = _dbl(SPELL_THR)
@@ -323,7 +340,7 @@ def _check_spell(got, d, v):
     exact(got.astype(np.float64), spell_ref(d.X, d.rb, d.rows, KELVIN, SPELL_THR, L, stat, side, *sk), ("spell", d.n, v.id))
 
 
-def _mid_roll(v):
+def _mid_roll(v, p=None):
     import climate_toolbox_amd._lib as _lib
     lengths, stat, of = v.p
     w = np.ascontiguousarray(lengths, dtype=np.int32)
@@ -337,31 +354,66 @@ def _check_roll(got, d, v):
     exact(got, rolling_ref(d.X, d.rb, d.rows, KELVIN, lengths, stat, of, *sk), ("rolling", d.n, v.id))
 
 
+Q8 = [0.0, 0.05, 1.0 / 3.0, 0.5, 0.9, 0.95, 1.0, 0.5]
+Q16 = [0.5, 0.0, 1.0, 0.05, 0.95, 0.99, 0.01, 1.0 / 3.0, 2.0 / 3.0, 0.25, 0.75, 0.5, 0.1, 0.9, 0.125, 0.999]
+QUANT_ROWS_MAX = 1024
+
+
+def longest_list(rb):
+    return int(np.diff(np.asarray(rb)).max())
+
+
+def _quant_max_rows(v, longest):
+    """a variant's max_rows: its own, or (None) the longest list of the call"""
+    return longest if v.p[2] is None else v.p[2]
+
+
+def _mid_quantile(v, p):
+    import climate_toolbox_amd._lib as _lib
+    method, q, _ = v.p
+    a = _dbl(q)
+    return [_dp(a), len(a), {"linear": _lib.QUANT_LINEAR, "lower": _lib.QUANT_LOWER, "higher": _lib.QUANT_HIGHER}[method],
+            _quant_max_rows(v, p["longest"])], (a,)
+
+
+def _check_quantile(got, d, v):
+    method, q, _ = v.p
+    sk = (d.doy, d.win) if d.seasoned else (None, None)
+    exact(got, quantile_ref(d.X, d.rb, d.rows, KELVIN, q, method, *sk), ("quantile", d.n, v.id))
+
+
 _FOUR = (Variant("poly", False, 3, None), Variant("edd", True, 2, THR2))
 FAMILIES = {f.name: f for f in (
-    Family("period", "wagg_period_reduce_work_bytes", 0, True, "none", True, False, _FOUR, _mid_four,
+    Family("period", "wagg_period_reduce", "wagg_period_reduce_work_bytes", 0, True, "none", True, False, _FOUR, _mid_four,
            lambda e, X, X2, d, v: e.period_reduce(X, d.rb, d.rows, **_four_kw(X2, v)), _check_four),
-    Family("season", "wagg_season_reduce_work_bytes", 0, True, "always", True, False, _FOUR, _mid_four,
+    Family("season", "wagg_season_reduce", "wagg_season_reduce_work_bytes", 0, True, "always", True, False, _FOUR, _mid_four,
            lambda e, X, X2, d, v: e.season_reduce(X, d.rb, d.rows, d.doy, d.win, **_four_kw(X2, v)), _check_four),
-    Family("edd_ladder", "wagg_edd_ladder_work_bytes", 0, False, "optional", True, False, (Variant("thr9", True, 9, THR9),), _mid_list,
+    Family("edd_ladder", "wagg_edd_ladder_reduce", "wagg_edd_ladder_work_bytes", 0, False, "optional", True, False, (Variant("thr9", True, 9, THR9),), _mid_list,
            lambda e, X, X2, d, v: e.edd_ladder_reduce(X, X2, d.rb, d.rows, KELVIN, v.p, **_season_kw(d)),
            lambda got, d, v: _check_edd(got, d, v.p)),
-    Family("bin_days", "wagg_bin_days_work_bytes", 1, False, "optional", True, True, (Variant("bins9", False, 9, BIN_EDGES),), _mid_list,
+    Family("bin_days", "wagg_bin_days_reduce", "wagg_bin_days_work_bytes", 1, False, "optional", True, True, (Variant("bins9", False, 9, BIN_EDGES),), _mid_list,
            lambda e, X, X2, d, v: e.bin_days_reduce(X, d.rb, d.rows, KELVIN, v.p, **_season_kw(d)), _check_bins),
-    Family("hinge", "wagg_hinge_work_bytes", 0, False, "optional", True, False,
+    Family("hinge", "wagg_hinge_reduce", "wagg_hinge_work_bytes", 0, False, "optional", True, False,
            (Variant("p1-above", False, 9, (1, "above", False)), Variant("p2-below-tail", False, 9, (2, "below", True))), _mid_hinge,
            lambda e, X, X2, d, v: e.hinge_reduce(X, d.rb, d.rows, KELVIN, KNOTS9, power=_hinge_p(v)[0], side=_hinge_p(v)[1],
                                                  tail=_hinge_p(v)[2], **_season_kw(d)), _check_hinge),
-    Family("exposure", "wagg_exposure_work_bytes", 1, False, "optional", True, False, (Variant("bins9", True, 9, EXP_EDGES),), _mid_list,
+    Family("exposure", "wagg_exposure_reduce", "wagg_exposure_work_bytes", 1, False, "optional", True, False, (Variant("bins9", True, 9, EXP_EDGES),), _mid_list,
            lambda e, X, X2, d, v: e.exposure_reduce(X, X2, d.rb, d.rows, KELVIN, v.p, **_season_kw(d)), _check_exposure),
-    Family("spell", "wagg_spell_work_bytes", 0, False, "optional", False, True,
+    Family("spell", "wagg_spell_reduce", "wagg_spell_work_bytes", 0, False, "optional", False, True,
            (Variant("days-above", False, 3, (2, "days", "above")), Variant("events-below", False, 3, (2, "events", "below"))), _mid_spell,
            lambda e, X, X2, d, v: e.spell_reduce(X, d.rb, d.rows, KELVIN, SPELL_THR, min_length=v.p[0], stat=v.p[1], side=v.p[2],
                                                  **_season_kw(d)), _check_spell),
     # a window above 8 days runs one cell per lane whatever the alignment: [3, 16] meets route 1 like every other
-    Family("rolling", "wagg_rolling_work_bytes", 0, False, "optional", False, True,
+    Family("rolling", "wagg_rolling_reduce", "wagg_rolling_work_bytes", 0, False, "optional", False, True,
            (Variant("ring8", False, 5, ([1, 2, 3, 5, 8], "max", "mean")), Variant("ring16", False, 2, ([3, 16], "min", "sum"))), _mid_roll,
            lambda e, X, X2, d, v: e.rolling_reduce(X, d.rb, d.rows, KELVIN, v.p[0], stat=v.p[1], of=v.p[2], **_season_kw(d)), _check_roll),
+    # no *_work_bytes: work / work_bytes are ignored.  8 planes with max_rows = the longest list; 16 planes (two quantiles a lane in
+    # fp32) with max_rows at the limit, 128 KiB of LDS for a list of 9 or 70 entries
+    Family("quantile", "wagg_quantile_select", None, 0, False, "optional", False, True,
+           (Variant("linear-q8", False, 8, ("linear", Q8, None)), Variant("higher-q16", False, 16, ("higher", Q16, QUANT_ROWS_MAX))),
+           _mid_quantile,
+           lambda e, X, X2, d, v: e.quantile_select(X, d.rb, d.rows, KELVIN, v.p[1], method=v.p[0],
+                                                    max_rows=_quant_max_rows(v, longest_list(d.rb)), **_season_kw(d)), _check_quantile),
 )}
 
 
@@ -377,9 +429,10 @@ def variants_for(fam, route):
 
 def build_args(fam, v, p):
     """(the entry point's argument list, what must outlive the call) from the pointers and sizes `p`: a dict with X, X2, T, n,
-    ldx, rb, rows, P, n_rows, doy, win (None without a season), flags, out, ldo, pstride, status, work, work_bytes, stream"""
+    ldx, rb, rows, P, n_rows, doy, win (None without a season), flags, out, ldo, pstride, status, work, work_bytes, stream, and
+    longest: the entries of the longest list (a host integer, for a middle that bounds it)"""
     vp = lambda a: None if a is None else C.c_void_p(a)
-    mid, keep = fam.middle(v)
+    mid, keep = fam.middle(v, p)
     if fam.four_plane:
         fields = [vp(p["X"]), vp(p["X2"]) if v.two_fields else None]
     else:

@@ -6,11 +6,19 @@ At the kernel layer results are compared EXACTLY -- equal as numbers, NaN exactl
 exact and the interpolation is three separately rounded fp64 operations on both sides.  Only the weighted mean of the public call
 rounds.  The kernel cases use the rolling extremes' small shape -- T = 23 rows, three periods of 9, 8 and 0 entries, a gap at row
 4 -- and the row-list layout tests' one list of 70 entries (rows 0..69 without row 41, row 5 listed twice): more than one load per
-lane in phase 1 (8 | 16 entries a pass) and more than 64 entries."""
+lane in phase 1 (8 | 16 entries a pass) and more than 64 entries.
+
+The kernel's real workload -- a year of 365 or 366 entries, up to its limit of 1024, 128 KiB of LDS -- is the LONG SHAPE of
+tests/quantile_ref.py (T = 1040; ten periods of 255 .. 1024 and 0 entries in one call; tests/test_quantile_host.py checks the shape
+itself) at n = 17 and 33, RL.LONG (512 entries over 64 rows, every row eight times) and a public call over 2004 and 2005.  Their
+references are computed once per (element type, n, method, offset, season) and shared (``_long_want``)."""
+import functools
+
 import numpy as np
 import pytest
 
 from tests import rowlist_layout as RL
+from tests import quantile_ref as QR
 from tests.quantile_ref import quantile_ref
 from tests.rolling_ref import WIN_INVERT, WIN_NULL, in_season
 from tests.test_gpu_packed_totals import _Sparse, segment_plans  # noqa: F401
@@ -348,3 +356,200 @@ def test_public_call(torch_cuda, segment_plans, dtype, kelvin):
                              coords={"time": np.datetime64("2001-01-01") + np.arange(long_T), "lat": c.lat, "lon": c.lon})
     with pytest.raises(ValueError, match="1025 days.*at most 1024"):
         tas_quantile_aggregate(long_ds, q, "popwt", "reg", c.df, period=np.zeros(long_T, dtype=np.int64))
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# lists as long as the workload's: a year, the limit of 1024 entries, every entry of LDS beyond 64 KiB
+# ---------------------------------------------------------------------------------------------------------------------------------
+LONG_NS = (17, 33)                                # fp64: 2 and 3 tiles; fp32: 1 and 2, the last holding one cell
+LONG_RB, LONG_ROWS = QR.long_lists()
+EMPTY = len(QR.LONG_LENGTHS) - 1
+
+
+@functools.lru_cache(maxsize=None)
+def _long_field(n, dtype):
+    X = QR.long_field(n, dtype)
+    X.setflags(write=False)
+    return X
+
+
+@functools.lru_cache(maxsize=None)
+def _long_want(n, dtype, method, off, season):
+    """the restatement on the long shape, once per case (read-only: shared by the tests below)"""
+    sk = QR.long_season(n) if season else (None, None)
+    want = quantile_ref(_long_field(n, dtype), LONG_RB, LONG_ROWS, off, Q16, method, *sk)
+    want.setflags(write=False)
+    return want
+
+
+def _inf_padded(torch, host, pad):
+    """a device tensor with row stride n + pad whose pad columns hold +inf: a lane of the last, partial tile that read past n
+    would raise bit 0 of the status word"""
+    Tn, n = host.shape
+    dev = torch.from_numpy(np.array(host)).cuda()                                 # (a copy: the cached fields are read-only)
+    buf = torch.full((Tn, n + pad), float("inf"), dtype=dev.dtype, device="cuda")
+    buf[:, :n] = dev
+    out = buf[:, :n]
+    assert out.stride(0) == n + pad
+    return out
+
+
+def _season_kw(n, season):
+    if not season:
+        return {}
+    doy, win = QR.long_season(n)
+    return dict(doy=doy, windows=win)
+
+
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+@pytest.mark.parametrize("n", LONG_NS)
+def test_long_lists_equal_the_restatement(torch_cuda, dtype, n):
+    """The long shape in ONE call, 16 levels, all three methods, offset 0 and -273.15, with a season (doy = 1 + t % 366, every
+    kind of window on every kind of column; some cell keeps fewer than 8 of a 1024-entry list) and without, on contiguous rows and
+    on ldx = n + 1 with +inf in the pad column, max_rows = 1024 -- which IS the longest list of this call -- and max_rows=None:
+    every plane equals the restatement exactly, the empty period and the all-NaN columns are NaN in every plane, and the status
+    word stays 0 although rows 1030.. and the pad hold +inf."""
+    from climate_toolbox_amd import engine
+    torch = torch_cuda
+    X = _long_field(n, dtype)
+    P = len(LONG_RB) - 1
+    assert int(np.diff(LONG_RB).max()) == 1024
+    nan_cols = [j for j in range(n) if QR.LONG_KINDS[j % 6] == "e"]
+    for season in (False, True):
+        kw = _season_kw(n, season)
+        for pad in (0, 1):
+            Xd = _inf_padded(torch, X, pad)
+            for method in METHODS:
+                for off in (0.0, -273.15):
+                    what = (n, season, pad, method, off)
+                    got, st = engine.quantile_select(Xd, LONG_RB, LONG_ROWS, off, Q16, method=method, max_rows=1024, **kw)
+                    assert got.shape == (16, P, n) and int(st.item()) == 0, what
+                    _exact(got, _long_want(n, dtype, method, off, season), what)
+                    assert torch.isnan(got[:, EMPTY]).all() and torch.isnan(got[:, :, nan_cols]).all(), what
+            auto, st = engine.quantile_select(Xd, LONG_RB, LONG_ROWS, -273.15, Q16, method="higher", **kw)      # max_rows=None
+            assert int(st.item()) == 0
+            _exact(auto, _long_want(n, dtype, "higher", -273.15, season), (n, season, pad, "max_rows=None"))
+            assert not torch.isnan(auto[:, :EMPTY, 0]).any()                      # (column 0: continuous, open all year)
+
+
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+def test_every_row_eight_times(torch_cuda, dtype):
+    """RL.LONG -- ONE list of 512 entries over 64 rows, every row eight times: every value is an eightfold tie, so v[lo + 1] is
+    v[lo] for seven ranks of eight (the c_le rule) -- at n = 33: the result equals the restatement exactly, and for every level
+    the "lower" and the "higher" plane bracket the "linear" one."""
+    from climate_toolbox_amd import engine
+    torch = torch_cuda
+    Tn, rb, rows = RL.LONG
+    n = 33
+    X = _field(Tn, n, dtype, seed=64)
+    X[5, ::4] = np.nan                                                            # m = 504 in every fourth cell
+    planes = {}
+    for method in METHODS:
+        for pad in (0, 1):
+            got, st = engine.quantile_select(_inf_padded(torch, X, pad), rb, rows, -273.15, Q16, method=method, max_rows=512)
+            assert int(st.item()) == 0
+            _exact(got, quantile_ref(X, rb, rows, -273.15, Q16, method), (method, pad))
+        planes[method] = got.cpu().numpy()
+    assert not np.isnan(planes["linear"]).any()
+    assert (planes["lower"] <= planes["linear"]).all() and (planes["linear"] <= planes["higher"]).all()
+    assert (planes["lower"] < planes["higher"]).any()
+
+
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+def test_confinement_at_the_limit(torch_cuda, dtype):
+    """Device lists of 1024 and 1025 entries (the second: the first plus one repeated row, T unchanged) with checked=True and
+    max_rows=1024: the 1025-entry period is NaN in every plane and the status word is 2, the 1024-entry period -- all 128 KiB of
+    LDS -- is exact, a sentinel behind ``out`` is untouched.  Without checked=True the library's look at the lists rejects the
+    call; max_rows=None with a host list of 1025 entries is the binding's ValueError."""
+    from climate_toolbox_amd import engine
+    torch = torch_cuda
+    n = 33
+    X = _long_field(n, dtype)
+    full = LONG_ROWS[LONG_RB[8]:LONG_RB[9]]
+    assert len(full) == 1024 and len(set(full.tolist())) == 1024
+    rb, rows = np.array([0, 1024, 2049]), np.concatenate([full, full, [full[3]]])
+    Xd = torch.from_numpy(np.array(X)).cuda()
+    drb, drw = _dev_lists(torch, rb, rows)
+    size = 16 * 2 * n
+    big = torch.full((size + RL.GUARD,), 12345.0, dtype=Xd.dtype, device="cuda")
+    out = big[:size].view(16, 2, n)
+    got, st = engine.quantile_select(Xd, drb, drw, 0.0, Q16, max_rows=1024, checked=True, out=out)
+    assert got.data_ptr() == big.data_ptr() and int(st.item()) == 2
+    assert bool((big[size:] == 12345.0).all())
+    want = quantile_ref(X, rb, rows, 0.0, Q16, max_rows=1024)
+    assert np.isnan(want[:, 1]).all() and not np.isnan(want[:, 0, :3]).any() and torch.isnan(got[:, 1]).all()
+    _exact(got, want, "confined at 1025")
+    np.testing.assert_array_equal(want[:, 0], _long_want(n, dtype, "linear", 0.0, False)[:, 8])
+    with pytest.raises(engine.WaggError, match="max_rows"):
+        engine.quantile_select(Xd, drb, drw, 0.0, Q16, max_rows=1024)
+    with pytest.raises(ValueError, match="1025 rows"):
+        engine.quantile_select(Xd, rb, rows, 0.0, Q16)
+
+
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+def test_planes_and_extremes_bit_for_bit_at_length(torch_cuda, dtype):
+    """On the long shape at n = 33, under a season and without: plane k of the 16-level call is the one-level call bit for bit;
+    q = 1 / q = 0 are engine.rolling_reduce's W = 1 maximum / minimum on the same lists."""
+    from climate_toolbox_amd import engine
+    torch = torch_cuda
+    n = 33
+    Xd = _inf_padded(torch, _long_field(n, dtype), 1)
+    for season in (False, True):
+        kw = _season_kw(n, season)
+        for method in METHODS:
+            got, st = engine.quantile_select(Xd, LONG_RB, LONG_ROWS, -273.15, Q16, method=method, max_rows=1024, **kw)
+            assert int(st.item()) == 0
+            for k, qk in enumerate(Q16):
+                one, _ = engine.quantile_select(Xd, LONG_RB, LONG_ROWS, -273.15, [qk], method=method, max_rows=1024, **kw)
+                assert _same(torch, got[k], one[0]), (season, method, k)
+            hi, _ = engine.rolling_reduce(Xd, LONG_RB, LONG_ROWS, -273.15, [1], stat="max", of="mean", **kw)
+            lo, _ = engine.rolling_reduce(Xd, LONG_RB, LONG_ROWS, -273.15, [1], stat="min", of="mean", **kw)
+            assert _same(torch, got[2], hi[0]) and _same(torch, got[1], lo[0]), (season, method)
+        _exact(got, _long_want(n, dtype, "higher", -273.15, season), season)
+
+
+@pytest.mark.parametrize("dtype,kelvin", [(np.float32, True), (np.float64, False)])
+def test_public_call_over_real_years(torch_cuda, segment_plans, dtype, kelvin):
+    """tas_quantile_aggregate(period="year") on the 16 x 32 grid and table of test_public_call with 731 daily steps from
+    2004-01-01 -- a year of 366 and one of 365 entries -- for cells="all" and "referenced", with and without a season: against the
+    restatement per cell aggregated by the fp64 oracle, by test_public_call's rule and rtol (the largest ratio is printed)."""
+    import climate_toolbox_amd as pkg
+    from climate_toolbox_amd import periods
+    from climate_toolbox_amd.transformations import convert_kelvin_to_celsius, tas_quantile_aggregate
+    from oracle import ref_numpy as O
+    torch = torch_cuda
+    c = _Sparse(16, 32, dtype, seed=31)
+    Tn = c.T = 731
+    c.time = np.datetime64("2004-01-01") + np.arange(Tn)
+    rng = np.random.default_rng(2004)
+    flat = (280 + 15 * rng.standard_normal((Tn, c.G))).astype(dtype)
+    flat[::3, int(c.cell[1])] = np.nan
+    flat[:, int(c.cell[2])] = np.nan
+    field = flat.reshape(Tn, c.nlat, c.nlon)
+    q = [0.5, 0.05, 0.95, 0.99, 1.0]
+    off = -273.15 if kelvin else 0.0
+    gd, z1, z2 = _seasons_for(c, seed=Tn)
+    sw = pkg.season_windows(gd)
+    mask = _mask_TG(z1, z2, pkg.day_of_year(c.time))
+    _, rb, rows = periods.period_rows(c.time, "year")
+    assert list(np.diff(rb)) == [366, 365]
+
+    def ds():
+        d = c.dataset(torch, tas=field)
+        return convert_kelvin_to_celsius(d, "tas") if kelvin else d
+
+    worst = _Worst()
+    for season in (None, sw):
+        src = flat if season is None else np.where(mask == 1, flat, np.nan).astype(dtype)
+        for method in ("linear", "higher"):
+            what = (season is not None, method)
+            cells = quantile_ref(src, rb, rows, off, q, method).astype(np.float64)                # (n_q, 2, G)
+            assert np.isnan(cells[:, :, int(c.cell[2])]).all()
+            want = np.stack([O.agg_coded(cells[k], c.cell, c.code, c.w_eff, c.R) for k in range(len(q))])
+            scale = np.stack([O.agg_coded(np.abs(np.nan_to_num(cells[k], nan=0.0)), c.cell, c.code, c.w_eff, c.R) for k in range(len(q))])
+            for cells_kw in ("all", "referenced"):
+                got = tas_quantile_aggregate(ds(), q, "popwt", "reg", c.df, method=method, period="year", season=season,
+                                             cells=cells_kw)["tas-quantile"].values
+                assert got.dtype == dtype and got.shape == (len(q), 2, c.R), what
+                worst.ok(got, want, scale, c.rtol, what + (cells_kw,))
+    print("quantile public call over 2004-2005 %s: largest |got - ref| / (RTOL * A) = %.3g" % (np.dtype(dtype).name, worst.ratio))

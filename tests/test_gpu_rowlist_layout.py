@@ -1,8 +1,9 @@
-"""The sixteen row-list entry points (wagg_{period,season,edd_ladder,bin_days,hinge,exposure,spell,rolling}_reduce_f32 / _f64)
-called through ctypes with what the binding never hands them (run with -m gpu; tests/rowlist_layout.py has the layouts and the
+"""The eighteen row-list entry points (wagg_{period,season,edd_ladder,bin_days,hinge,exposure,spell,rolling}_reduce_f32 / _f64
+and wagg_quantile_select_f32 / _f64) called through ctypes with what the binding never hands them (run with -m gpu; tests/rowlist_layout.py has the layouts and the
 case table): a pitched result (ldo = n + 5, out_pstride = P * ldo + 7) at a 16-byte boundary and one element past it, fields
 that are views into poisoned buffers, field bases one element off a 16-byte boundary (both fields, and tasmax alone), and
-workspaces of the family's own size, of three parts, of one part and none.
+workspaces of the family's own size, of three parts, of one part and none.  The period quantiles have no *_work_bytes and
+promise to ignore the argument: they get the same four workspaces ("full" being three parts) and must leave every byte of them.
 
 Every call is checked four ways: against the family's reference on the unpoisoned logical field (exact where the family's own
 test is exact, else RTOL32 / RTOL64 with that test's scale); bit for bit against the binding's call on a zero-padded view of
@@ -79,7 +80,7 @@ class _Case:
         es = buf.element_size()
         out_ptr = buf.data_ptr() + lay.start * es
         assert buf.data_ptr() % 16 == 0 and out_ptr % 16 == out_off * es
-        full = int(getattr(L, fam.work_bytes)(d.n, d.P, len(d.rows), RL.work_count(fam, v)))
+        full = RL.full_work_bytes(L, fam, v, d.n, d.P, len(d.rows))
         wb = RL.work_bytes_of(work_kind, full, v.planes, d.P, d.n)
         work = _sentinel_filled(torch, wb // 8 + RL.GUARD, torch.float64) if wb else None
         status = torch.zeros(1, dtype=torch.int32, device="cuda")
@@ -87,8 +88,8 @@ class _Case:
             X=self.X.data_ptr(), X2=self.X2.data_ptr(), T=d.T, n=d.n, ldx=self.ldx, rb=c.row_begin.data_ptr(), rows=c.rows.data_ptr(),
             P=c.P, n_rows=c.n_rows, doy=c.doy.data_ptr() if d.seasoned else None, win=c.windows.data_ptr() if d.seasoned else None,
             flags=c.flags, out=out_ptr, ldo=lay.ldo, pstride=lay.pstride, status=status.data_ptr(),
-            work=work.data_ptr() if wb else None, work_bytes=wb, stream=engine._stream_handle(None)))
-        name = "wagg_%s_reduce_%s" % (fam.name, "f32" if d.dtype == RL.F32 else "f64")
+            work=work.data_ptr() if wb else None, work_bytes=wb, stream=engine._stream_handle(None), longest=RL.longest_list(d.rb)))
+        name = RL.symbol(fam, d.dtype)
         _lib.check(getattr(L, name)(*args), name)
         torch.cuda.synchronize()
         del keep
@@ -102,7 +103,9 @@ class _Case:
             len(touched), touched[0], touched[0] - lay.start)
         assert (bits[idx] != RL.SENTINEL[es]).all(), "an element of out[k][p][0:n] was not written"
         got = bits[idx].view(d.dtype)
-        # the workspace: nothing behind work_bytes; nothing at all where the list is summed in one part
+        # the workspace: nothing behind work_bytes; nothing at all where the list is summed in one part -- or where the family
+        # has no *_work_bytes and ignores the argument (fam.splits is False for it)
+        assert fam.work_bytes is not None or (not fam.splits and (work_kind == "none") == (wb == 0))
         lanes = RL.vec(d.dtype) if RL.is_wide(self.route, d.dtype, d.n, v.two_fields) else 1
         split = RL.expected_split(work_kind, full, v.planes, d.P, d.n, len(d.rows), lanes) if fam.splits else 1
         if wb:

@@ -26,12 +26,14 @@ probe B; it is the one call that may wait for the current stream.
 
 Shapes are the suite's smallest: the row lists of tests/test_gpu_spell.py (T = 23; 9, 8 and 0 entries) at n = 257 on the aligned
 pitch and on pad + 1; ``_Sparse(16, 32)`` of tests/test_gpu_packed_totals.py; the 127 x 15 table of
-tests/test_gpu_dense_forms_small.py.  tests/spell_ref.py and tests/rolling_ref.py anchor the default-stream reference itself once
-each.  tests/test_stream_order_host.py checks, without a GPU, that PROBES and EXEMPT cover every ``stream=`` entry point."""
+tests/test_gpu_dense_forms_small.py.  tests/spell_ref.py, tests/rolling_ref.py and tests/quantile_ref.py anchor the default-stream
+reference itself once each.  ``quantile_select`` is called with an explicit ``max_rows`` (the longest list, 9): ``max_rows=None`` on
+device lists blocks on torch's current stream, which its docstring says.  tests/test_stream_order_host.py checks, without a GPU, that PROBES and EXEMPT cover every ``stream=`` entry point."""
 import numpy as np
 import pytest
 
 from tests import stream_gate as gate
+from tests.quantile_ref import quantile_ref
 from tests.rolling_ref import rolling_ref
 from tests.spell_ref import spell_ref
 from tests.test_gpu_dense_forms_small import EDD_THRESHOLDS, OFFSET, build_plan, edd_fields, kelvin_field
@@ -206,6 +208,7 @@ DOY = np.arange(100, 100 + T)
 WIN = np.where(np.arange(N) % 3 == 0, OPEN, 101 | 112 << 10).astype(np.int32)      # cell 3: open all year; rows 1 .. 12 elsewhere
 THR = [5.0, 2.0, 8.75]
 EDGES = [-np.inf, 2.0, 5.0, 8.0, np.inf]
+QLEV = [0.5, 0.0, 1.0, 0.05, 0.95, 1.0 / 3.0]
 
 # the row-list calls: name -> (two fields?, call(engine, X, X2, rb, rows, season kwargs, stream))
 ROWLIST = {
@@ -218,6 +221,7 @@ ROWLIST = {
     "hinge_reduce": (False, lambda e, X, X2, rb, rw, kw, s: e.hinge_reduce(X, rb, rw, 0.0, [2.0, 5.0, 8.0], power=2, checked=True, stream=s, **kw)),
     "spell_reduce": (False, lambda e, X, X2, rb, rw, kw, s: e.spell_reduce(X, rb, rw, 0.0, THR, min_length=2, stat="days", checked=True, stream=s, **kw)),
     "rolling_reduce": (False, lambda e, X, X2, rb, rw, kw, s: e.rolling_reduce(X, rb, rw, 0.0, [1, 3], stat="max", of="mean", checked=True, stream=s, **kw)),
+    "quantile_select": (False, lambda e, X, X2, rb, rw, kw, s: e.quantile_select(X, rb, rw, 0.0, QLEV, max_rows=9, checked=True, stream=s, **kw)),
 }
 ALWAYS_SEASON = ("season_reduce",)
 NEVER_SEASON = ("period_reduce",)
@@ -247,6 +251,9 @@ def _rowlist_cases(name):
                 if name == "rolling_reduce" and season and pad == _pads(N, dtype)[0]:
                     def check(ref):
                         assert np.array_equal(ref[0], rolling_ref(lo, RB, ROWS, 0.0, [1, 3], "max", "mean", DOY, WIN), equal_nan=True) and ref[1].tolist() == [0]
+                if name == "quantile_select" and season and pad == _pads(N, dtype)[0]:
+                    def check(ref):
+                        assert np.array_equal(ref[0], quantile_ref(lo, RB, ROWS, 0.0, QLEV, "linear", DOY, WIN), equal_nan=True) and ref[1].tolist() == [0]
                 add("pad %d, %s" % (pad, "season" if season else "no season"), lo, hi, pad, season, (rb, rw), check=check)
         # the status word: one counted +inf, so the reference reads 1 -- a zero-fill that lands late reads 0
         ilo, ihi = _fields(dtype, inf=True)

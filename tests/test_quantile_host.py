@@ -1,7 +1,8 @@
 """Period quantiles, the part that needs no GPU: the exports of wagg_quantile_select_* (include/wagg.h) and their constants, every
 bad-argument code with its message (all decided before any device call), the naming rule that keeps the two symbols out of the
-row-list layout table, the binding's and the public call's argument checks that precede any device work, and the NumPy
-restatement tests/quantile_ref.py against np.quantile / np.sort."""
+wagg_*_reduce_* pattern (the row-list layout table names them by their own symbol), the binding's and the public call's argument
+checks that precede any device work, the NumPy restatement tests/quantile_ref.py against np.quantile / np.sort, and the long shape
+of that module, which tests/test_gpu_quantile.py runs."""
 import ctypes as C
 import inspect
 import os
@@ -10,8 +11,9 @@ import re
 import numpy as np
 import pytest
 
+from tests import quantile_ref as QR
 from tests.quantile_ref import quantile_ref
-from tests.rolling_ref import WIN_NULL
+from tests.rolling_ref import WIN_INVERT, WIN_NULL
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ("wagg_quantile_select_f32", "wagg_quantile_select_f64")
@@ -36,8 +38,8 @@ def test_exports_version_and_constants():
 
 
 def test_names_stay_out_of_the_reduce_pattern_and_there_is_no_workspace_export():
-    """No export of this family matches wagg_(\\w+)_reduce_(f32|f64) (tests/rowlist_layout.py lists those exhaustively), and there
-    is no wagg_quantile*_work_bytes: a list is never split."""
+    """No export of this family matches wagg_(\\w+)_reduce_(f32|f64) (tests/rowlist_layout.py has it under its own symbol,
+    ``entry="wagg_quantile_select"``, with no ``work_bytes``), and there is no wagg_quantile*_work_bytes: a list is never split."""
     from climate_toolbox_amd import _lib
     L = _lib.load()
     ours = [name for name in _lib.EXPORTS if "quantile" in name]
@@ -50,13 +52,21 @@ def test_names_stay_out_of_the_reduce_pattern_and_there_is_no_workspace_export()
         assert not hasattr(L, name), name
 
 
-def test_binding_has_no_stream_keyword():
-    """engine.quantile_select runs on the current stream: the keyword comes together with its stream-order probe."""
+def test_binding_takes_stream_last_and_says_what_still_blocks():
+    """engine.quantile_select has ``stream=None`` behind the parameters it had, and a probe in tests/test_gpu_stream_order.py that
+    passes max_rows; its docstring still says that max_rows=None on device lists blocks, and now on which stream."""
     from climate_toolbox_amd import engine
+    from tests import test_gpu_stream_order as probes
     params = inspect.signature(engine.quantile_select).parameters
-    assert "stream" not in params
-    assert list(params) == ["X", "row_begin", "rows", "offset", "q", "method", "max_rows", "doy", "windows", "checked", "out", "status"]
-    assert "stream" in engine.quantile_select.__doc__ and "blocks" in engine.quantile_select.__doc__.lower()
+    assert list(params) == ["X", "row_begin", "rows", "offset", "q", "method", "max_rows", "doy", "windows", "checked", "out", "status",
+                            "stream"]
+    assert params["stream"].default is None
+    doc = " ".join(engine.quantile_select.__doc__.split())
+    assert "NO ``stream=``" not in doc and "``stream=``" in doc
+    assert "``row_begin.diff().max()``" in doc and "blocks" in doc and "CURRENT stream" in doc and "passes ``max_rows``" in doc
+    assert "quantile_select" in probes.ROWLIST and "quantile_select" in probes.PROBES and "quantile_select" not in probes.EXEMPT
+    src = inspect.getsource(probes)
+    assert re.search(r"e\.quantile_select\([^\n]*max_rows=9, checked=True, stream=s", src)
 
 
 def test_abi_bad_arguments_return_codes():
@@ -203,3 +213,60 @@ def test_ref_by_hand():
     assert np.isnan(quantile_ref(X, rb, rows, 0.0, [0.5], max_rows=5)).all() and quantile_ref(X, rb, rows, 0.0, [0.5], max_rows=6)[0, 0, 0] == 3.0
     one = np.array([[7.0]])
     assert quantile_ref(one, [0, 1], [0], 0.0, [0, 0.37, 1])[:, 0, 0].tolist() == [7.0, 7.0, 7.0]      # m = 1: h = 0 for every level
+
+
+def test_the_long_shape():
+    """tests/quantile_ref.py's long shape is what tests/test_gpu_quantile.py says it gives the kernel: T = 1040; periods of 255,
+    256, 257, 365, 366, 512, 513, 1023, 1024 and 0 entries; every list distinct rows of 0..1029 in no ascending order, but for the
+    one that names one row twice; rows 1030.. in no list (and +inf); the six kinds of column at n = 17 and 33; the season that
+    leaves a cell of a 1024-entry period fewer than 8 valid entries."""
+    rb, rows = QR.long_lists()
+    lens = np.diff(rb)
+    assert QR.LONG_T == 1040 and list(lens) == [255, 256, 257, 365, 366, 512, 513, 1023, 1024, 0] == list(QR.LONG_LENGTHS)
+    assert rb[0] == 0 and rb[-1] == len(rows) and rows.min() >= 0 and rows.max() < QR.LONG_LISTED == 1030
+    assert lens.max() == QR.QUANT_ROWS_MAX and any(L % 8 != 0 and L % 16 != 0 for L in lens) and (lens > 512).sum() >= 3
+    twice = []
+    for p, L in enumerate(lens):
+        lst = rows[rb[p]:rb[p + 1]]
+        if L:
+            assert (np.diff(lst) < 0).sum() > L // 4, p                           # not ascending: entry index != row index
+            assert not np.array_equal(lst, np.arange(L)), p
+        if len(set(lst.tolist())) != L:
+            assert len(set(lst.tolist())) == L - 1
+            twice.append(p)
+    assert twice == [QR.LONG_TWICE]
+    rb2, rows2 = QR.long_lists()
+    assert np.array_equal(rb, rb2) and np.array_equal(rows, rows2)                # seeded
+    for dtype in (np.float32, np.float64):
+        for n in (17, 33):
+            X = QR.long_field(n, dtype)
+            assert X.shape == (1040, n) and X.dtype == dtype and np.isposinf(X[1030:]).all() and not np.isinf(X[:1030]).any()
+            m = QR.valid_counts(X, rb, rows)
+            kinds = {k: [j for j in range(n) if QR.LONG_KINDS[j % 6] == k] for k in QR.LONG_KINDS}
+            assert all(kinds[k] for k in kinds)
+            full = lens[:, None]
+            for k in "abcf":
+                assert (m[:, kinds[k]] == full).all(), k
+            assert (m[:, kinds["e"]] == 0).all()
+            d = m[:-1, kinds["d"]]
+            assert (d > 0).all() and (d < full[:-1]).all()                        # strictly between 0 and L, every non-empty period
+            assert (m[:-1, kinds["d"]] != m[:-1, [j - 1 for j in kinds["d"]]]).all()      # and not the neighbouring cell's m
+            a, b, c, f = (X[:1030, kinds[k][0]] for k in "abcf")
+            assert (a < 0).any() and (a > 0).any() and len(set(a.tolist())) > 1000
+            assert set(b.tolist()) == {-0.5, -0.25, 0.0, 0.25, 0.5} and len(set(c.tolist())) == 1
+            tiny = np.finfo(dtype).tiny
+            assert np.signbit(f[f == 0]).any() and not np.signbit(f[f == 0]).all() and ((f != 0) & (np.abs(f) < tiny)).any()
+            for p in (7, 8):                                                      # 1023 and 1024 entries: ties at the median
+                col = np.sort(X[rows[rb[p]:rb[p + 1]], kinds["b"][0]])
+                assert (col == col[(len(col) - 1) // 2]).sum() >= 100, p
+            doy, win = QR.long_season(n)
+            assert doy.min() == 1 and doy.max() == 366 and np.array_equal(doy, 1 + np.arange(1040) % 366) and win.shape == (n,)
+            assert (win == (0 | 1023 << 10)).any() and (win & WIN_NULL).any() and (win & WIN_INVERT).any()
+            ms = QR.valid_counts(X, rb, rows, doy, win)
+            assert ((ms[8] > 0) & (ms[8] < 8)).any() and (ms[8] == 1024).any() and (ms[8] == 0).any()
+            assert (ms <= m).all() and len(set(ms[8].tolist())) >= 6
+    # the restatement on it: the median of the all-equal column, and of the tied one, by hand
+    X = QR.long_field(17, np.float64)
+    want = quantile_ref(X, rb, rows, 0.0, [0.5], "linear")
+    assert want.shape == (1, 10, 17) and np.isnan(want[0, 9]).all() and np.isnan(want[0, :, 4]).all()
+    assert (want[0, :9, 2] == 287.65).all() and set(want[0, :9, 1].tolist()) <= {-0.5, -0.25, 0.0, 0.25, 0.5}

@@ -13,20 +13,42 @@ HEADER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))
 
 
 def test_the_case_table_names_every_row_list_entry_point():
-    """A family is an export wagg_<name>_reduce_f32 with its _f64 sibling: each has a row, each row has both, and its
-    *_work_bytes is an export too.  A ninth family cannot arrive without a row."""
+    """A family is an export wagg_<name>_reduce_f32 -- or wagg_quantile_select_f32 -- with its _f64 sibling: each has a row, each
+    row has both, and its *_work_bytes is an export too, but for the period quantiles, which have none (fam.work_bytes is None:
+    no such export exists, and the family never splits).  A tenth family cannot arrive without a row."""
     from climate_toolbox_amd import _lib
     found = {}
     for e in _lib.EXPORTS:
-        m = re.fullmatch(r"wagg_(\w+)_reduce_(f32|f64)", e)
+        m = re.fullmatch(r"(wagg_\w+_(?:reduce|select))_(f32|f64)", e)
         if m:
             found.setdefault(m.group(1), set()).add(m.group(2))
     assert found and all(v == {"f32", "f64"} for v in found.values()), found
-    assert sorted(found) == sorted(RL.FAMILIES), "tests/rowlist_layout.py FAMILIES and the declared wagg_*_reduce_* differ"
-    assert len(RL.FAMILIES) == 8
+    by_entry = {fam.entry: fam for fam in RL.FAMILIES.values()}
+    assert len(by_entry) == len(RL.FAMILIES) == 9
+    assert sorted(found) == sorted(by_entry), "tests/rowlist_layout.py FAMILIES and the declared wagg_*_reduce_* / _select_* differ"
     for name, fam in RL.FAMILIES.items():
-        assert fam.name == name and fam.work_bytes in _lib.EXPORTS and fam.variants, name
+        assert fam.name == name and fam.variants, name
+        assert fam.entry == ("wagg_quantile_select" if name == "quantile" else "wagg_%s_reduce" % name), name
+        assert [RL.symbol(fam, d) for d in RL.DTYPES] == [fam.entry + "_f32", fam.entry + "_f64"]
+        assert all(RL.symbol(fam, d) in _lib.EXPORTS and hasattr(_lib.load(), RL.symbol(fam, d)) for d in RL.DTYPES), name
+        if fam.work_bytes is None:
+            assert name == "quantile" and not fam.splits and fam.counting and fam.count_extra == 0
+            assert not any(e.startswith("wagg_quantile") and e.endswith("_work_bytes") for e in _lib.EXPORTS)
+        else:
+            assert fam.work_bytes in _lib.EXPORTS, name
         assert len({v.id for v in fam.variants}) == len(fam.variants)
+    assert [n for n, f in RL.FAMILIES.items() if f.work_bytes is None] == ["quantile"]
+    # the quantiles: 8 planes with max_rows = the longest list, 16 planes (the most: two a lane in fp32) with the limit itself
+    qv = {v.id: v for v in RL.FAMILIES["quantile"].variants}
+    assert sorted(qv) == ["higher-q16", "linear-q8"] and qv["linear-q8"].planes == len(RL.Q8) == 8
+    assert qv["higher-q16"].planes == len(RL.Q16) == _lib.QUANT_MAX == 16 and RL.QUANT_ROWS_MAX == _lib.QUANT_ROWS_MAX
+    assert qv["linear-q8"].p == ("linear", RL.Q8, None) and qv["higher-q16"].p == ("higher", RL.Q16, 1024)
+    for lists, longest in (("small", 9), ("split", 70), ("long", 512)):
+        assert RL.longest_list(RL.LISTS[lists][1]) == longest
+        mid, keep = RL.FAMILIES["quantile"].middle(qv["linear-q8"], {"longest": longest})
+        assert mid[1:] == [8, _lib.QUANT_LINEAR, longest] and list(keep[0]) == RL.Q8
+        mid, keep = RL.FAMILIES["quantile"].middle(qv["higher-q16"], {"longest": longest})
+        assert mid[1:] == [16, _lib.QUANT_HIGHER, 1024] and list(keep[0]) == RL.Q16
     # two groups of the family's *_GROUP for the grouped summing / counting families, 3 powers and 2 thresholds for the others
     groups = {"edd_ladder": _lib.EDD_LADDER_GROUP, "bin_days": _lib.BIN_GROUP, "hinge": _lib.HINGE_GROUP, "exposure": _lib.EXPOSURE_GROUP}
     for name, g in groups.items():
@@ -39,7 +61,8 @@ def test_the_case_table_names_every_row_list_entry_point():
 def test_the_split_the_gpu_cases_count_on():
     """T = 70 entries in ONE period: n_rows / P / 8 caps the split at 8 on every route, so every family that splits asks for
     8 parts of 8 * planes * P * n bytes (wagg_period_reduce_work_bytes among them); the small lists (17 entries in 3 periods)
-    never split; the spells and the rolling extremes ask for nothing."""
+    never split; the spells and the rolling extremes ask for nothing; the period quantiles have no *_work_bytes to ask: their
+    "full" workspace is three parts, non-zero, and no size makes them split."""
     from climate_toolbox_amd import _lib
     L = _lib.load()
     T, rb, rows = RL.SPLIT
@@ -51,7 +74,11 @@ def test_the_split_the_gpu_cases_count_on():
             assert L.wagg_period_reduce_work_bytes(n, 1, 70, planes) == 8 * RL.SPLIT_PARTS * planes * 1 * n
         for fam in RL.FAMILIES.values():
             for v in fam.variants:
-                full = getattr(L, fam.work_bytes)(n, 1, 70, RL.work_count(fam, v))
+                full = RL.full_work_bytes(L, fam, v, n, 1, 70)
+                if fam.work_bytes is None:
+                    assert full == 3 * RL.per_part(v.planes, 1, n) > 0 and RL.full_work_bytes(L, fam, v, n, 3, 17) == 3 * RL.per_part(v.planes, 3, n)
+                    assert not fam.splits and [RL.work_bytes_of(k, full, v.planes, 1, n) > 0 for k in RL.WORKS] == [True, True, True, False]
+                    continue
                 assert full == (RL.SPLIT_PARTS * RL.per_part(v.planes, 1, n) if fam.splits else 0), (fam.name, v.id, n)
                 assert getattr(L, fam.work_bytes)(n, 3, 17, RL.work_count(fam, v)) == 0
                 if fam.splits:
@@ -165,7 +192,7 @@ def test_the_header_asks_element_alignment_of_out_dev():
     text = open(HEADER).read()
     a, b = text.index("---- period totals"), text.index("---- packed rows")
     section = text[a:b]
-    assert all(("wagg_%s_reduce_f32" % name) in section for name in RL.FAMILIES)
+    assert all(RL.symbol(fam, RL.F32) in section for fam in RL.FAMILIES.values())
     for line in section.splitlines():
         if "out_dev" in line:
             assert "align" not in line.lower(), line

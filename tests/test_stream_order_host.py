@@ -28,7 +28,7 @@ def _stream_entry_points():
 
 def test_every_stream_entry_point_is_probed_or_exempt():
     found = _stream_entry_points()
-    assert len(found) >= 29 and "period_reduce" in found and "SparsePlan.apply" in found and "DensePlan.saw_inf" in found, sorted(found)
+    assert len(found) >= 30 and "period_reduce" in found and "quantile_select" in found and "SparsePlan.apply" in found and "DensePlan.saw_inf" in found, sorted(found)
     missing = sorted(set(found) - set(probes.PROBES) - set(probes.EXEMPT))
     assert not missing, "engine entry points with stream= that tests/test_gpu_stream_order.py neither probes nor exempts: %s" % missing
     gone = sorted((set(probes.PROBES) | set(probes.EXEMPT)) - set(found))
