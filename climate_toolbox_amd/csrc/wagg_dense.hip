@@ -539,7 +539,7 @@ static void dense_build_image(wagg_dense *d, hipStream_t st) {
     if (big.form != DENSE_FORM_SPLIT || d->n_tiles <= 0) return;
     const char *off = getenv("WAGG_DENSE_NO_W_IMAGE");
     if (off && off[0] && off[0] != '0') return;
-    const size_t workspace = (big.xp_words + big.slabs_words + big.xmax_words) * sizeof(float);
+    const size_t workspace = (big.xp_words + big.slabs_words + big.xmax_words * (1 + SPLIT_NS)) * sizeof(float);
     const size_t bytes = (size_t)d->w_slots() * 16;
     size_t free_b = 0, total_b = 0;
     if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); return; }
@@ -889,6 +889,7 @@ static int dense_launch_split(wagg_dense *d, const float *X_dev, int64_t Tn, int
     if (d->slabs.n < r.slabs_words) WAGG_HIP(d->slabs.alloc(r.slabs_words));
     if (d->xp.n < r.xp_words) WAGG_HIP(d->xp.alloc(r.xp_words));
     if (d->xmax.n < r.xmax_words) WAGG_HIP(d->xmax.alloc(r.xmax_words));
+    if (d->xmax_part.n < r.xmax_words * SPLIT_NS) WAGG_HIP(d->xmax_part.alloc(r.xmax_words * SPLIT_NS));
     bool img = r.image;
 #ifdef WAGG_DIAG      // WAGG_SPLIT_IMG=0: split in registers although the plan holds an image (A/B in one process)
     if (const char *e = getenv("WAGG_SPLIT_IMG")) img = img && e[0] != '0';
@@ -909,12 +910,17 @@ static int dense_launch_split(wagg_dense *d, const float *X_dev, int64_t Tn, int
 #endif
     const size_t shmem = 3 * (size_t)d_xt_bytes(MT);          // the split kernel's ring of three X tiles (W: registers)
     WAGG_HIP(allow_dynamic_lds(kern, shmem));
-    unsigned *xmax = reinterpret_cast<unsigned *>(d->xmax.p);
-    WAGG_HIP(hipMemsetAsync(xmax, 0, sizeof(unsigned) * (size_t)Tn, st));
-    const int64_t gx = (d->G + 4095) / 4096 < 64 ? (d->G + 4095) / 4096 : 64;
-    hipLaunchKernelGGL(dense_rowmax_kernel, dim3((unsigned)gx, (unsigned)Tn), dim3(256), 0, st, X_dev, ldx, d->G, xf, xmax);
-    hipLaunchKernelGGL(dense_pack_x_split_kernel, dim3(256 * 16), dim3(256), 0, st, X_dev, Tn, ldx, d->G, n_kt, bm, r.x_slots, aligned,
-                       (const unsigned *)xmax, reinterpret_cast<f16x8 *>(d->xp.p), xf, d->inf_dev);
+    // row maxima: SPLIT_NS partial words a row (every one written by the first kernel, none cleared), folded by the pack
+    // kernel, which also leaves the final xmax[t] for the reduce.  The pack grid: (16-row group, row block, k-tile share) with
+    // about 32 workgroups a CU in all, each walking every n_cb-th group of four k tiles
+    unsigned *xmax = reinterpret_cast<unsigned *>(d->xmax.p), *xpart = reinterpret_cast<unsigned *>(d->xmax_part.p);
+    hipLaunchKernelGGL(dense_rowmax_kernel, dim3(SPLIT_NS, (unsigned)Tn), dim3(SPLIT_PREP_THREADS), 0, st, X_dev, ldx, d->G, aligned, xf,
+                       xpart);
+    const int kt_groups = (n_kt + 3) / 4, cb_want = (d->ncu * 32 + MT * n_mb - 1) / (MT * n_mb);
+    const int n_cb = cb_want < kt_groups ? cb_want : kt_groups;
+    hipLaunchKernelGGL(dense_pack_x_split_kernel, dim3((unsigned)MT, (unsigned)n_mb, (unsigned)n_cb), dim3(SPLIT_PREP_THREADS), 0, st,
+                       X_dev, Tn, ldx, d->G, n_kt, aligned, (const unsigned *)xpart, xmax, reinterpret_cast<f16x8 *>(d->xp.p), xf,
+                       d->inf_dev);
     WAGG_HIP(hipGetLastError());
     const f16x8 *xp = reinterpret_cast<const f16x8 *>(d->xp.p);
     const float *wp = img ? d->wimg.p : d->W.p, *wmax = d->wmax.p;
@@ -1228,12 +1234,20 @@ extern "C" int wagg_dense_destroy(wagg_dense *d) {
 }
 
 // Diagnostic entry (include/wagg.h): the stored tiles as they lie on the device; tests/test_gpu_split_image.py pins the image's
-// layout with it.
+// layout with it.  image = 2 / 3: the first `bytes` of the split form's workspaces as the last apply left them -- the packed
+// f16 tiles of X / the row maxima (tests/test_gpu_split_prep.py); the caller has waited for that apply.
 extern "C" int wagg_dense_read_w(const wagg_dense *d, int image, void *host, uint64_t bytes) {
     using namespace wagg;
     clear_error();
     WAGG_REQUIRE(d && host, "NULL argument");
     WAGG_REQUIRE(!d->spmm, "an entry-list plan holds no W matrix");
+    if (image == 2 || image == 3) {
+        const DevBuf<float> &ws = image == 2 ? d->xp : d->xmax;
+        WAGG_REQUIRE(ws.p != nullptr && bytes <= (uint64_t)ws.n * sizeof(float), "the workspace holds %llu bytes, the buffer %llu",
+                     (unsigned long long)(ws.n * sizeof(float)), (unsigned long long)bytes);
+        WAGG_HIP(hipMemcpy(host, ws.p, bytes, hipMemcpyDeviceToHost));
+        return WAGG_OK;
+    }
     const float *src = image ? d->wimg.p : d->W.p;
     WAGG_REQUIRE(src != nullptr, "the plan holds no image of W");
     WAGG_REQUIRE(bytes == (uint64_t)d->w_slots() * 16, "W is %lld bytes, the buffer %llu", (long long)d->w_slots() * 16,

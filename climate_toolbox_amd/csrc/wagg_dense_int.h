@@ -75,8 +75,9 @@ struct wagg_dense {
     wagg::DevBuf<float> W, den32, slabs, xp;     // W and xp in packed tile order (sized in 4-byte units for both types)
     wagg::DevBuf<double> den64;
     // full-form fp32 plans: max |w| of every column (n_nt * 256, zero-padded), from which the split form takes its
-    // power-of-two column scales (wagg_dense_split.inc); xmax: the row maxima of the apply in flight (workspace)
-    wagg::DevBuf<float> wmax, xmax;
+    // power-of-two column scales (wagg_dense_split.inc); xmax: the row maxima of the apply in flight (workspace), xmax_part:
+    // the per-strip maxima they are folded from (64 words a row)
+    wagg::DevBuf<float> wmax, xmax, xmax_part;
     // ... and, when the device had room for it at plan time, the f16 high / low parts of the scaled W in the packed tile
     // layout (W's size again): what the split kernel would make of every tile on every apply (dense_split_image_kernel)
     wagg::DevBuf<float> wimg;

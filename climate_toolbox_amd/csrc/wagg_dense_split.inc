@@ -337,55 +337,116 @@ __global__ __launch_bounds__(D_THREADS) void dense_split_image_kernel(const floa
     }
 }
 
-// row maxima of the transformed X (NaN counts as 0, +-inf is left out): rowmax[t] (zeroed by the caller) as float bits,
-// combined with an unsigned atomic max (non-negative floats order like their bits: the same result in any order)
-__global__ void dense_rowmax_kernel(const float *__restrict__ X, int64_t ldx, int64_t G, PackXfT<float> xf,
-                                    unsigned *__restrict__ rowmax) {
+// Row maxima of the transformed X (NaN counts as 0, +-inf is left out), in two steps without a buffer to clear: a row is cut
+// into SPLIT_NS strips of whole 4-cell quads (the last one takes the G % 4 cells behind them), workgroup (j, t) writes the
+// maximum of strip j of row t -- 0 for a strip without cells -- as float bits into part[t][j], and the pack kernel below
+// takes the maximum of a row's SPLIT_NS words.  Every word is written on every apply, and the maximum of non-negative floats
+// is the same in any order.  aligned: X (and the EDD second field) and ldx are multiples of 16 bytes, the quads are loaded whole.
+constexpr int SPLIT_NS = 64;
+constexpr int SPLIT_PREP_THREADS = 256;
+__global__ __launch_bounds__(SPLIT_PREP_THREADS) void dense_rowmax_kernel(const float *__restrict__ X, int64_t ldx, int64_t G, int aligned,
+                                                                          PackXfT<float> xf, unsigned *__restrict__ part) {
     const int64_t t = blockIdx.y;
     const float *src = X + t * ldx;
     const float *src2 = xf.mode == XF_EDD ? xf.X2 + t * ldx : src;
+    const bool edd = xf.mode == XF_EDD;
+    const int64_t nq = (G + 3) >> 2, per = (nq + SPLIT_NS - 1) / SPLIT_NS;
+    const int64_t q0 = (int64_t)blockIdx.x * per < nq ? (int64_t)blockIdx.x * per : nq;
+    const int64_t q1 = q0 + per < nq ? q0 + per : nq;
     bool inf_seen = false;
     float m = 0.0f;
-    for (int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; g < G; g += (int64_t)gridDim.x * blockDim.x) {
-        const float y = pack_xf<float>(xf, src[g], src2[g], inf_seen);
-        const float a = fabsf(y);
+    auto take = [&](float x, float x2) {
+        const float a = fabsf(pack_xf<float>(xf, x, x2, inf_seen));
         m = a <= FLT_MAX && a > m ? a : m;
+    };
+    if (aligned) {
+        const int64_t qf = q1 < (G >> 2) ? q1 : (G >> 2);          // the quads that lie inside the row as a whole
+        const f32x4 *s4 = reinterpret_cast<const f32x4 *>(src), *s42 = reinterpret_cast<const f32x4 *>(src2);
+        int64_t q = q0 + threadIdx.x;
+        for (; q + 3 * SPLIT_PREP_THREADS < qf; q += 4 * SPLIT_PREP_THREADS) {   // four loads (EDD: eight) in flight
+            f32x4 a[4], b[4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) a[i] = s4[q + i * SPLIT_PREP_THREADS];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) b[i] = edd ? s42[q + i * SPLIT_PREP_THREADS] : a[i];
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+#pragma unroll
+                for (int c = 0; c < 4; ++c) take(a[i][c], b[i][c]);
+        }
+        for (; q < qf; q += SPLIT_PREP_THREADS) {
+            const f32x4 a = s4[q];
+            const f32x4 b = edd ? s42[q] : a;
+#pragma unroll
+            for (int c = 0; c < 4; ++c) take(a[c], b[c]);
+        }
+        if (q0 <= qf && qf < q1 && threadIdx.x == 0)                // this strip ends in the ragged quad: the last G % 4 cells
+            for (int64_t g = 4 * qf; g < G; ++g) take(src[g], src2[g]);
+    } else {
+        const int64_t g1 = 4 * q1 < G ? 4 * q1 : G;
+        for (int64_t g = 4 * q0 + threadIdx.x; g < g1; g += SPLIT_PREP_THREADS) take(src[g], src2[g]);
     }
 #pragma unroll
     for (int o = 32; o >= 1; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
-    __shared__ float wm[16];
+    __shared__ float wm[SPLIT_PREP_THREADS / 64];
     if ((threadIdx.x & 63) == 0) wm[threadIdx.x >> 6] = m;
     __syncthreads();
     if (threadIdx.x == 0) {
-        for (int w = 1; w < (int)(blockDim.x >> 6); ++w) m = fmaxf(m, wm[w]);
-        if (m > 0.0f) atomicMax(rowmax + t, __float_as_uint(m));
+        for (int w = 1; w < SPLIT_PREP_THREADS / 64; ++w) m = fmaxf(m, wm[w]);
+        part[t * SPLIT_NS + blockIdx.x] = __float_as_uint(m);
     }
 }
 
 // X (T x G) -> packed split tiles: the slot layout of dense_pack_x_kernel<float>, but piece p < 4 of a row holds the f16
 // high parts and piece p + 4 the low parts of k = 32 kt + {4 p + c, 16 + 4 p + c}, c = 0..3, scaled by 2^ex[t].  Same
 // transforms, NaN -> 0 (S6), zero rows >= T and cells >= G; +-inf: high part +-inf, low part 0, and the caller is told.
-__global__ void dense_pack_x_split_kernel(const float *__restrict__ X, int64_t Tn, int64_t ldx, int64_t G, int n_kt, int bm,
-                                          int64_t n_slots, int aligned, const unsigned *__restrict__ rowmax,
-                                          f16x8 *__restrict__ Xp, PackXfT<float> xf, int *__restrict__ inf_flag) {
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    const int tile_slots = bm * 8;
-    bool inf_seen = false;
-    for (int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; s < n_slots; s += stride) {
-        const int slot = (int)(s % tile_slots);
-        const int64_t tk = s / tile_slots;
-        const int kt = (int)(tk % n_kt);
-        const int64_t mb = tk / n_kt;
-        const int row = slot >> 3, p = (slot & 7) ^ ((row >> 1) & 7);
-        const bool low = p >= 4;
-        const int64_t t = mb * bm + row, k0 = (int64_t)kt * 32 + 4 * (p & 3);
-        f16x8 o;
-#pragma unroll
-        for (int c = 0; c < 8; ++c) o[c] = (_Float16)0.0f;
+//
+// Workgroup (m, mb, cb) of a grid (MT, n_mb, n_cb) keeps the sixteen rows of row block mb's 16-row group m and walks the k tiles
+// 4 (cb + i n_cb) + wave, i = 0, 1, ...: no division anywhere.  It first takes the rows' maxima from the SPLIT_NS partial words
+// of dense_rowmax_kernel (sixteen lanes a row, one 16-byte load each) -- and, as the workgroup that owns the rows' first slots
+// (cb = 0), writes them to rowmax[t] for the reduce kernel.  Lane (lr, p) of a wave then owns the pair of pieces p and p + 4 of
+// row 16 m + lr: it loads the row's cells 4 p + c and 16 + 4 p + c once, transforms and scales each value once and stores the
+// high parts at slot p ^ swz and the low parts at slot (p + 4) ^ swz = (p ^ swz) ^ 4 of the row, swz = (row >> 1) & 7 (the
+// swizzle of the tile image).  A wave reads 128 bytes of each of sixteen rows and its two stores cover the sixteen 128-byte tile
+// rows whole: 2 KiB of the image, end to end.
+__global__ __launch_bounds__(SPLIT_PREP_THREADS) void dense_pack_x_split_kernel(
+    const float *__restrict__ X, int64_t Tn, int64_t ldx, int64_t G, int n_kt, int aligned, const unsigned *__restrict__ part,
+    unsigned *__restrict__ rowmax, f16x8 *__restrict__ Xp, PackXfT<float> xf, int *__restrict__ inf_flag) {
+    const int m = blockIdx.x, cb = blockIdx.z, n_cb = gridDim.z, bm = (int)gridDim.x * 16;
+    const int64_t mb = blockIdx.y;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    __shared__ int ex_s[16];
+    {
+        const int r = threadIdx.x >> 4, q = threadIdx.x & 15;
+        const int64_t t = mb * bm + m * 16 + r;
+        unsigned mx = 0;                                           // (non-negative floats order like their bits)
         if (t < Tn) {
-            const int ex = split_exp(__uint_as_float(rowmax[t]));
-            const float *src = X + t * ldx;
-            const float *src2 = xf.mode == XF_EDD ? xf.X2 + t * ldx : src;
+            const u32x4 v = *reinterpret_cast<const u32x4 *>(part + t * SPLIT_NS + 4 * q);
+            mx = max(max(v[0], v[1]), max(v[2], v[3]));
+        }
+#pragma unroll
+        for (int o = 8; o >= 1; o >>= 1) mx = max(mx, (unsigned)__shfl_xor((int)mx, o, 64));
+        if (q == 0) {
+            ex_s[r] = split_exp(__uint_as_float(mx));
+            if (cb == 0 && t < Tn) rowmax[t] = mx;
+        }
+    }
+    __syncthreads();
+    const int lr = lane >> 2, p = lane & 3;
+    const int row = m * 16 + lr;
+    const int64_t t = mb * bm + row;
+    const int ex = ex_s[lr];
+    const int s_hi = p ^ ((lr >> 1) & 7), s_lo = s_hi ^ 4;         // (row >> 1) & 7 = (lr >> 1) & 7: row = 16 m + lr
+    const float *src = X + (t < Tn ? t : 0) * ldx;
+    const float *src2 = xf.mode == XF_EDD ? xf.X2 + (t < Tn ? t : 0) * ldx : src;
+    f16x8 *dst = Xp + (mb * n_kt * bm + row) * 8;                 // the row's eight slots in k tile 0 of row block mb
+    bool inf_seen = false;
+    for (int kt = 4 * cb + wave; kt < n_kt; kt += 4 * n_cb) {
+        const int64_t k0 = (int64_t)kt * 32 + 4 * p;
+        f16x8 hi, lo;
+#pragma unroll
+        for (int c = 0; c < 8; ++c) hi[c] = lo[c] = (_Float16)0.0f;
+        if (t < Tn) {
             float v[8], h[8];
 #pragma unroll
             for (int c = 0; c < 8; ++c) { v[c] = 0.0f; h[c] = 0.0f; }
@@ -407,11 +468,13 @@ __global__ void dense_pack_x_split_kernel(const float *__restrict__ X, int64_t T
                 const int64_t k = k0 + 16 * (c >> 2) + (c & 3);
                 if (k >= G) continue;
                 const float y = __builtin_amdgcn_ldexpf(pack_xf<float>(xf, v[c], h[c], inf_seen), ex);
-                const _Float16 hi = (_Float16)y;
-                o[c] = low ? (__builtin_isinf(y) ? (_Float16)0.0f : (_Float16)(y - (float)hi)) : hi;
+                hi[c] = (_Float16)y;
+                lo[c] = __builtin_isinf(y) ? (_Float16)0.0f : (_Float16)(y - (float)hi[c]);
             }
         }
-        Xp[s] = o;
+        f16x8 *o = dst + (int64_t)kt * bm * 8;
+        o[s_hi] = hi;
+        o[s_lo] = lo;
     }
     if (inf_seen) __hip_atomic_store(inf_flag, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }

@@ -569,6 +569,15 @@ class DensePlan:
         _lib.check(fn(self._h, 1 if image else 0, buf.ctypes.data_as(C.c_void_p), buf.nbytes), "wagg_dense_read_w")
         return buf
 
+    def read_split(self, what, nbytes):
+        """The first ``nbytes`` of a split-form workspace as the last apply left it (``wagg_dense_read_w`` with image = 2 / 3):
+        ``what`` = "xp", the packed f16 high / low tiles of X, or "xmax", the row maxima as float bits.  The caller has
+        waited for the apply.  For layout tests."""
+        buf = np.empty(int(nbytes), dtype=np.uint8)
+        _lib.check(_lib.load().wagg_dense_read_w(self._h, {"xp": 2, "xmax": 3}[what], buf.ctypes.data_as(C.c_void_p), buf.nbytes),
+                   "wagg_dense_read_w")
+        return buf
+
     def close(self):
         for r in getattr(self, "_replicas", {}).values():
             r.close()

@@ -488,7 +488,9 @@ int wagg_dense_destroy(wagg_dense *d);
 int wagg_dense_get_den(const wagg_dense *d, double *den_host /* R values */);
 /* Diagnostic entry (layout tests; a library built from an older header lacks it): the stored tiles as they lie on the device, to
  * a host buffer of exactly w_bytes -- image = 0 the packed W, 1 the f16 high / low image of a full-form fp32 plan (WAGG_EINVAL
- * when the plan holds none).  Not for entry-list plans. */
+ * when the plan holds none).  image = 2 / 3: the first `bytes` of the split form's workspaces as the last apply of the plan
+ * left them (the caller has waited for it): 2 the packed f16 high / low tiles of X, 3 the row maxima as float bits, one a
+ * row.  Not for entry-list plans. */
 int wagg_dense_read_w(const wagg_dense *d, int image, void *host, uint64_t bytes);
 /* out[t, r] = sum_g nan0(X[t,g]) * W[g,r] / den[r], fp32 MFMA (v_mfma_f32_16x16x4_f32).
  * ksplit = 0 picks the k-slice count; otherwise a multiple of 8.  The plan owns the packed copy of
