@@ -1,7 +1,7 @@
 """MI355X-native weighted grid->region aggregation engine: a drop-in for the aggregation path of
 ClimateImpactLab/climate_toolbox (``climate_toolbox.aggregations``).  See DESIGN.md."""
 
-__version__ = "0.15.0"
+__version__ = "0.16.0"
 
 from .aggregations import (  # noqa: F401
     weighted_aggregate_grid_to_regions,
@@ -29,6 +29,7 @@ from .standardize import (  # noqa: F401  (coordinate standardisati
     convert_lons_mono,
     rename_coords_to_lon_and_lat,
 )
+from .relative import CellThresholds, cell_quantiles, cell_spell_reduce  # noqa: F401  (per-cell thresholds kept on the device)
 from .transformations import (  # noqa: F401  (tas_poly fused into the aggregation)
     tas_poly,
     tas_poly_aggregate,
@@ -42,5 +43,6 @@ from .transformations import (  # noqa: F401  (tas_poly fused into 
     tas_spell_aggregate,
     tas_rolling_aggregate,
     tas_quantile_aggregate,
+    tas_relative_spell_aggregate,
     validate_edd_snyder_agriculture,
 )

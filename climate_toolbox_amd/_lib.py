@@ -55,6 +55,7 @@ EXPORTS = (
     "wagg_spell_reduce_f32", "wagg_spell_reduce_f64", "wagg_spell_work_bytes",
     "wagg_rolling_reduce_f32", "wagg_rolling_reduce_f64", "wagg_rolling_work_bytes",
     "wagg_quantile_select_f32", "wagg_quantile_select_f64",
+    "wagg_cell_spells_f32", "wagg_cell_spells_f64",
     "wagg_plan_compact_info", "wagg_plan_compact_cells", "wagg_pack_rows_f32", "wagg_pack_rows_f64",
     "wagg_pack_rows_host_f32", "wagg_pack_rows_host_f64",
 )
@@ -83,6 +84,8 @@ ROLL_MAX, ROLL_MIN = 0, 1                        # ... the extreme of a call
 ROLL_MEAN, ROLL_SUM = 0, 1                       # ... and what it is the extreme of
 QUANT_MAX, QUANT_ROWS_MAX = 16, 1024             # WAGG_QUANT_*: quantiles a call takes / the longest period list (128 B of LDS an entry)
 QUANT_LINEAR, QUANT_LOWER, QUANT_HIGHER = 0, 1, 2        # ... and the method of a call
+CELL_SPELL_MAX, CELL_SPELL_GROUP = 64, 4         # WAGG_CELL_SPELL_*: threshold levels a call takes / the kernel's group size
+CELL_SPELL_AMOUNT, CELL_SPELL_EXCESS = 3, 4      # ... and its two fp64 sums, beside SPELL_DAYS / _EVENTS / _LONGEST
 
 
 class HostStats(C.Structure):
@@ -328,6 +331,10 @@ def load():
     for name in ("wagg_quantile_select_f32", "wagg_quantile_select_f64"):
         getattr(L, name).argtypes = [vp, C.c_int64, C.c_int64, C.c_int64, vp, vp, C.c_int32, C.c_int64, vp, vp, C.c_double, f64p, C.c_int,
                                      C.c_int, C.c_int32, C.c_int, vp, C.c_int64, C.c_int64, vp, vp, C.c_int64, vp]
+    for name in ("wagg_cell_spells_f32", "wagg_cell_spells_f64"):
+        getattr(L, name).argtypes = [vp, C.c_int64, C.c_int64, C.c_int64, vp, vp, C.c_int32, C.c_int64, vp, vp, C.c_double, vp, C.c_int,
+                                     C.c_int64, C.c_int64, vp, C.c_int32, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int64, C.c_int64,
+                                     vp, vp, C.c_int64, vp]
     for name in ("wagg_hinge_reduce_f32", "wagg_hinge_reduce_f64"):
         getattr(L, name).argtypes = [vp, C.c_int64, C.c_int64, C.c_int64, vp, vp, C.c_int32, C.c_int64, vp, vp, C.c_double, f64p, C.c_int,
                                      C.c_int, C.c_int, f64p, f64p, f64p, C.c_int, vp, C.c_int64, C.c_int64, vp, vp, C.c_int64, vp]

@@ -1,0 +1,291 @@
+"""Thresholds that are a FIELD: per-cell percentiles kept on the device, and the spell / exceedance statistics measured against
+them (``wagg_cell_spells_*``, csrc/wagg_cell_spells.hip) -- days above the cell's own 90th percentile (TX90p / TN10p), warm-spell
+days (WSDI / CSDI), events above the local 95th percentile, precipitation on days above the cell's 95th wet-day percentile
+(R95pTOT).
+
+  :func:`cell_quantiles`      per-cell quantiles of a variable (``engine.quantile_select``), NOT aggregated: a :class:`CellThresholds`
+  :class:`CellThresholds`     K threshold levels x M planes x grid, in RAW units, with the Kelvin shift of the variable they came from
+  :func:`cell_spell_reduce`   the device-level call: ``engine.spell_reduce`` with a (K, M, n) threshold tensor and a plane per period
+
+The public call on top is :func:`climate_toolbox_amd.transformations.tas_relative_spell_aggregate`.  :func:`cell_spell_reduce`
+lives here and not in ``engine``: its stream-order and graph-replay probes are tests/test_gpu_cell_spell_streams.py."""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from . import _lib, engine as _engine
+
+__all__ = ["CellThresholds", "cell_quantiles", "cell_spell_reduce"]
+
+_STATS = {"days": _lib.SPELL_DAYS, "events": _lib.SPELL_EVENTS, "longest": _lib.SPELL_LONGEST, "amount": _lib.CELL_SPELL_AMOUNT,
+          "excess": _lib.CELL_SPELL_EXCESS}
+
+
+def _is_tensor(v):
+    return type(v).__module__.startswith("torch")
+
+
+def cell_spell_reduce(X, row_begin, rows, offset, thr, plane_of_period=None, min_length=1, stat="days", side="above", doy=None,
+                      windows=None, checked=False, out=None, status=None, stream=None):
+    """:func:`engine.spell_reduce` against PER-CELL thresholds, in ONE launch (``wagg_cell_spells_*``).  Entry ``i`` of period
+    ``p``'s list is hot for cell ``j`` and level ``k`` when its row ``t`` lies in the field, the cell is in season on ``doy[t]``
+    and ``X[t, j] + offset >= thr[k, m, j]`` (``side="above"``) or ``< thr[k, m, j]`` (``"below"``), ``m`` being the period's
+    plane.  ``thr``: a CUDA tensor ``(K, M, n)`` or ``(K, n)`` (one plane) of ``X``'s dtype and device, 1 <= K <=
+    ``_lib.CELL_SPELL_MAX``; it may be strided in its first two dims, the last is contiguous.  ``plane_of_period``: P plane
+    indices in 0..M-1, host integers (checked here, uploaded) or an int32 CUDA tensor; None only for M == 1 (every period reads
+    plane 0) or M == P (period p reads plane p).  The comparison is the scalar call's, formed on the device: the raw value
+    against ``ceilT(float64(thr) - offset)``, so a threshold tensor that is constant over the cells gives
+    :func:`engine.spell_reduce`'s plane bit for bit.  A NaN threshold makes that cell's result NaN; +-inf thresholds compare as
+    they compare; NaN days are never hot.  ``stat``: ``"days"`` / ``"events"`` / ``"longest"`` as for the scalar call, or
+    ``"amount"``: the sum over hot entries of ``float64(x) + offset``, ``"excess"``: of ``(float64(x) + offset) - float64(thr)``
+    (``"below"``: ``float64(thr) - (float64(x) + offset)``) -- fp64, added in list order, rounded once; ``min_length`` must be 1
+    for both.  ``row_begin`` / ``rows`` / ``doy`` / ``windows`` / ``checked`` as for :func:`engine.spell_reduce`; with device
+    lists and ``checked=False`` the library's blocking look also checks the plane indices, with ``checked=True`` a period whose
+    plane index is out of range is NaN and sets bit 2 of the status word.  There is no workspace.  With ``stream=`` everything
+    runs there; the map tensor and ``thr`` are kept alive for it like the lists.  Returns ``(out, status)``: the (K, P, n)
+    tensor and the status word (bit 0: an in-season value was +-inf; bit 2: a plane index was out of range)."""
+    import torch
+    X = _engine._check_X(X, "TG")
+    n = int(X.shape[1])
+    if not (isinstance(thr, torch.Tensor) and thr.is_cuda and thr.dim() in (2, 3)):
+        raise TypeError("thr must be a (K, M, n) or (K, n) CUDA torch tensor")
+    if thr.dtype != X.dtype or thr.device != X.device:
+        raise TypeError("thr must have X's dtype and device, got %s on %s" % (thr.dtype, thr.device))
+    if thr.dim() == 2:
+        thr = thr.unsqueeze(1)
+    K, M = int(thr.shape[0]), int(thr.shape[1])
+    if int(thr.shape[2]) != n:
+        raise ValueError("thr must hold %d cells per plane, got %d" % (n, int(thr.shape[2])))
+    if not 1 <= K <= _lib.CELL_SPELL_MAX:
+        raise ValueError("1..%d threshold levels per call, got %d" % (_lib.CELL_SPELL_MAX, K))
+    if M < 1:
+        raise ValueError("thr must hold at least one plane")
+    if n > 1 and thr.stride(2) != 1:
+        raise ValueError("thr rows must be contiguous (stride(2) == 1)")
+    ldt = int(thr.stride(1)) if M > 1 else max(n, 1)
+    kstride = int(thr.stride(0)) if K > 1 else max(M * ldt, 1)
+    if ldt < n or kstride < M * ldt:
+        raise ValueError("thr must be laid out (K, M, n) with strides (>= M * stride(1), >= n, 1), got %r" % (tuple(thr.stride()),))
+    if stat not in _STATS:
+        raise ValueError("stat must be 'days', 'events', 'longest', 'amount' or 'excess', got %r" % (stat,))
+    if side not in ("above", "below"):
+        raise ValueError("side must be 'above' or 'below', got %r" % (side,))
+    if isinstance(min_length, bool) or not isinstance(min_length, (int, np.integer)) or not 1 <= min_length <= _lib.SPELL_MIN_LENGTH_MAX:
+        raise ValueError("min_length must be an integer in 1..%d, got %r" % (_lib.SPELL_MIN_LENGTH_MAX, min_length))
+    if stat == "longest" and min_length != 1:
+        raise ValueError("stat='longest' does not use min_length: it must be 1, got %r" % (min_length,))
+    if stat in ("amount", "excess") and min_length != 1:
+        raise ValueError("stat=%r has no run counter: min_length must be 1, got %r" % (stat, min_length))
+    P = (int(row_begin.numel()) if isinstance(row_begin, torch.Tensor) else len(np.asarray(row_begin))) - 1
+    pmap = plane_of_period
+    if pmap is None:
+        if M != 1 and M != P:
+            raise ValueError("plane_of_period=None needs one plane or one plane per period (M=%d, P=%d)" % (M, P))
+    else:
+        if not isinstance(pmap, torch.Tensor):
+            h = np.ascontiguousarray(pmap)
+            if h.ndim != 1 or h.dtype.kind not in "iu":
+                raise TypeError("plane_of_period must be a 1-D integer array or an int32 CUDA tensor")
+            if len(h) and (h.min() < 0 or h.max() >= M):
+                raise ValueError("plane_of_period must lie in 0..%d, got %r" % (M - 1, h.tolist()))
+            pmap = torch.from_numpy(h.astype(np.int32)).to(X.device)
+        if not (pmap.is_cuda and pmap.dtype == torch.int32 and pmap.dim() == 1 and pmap.is_contiguous()):
+            raise TypeError("plane_of_period must be a contiguous int32 CUDA tensor (or host integers)")
+        if int(pmap.numel()) != P:
+            raise ValueError("plane_of_period must hold %d entries, got %d" % (P, int(pmap.numel())))
+    res = _engine._grouped_reduce("wagg_cell_spells", (X,), row_begin, rows, doy, windows, checked, offset,
+                                  (C.c_void_p(thr.data_ptr()), K, ldt, kstride, None if pmap is None else C.c_void_p(pmap.data_ptr()), M,
+                                   int(min_length), _STATS[stat], 0 if side == "above" else 1),
+                                  K, lambda L, *a: 0, out, status, False, stream)
+    if stream is not None:                           # the map (uploaded here, perhaps) and thr must outlive the kernel on the
+        for t in (pmap, thr):                        # caller's stream
+            if t is not None:
+                t.record_stream(stream)
+    return res
+
+
+class CellThresholds:
+    """Per-cell thresholds on a grid: ``values`` ``(K, M, a, b)`` (or ``(K, M, G)``, G = a * b cells in row-major ``dims`` order)
+    -- K levels x M planes, a host array or a CUDA tensor, in RAW units; ``shift``: the Kelvin shift of the variable the values
+    were taken from (``values + shift`` is in final units; 0.0: they already are); ``levels``: K numbers (the ``threshold``
+    coordinate of a result); ``labels``: M plane labels (what a period is matched to); ``lat`` / ``lon``: the grid's labels and
+    ``dims`` -- ``("lat", "lon")`` or ``("lon", "lat")`` -- the order of the two grid axes of ``values``."""
+
+    def __init__(self, values, shift, levels, labels, lat, lon, dims=("lat", "lon")):
+        dims = tuple(dims)
+        if dims not in (("lat", "lon"), ("lon", "lat")):
+            raise ValueError("dims must be ('lat', 'lon') or ('lon', 'lat'), got %r" % (dims,))
+        lat, lon = np.asarray(lat), np.asarray(lon)
+        if lat.ndim != 1 or lon.ndim != 1:
+            raise ValueError("lat and lon must be 1-D label arrays")
+        grid = (len(lat), len(lon)) if dims == ("lat", "lon") else (len(lon), len(lat))
+        shape = tuple(int(s) for s in values.shape)
+        if not ((len(shape) == 4 and shape[2:] == grid) or (len(shape) == 3 and shape[2] == grid[0] * grid[1])):
+            raise ValueError("values must be (K, M, %d, %d) or (K, M, %d), got %r" % (grid + (grid[0] * grid[1], shape)))
+        levels, labels = np.asarray(levels), np.asarray(labels)
+        if levels.shape != (shape[0],) or labels.shape != (shape[1],):
+            raise ValueError("levels must hold K = %d numbers and labels M = %d plane labels" % (shape[0], shape[1]))
+        if len(np.unique(labels)) != len(labels):
+            raise ValueError("plane labels must be distinct, got %r" % (labels.tolist(),))
+        if not np.isfinite(float(shift)):
+            raise ValueError("shift must be finite")
+        self.values, self.shift, self.levels, self.labels = values, float(shift), levels.astype(np.float64), labels
+        self.lat, self.lon, self.dims = lat, lon, dims
+
+    @property
+    def K(self):
+        return int(self.values.shape[0])
+
+    @property
+    def M(self):
+        return int(self.values.shape[1])
+
+    @classmethod
+    def from_array(cls, values, lat, lon, dims=("lat", "lon"), labels=None, levels=None, shift=0.0):
+        """A caller's precomputed baseline: ``values`` a host array or a CUDA tensor, 2-D (one level, one plane), 3-D (K levels,
+        one plane) or 4-D (K, M), its last two axes the grid in ``dims`` order.  ``labels`` default to 0..M-1, ``levels`` to
+        0..K-1; ``shift`` as in the class."""
+        if not hasattr(values, "shape"):
+            values = np.asarray(values)
+        nd = len(values.shape)
+        if nd not in (2, 3, 4):
+            raise ValueError("values must be 2-D (grid), 3-D (K, grid) or 4-D (K, M, grid), got %d dimensions" % nd)
+        if not _is_tensor(values) and values.dtype not in (np.float32, np.float64):
+            values = values.astype(np.float64)
+        values = values.reshape((1,) * (4 - nd) + tuple(values.shape)) if nd != 3 else values.reshape(
+            (values.shape[0], 1) + tuple(values.shape[1:]))
+        K, M = int(values.shape[0]), int(values.shape[1])
+        return cls(values, shift, np.arange(K, dtype=np.float64) if levels is None else levels,
+                   np.arange(M) if labels is None else labels, lat, lon, dims)
+
+    def stored(self, lat, lon, dims, lon_perm, dtype, device):
+        """The values as a (K, M, G) CUDA tensor of ``dtype`` in a field's STORED cell order: this grid joined to the field's
+        ``lat`` / ``lon`` labels by exact equality (ValueError for a cell this grid lacks), then laid out like the field's buffer
+        -- ``dims`` order, column ``lon_perm[j]`` of the buffer holding longitude label j (``seasons._stored_windows``'s rule).
+        The selection runs on the device (``engine.take_axis``)."""
+        from ._labels import _exact_index
+        from ._layout import _spatial_layout
+        torch = _engine.require_gpu()
+        try:
+            ilat = _exact_index(self.lat, np.asarray(lat), "threshold latitude")
+            ilon = _exact_index(self.lon, np.asarray(lon), "threshold longitude")
+        except KeyError as e:
+            raise ValueError("the thresholds' grid does not match the field's: %s" % (e.args[0],)) from None
+        src_lon = np.empty(len(ilon), dtype=np.int64)
+        src_lon[np.arange(len(ilon)) if lon_perm is None else np.asarray(lon_perm)] = ilon
+        grid = (len(self.lat), len(self.lon)) if self.dims == ("lat", "lon") else (len(self.lon), len(self.lat))
+        v = self.values
+        v = v if _is_tensor(v) else torch.from_numpy(np.ascontiguousarray(v))
+        v = v.to(device=device, dtype=dtype).reshape((self.K, self.M) + grid)
+        ax_lat, ax_lon = (2, 3) if self.dims == ("lat", "lon") else (3, 2)
+        if not np.array_equal(ilat, np.arange(grid[ax_lat - 2])):
+            v = _engine.take_axis(v, ax_lat, ilat)
+        if not np.array_equal(src_lon, np.arange(grid[ax_lon - 2])):
+            v = _engine.take_axis(v, ax_lon, src_lon)
+        ia, io, *_ = _spatial_layout(dims)
+        if (ia < io) != (self.dims == ("lat", "lon")):
+            v = _engine.relayout(v, [0, 1, 3, 2])
+        elif not v.is_contiguous():
+            v = _engine.relayout(v)
+        return v.reshape(self.K, self.M, len(ilat) * len(ilon))
+
+
+def resolve_planes(plane_labels, period_labels, planes):
+    """The plane every period reads, as P indices into ``plane_labels``.  ``planes`` None: one plane serves every period, or the
+    plane labels equal the period labels one to one; ``"month"``: a period labelled ``year * 100 + month`` reads the plane
+    labelled ``month``; a callable maps a period label to a plane label.  A period without a plane is ValueError naming it."""
+    plane_labels, period_labels = np.asarray(plane_labels), np.asarray(period_labels)
+    M, P = len(plane_labels), len(period_labels)
+    if planes is None:
+        if M == 1:
+            return np.zeros(P, dtype=np.int32)
+        if M != P:
+            raise ValueError("planes=None needs one plane, or a plane per period: %d planes, %d periods" % (M, P))
+        want = list(period_labels.tolist())
+    elif isinstance(planes, str):
+        if planes != "month":
+            raise ValueError("planes must be None, 'month' or a callable, got %r" % (planes,))
+        if period_labels.dtype.kind not in "iu":
+            raise ValueError("planes='month' needs period labels of the form year * 100 + month, got dtype %s" % period_labels.dtype)
+        want = [int(v) % 100 for v in period_labels.tolist()]
+    elif callable(planes):
+        want = [planes(v) for v in period_labels.tolist()]
+    else:
+        raise ValueError("planes must be None, 'month' or a callable, got %r" % (planes,))
+    index = {v: i for i, v in enumerate(plane_labels.tolist())}
+    out = np.empty(P, dtype=np.int32)
+    for p, (label, w) in enumerate(zip(period_labels.tolist(), want)):
+        w = w.item() if isinstance(w, np.generic) else w
+        if w not in index:
+            raise ValueError("period %r has no threshold plane (it asks for plane %r; the planes are %r)" % (label, w, plane_labels.tolist()))
+        out[p] = index[w]
+    return out
+
+
+def cell_quantiles(ds, q, tas="tas", period=None, method="linear", season=None, leap_days="keep"):
+    """Per-cell quantiles of ``ds[tas]`` kept on the device and NOT aggregated: a :class:`CellThresholds` with one level per ``q``
+    and one plane per period -- the baseline of :func:`~climate_toolbox_amd.transformations.tas_relative_spell_aggregate`.
+
+    q         a non-empty sequence of numbers in [0, 1] (``engine.quantile_select``'s rule); more than 16 go in several launches.
+    tas       a plain variable or one shifted by ``convert_kelvin_to_celsius``: the quantiles are selected from the RAW elements
+              (offset 0) and the shift is stored in ``.shift``, so a consumer that reads the same variable compares raw
+              elements with raw order statistics.  A power or a degree-day variable is ValueError.
+    period    None: the whole record is one plane (label 0); "year", "month" or a label per day (``periods.period_rows``): one
+              plane per label -- month numbers 1..12 over a 30-year baseline give 12 planes of at most 930 days.  A plane of
+              more than ``_lib.QUANT_ROWS_MAX`` days is ValueError.
+    method    "linear", "lower" or "higher".
+    season, leap_days   as in :func:`~climate_toolbox_amd.transformations.tas_quantile_aggregate`.
+
+    There is no weights table and no plan.  A cell without a valid day in a plane is NaN there."""
+    from . import periods, seasons
+    from ._layout import _flatten_for_device, _spatial_layout, _to_device
+    from .transformations import remove_leap_days
+    if leap_days not in ("keep", "drop"):
+        raise ValueError("leap_days must be 'keep' or 'drop', got %r" % (leap_days,))
+    if method not in ("linear", "lower", "higher"):
+        raise ValueError("method must be 'linear', 'lower' or 'higher', got %r" % (method,))
+    raw = list(np.atleast_1d(np.asarray(q, dtype=object)))
+    if len(raw) < 1:
+        raise ValueError("q must be a non-empty sequence of numbers in [0, 1], got %r" % (q,))
+    qv = np.concatenate([_engine._quantile_levels(raw[k0:k0 + _lib.QUANT_MAX]) for k0 in range(0, len(raw), _lib.QUANT_MAX)])
+    if "time" not in ds.coords:
+        raise ValueError("the dataset has no 'time' coordinate")
+    if leap_days == "drop":
+        ds = remove_leap_days(ds)
+    var = ds[tas]
+    if not hasattr(var, "_values"):                  # (an xarray Dataset: the public calls take one through the table's join,
+        raise TypeError("cell_quantiles takes a climate_toolbox_amd.minixr Dataset: there is no segment table here to join an "     # which
+                        "xarray Dataset through; wrap the arrays as minixr.Dataset({name: (dims, values)}, coords=...)")         # this call lacks)
+    xform = getattr(var, "_xform", None)
+    if getattr(var, "_edd", None) is not None or (xform is not None and xform[1] != 1):
+        raise ValueError("cell_quantiles needs a plain (or Kelvin-shifted) variable, got %r" % (tas,))
+    dims = tuple(var.dims)
+    ia, io, _, _, others = _spatial_layout(dims)
+    if [dims[i] for i in others] != ["time"]:
+        raise ValueError("cell_quantiles needs a field whose only dimension besides lat / lon is time, got dims %r" % (dims,))
+    time_values = np.asarray(ds.coords["time"].values)
+    if period is None:
+        labels, row_begin, rows = np.array([0]), np.array([0, len(time_values)]), np.arange(len(time_values))
+    else:
+        labels, row_begin, rows = periods.period_rows(time_values, period)
+    lat, lon = np.asarray(ds.coords["lat"].values), np.asarray(ds.coords["lon"].values)
+    lon_perm = getattr(var, "_lon_perm", None)
+    shape = dict(zip(dims, tuple(var.shape)))
+    doy = win = None
+    if season is not None:
+        win = seasons._stored_windows(season, lat, lon, dims, shape, lon_perm)
+        doy = seasons.day_of_year(time_values)
+    _engine.require_gpu()
+    X2, layout, _, _ = _flatten_for_device(var._values, dims)
+    Xd = _to_device(X2)
+    Xd = Xd if layout == "TG" else _engine.relayout(Xd, [1, 0])
+    parts = [_engine.quantile_select(Xd, row_begin, rows, 0.0, qv[k0:k0 + _lib.QUANT_MAX], method=method, doy=doy, windows=win)[0]
+             for k0 in range(0, len(qv), _lib.QUANT_MAX)]
+    out = parts[0] if len(parts) == 1 else _engine.require_gpu().cat(parts)
+    stored = ("lat", "lon") if ia < io else ("lon", "lat")
+    out = out.reshape((len(qv), len(labels)) + tuple(shape[d] for d in stored))
+    if lon_perm is not None:                         # label j sits in column lon_perm[j] of the buffer: back to label order
+        out = _engine.take_axis(out, 2 + stored.index("lon"), np.asarray(lon_perm))
+    return CellThresholds(out, 0.0 if xform is None else float(xform[0]), qv, labels, lat, lon, stored)

@@ -366,13 +366,15 @@ def _plain_variable(ds, variable, what):
 
 
 def _grouped_totals(ds, variable, aggwt, agglev, weights, backup_aggwt, lists, P, season, grid, time_values, cells, name, of, rule,
-                    launches):
+                    launches, pass_cells=False):
     """The sum-first route of the grouped statistics (ladder, bins, hinges, exposure bins, spells, rolling extremes, period quantiles): every launch reduces its planes per period
     first, then one apply per launch contracts its planes * P rows on whatever plan serves the table.  ``name`` / ``of``: the statistic in
     the messages ("bin count" / "bins"); ``rule(ds, variable, what)``: ``(second field or None, offset)`` of a variable the
     statistic takes, ValueError for any other; ``launches``: an iterable, consumed as the launches run, of
     ``reduce(Xd, Hd, rb, rw, offset, **season)`` -> ``(planes, status)``, each one engine call on its cut of the parameter
     list.  ``season`` None: every day counts.  ``cells="referenced"``: all of it on the packed rows of :func:`_referenced_rows`.
+    ``pass_cells``: a launch also gets ``cells=`` -- None for whole rows, else the grid cell of every packed column (a
+    statistic with a per-cell parameter takes its columns by it).
     Returns ``(stack, rdims, coords, was_xarray)`` like :func:`_season_totals`, ``stack`` being the (planes, P | R, R | P)
     results of all launches in order."""
     from . import periods as _periods
@@ -388,7 +390,7 @@ def _grouped_totals(ds, variable, aggwt, agglev, weights, backup_aggwt, lists, P
         keep_dev = _agg._device_results_wanted() and _is_device_tensor(values) and not ds._was_xarray
         res = []
         for reduce in launches:
-            field, status = reduce(Xd, Hd, rb, rw, offset, doy=doy, windows=win, checked=True)
+            field, status = reduce(Xd, Hd, rb, rw, offset, doy=doy, windows=win, checked=True, **({"cells": pos} if pass_cells else {}))
             if int(status.item()) & 1:
                 raise ValueError("%s: a counted value of %r is +-inf; period totals of %s have no daily route that could give it the "
                                  "daily treatment" % (name, variable, of))
@@ -475,6 +477,39 @@ def _spell_totals(ds, variable, aggwt, agglev, weights, backup_aggwt, lists, P, 
 
     return _grouped_totals(ds, variable, aggwt, agglev, weights, backup_aggwt, lists, P, season, grid, time_values, cells, "spell count",
                            "spells", _plain_variable, launches())
+
+
+def _cell_spell_totals(ds, variable, aggwt, agglev, weights, backup_aggwt, lists, P, thresholds, plane_of_period, min_length, stat, side,
+                       season, grid, time_values, cells="all"):
+    """Period totals of the spell / exceedance statistic ``stat`` of ``variable`` against the PER-CELL thresholds of a
+    ``relative.CellThresholds`` (``wagg_cell_spells_*``, up to 64 levels a launch) through :func:`_grouped_totals`.  ``variable``:
+    as for :func:`_bin_totals`; ``grid``: the dataset's own ``(lat, lon)`` labels (also without a season), to which the
+    thresholds' grid is joined by exact labels in the field's stored cell order, converted to the field's dtype once; with
+    ``cells="referenced"`` the packed columns are taken on the device.  ``plane_of_period``: the plane index of every period.
+    The kernel's offset is the field's shift minus the thresholds' own -- exactly 0 when both come from one Kelvin variable.  A
+    cell whose threshold is NaN is NaN there, which the contraction treats as any NaN of a field.  ``stack`` is the (K, P | R,
+    R | P) results in the levels' order."""
+    from ._lib import CELL_SPELL_MAX
+    from .relative import cell_spell_reduce
+    state = {}
+
+    def stored(X, cells_of_pos):
+        if "thr" not in state:                       # (behind _gridded_field's checks: once, whatever the number of launches)
+            thr = thresholds.stored(grid[0], grid[1], ds._src_dims[variable], ds._lon_perms.get(variable), X.dtype, X.device)
+            state["thr"] = thr if cells_of_pos is None else _engine.take_axis(thr, 2, cells_of_pos)
+            state["map"] = _engine.require_gpu().from_numpy(np.ascontiguousarray(plane_of_period, dtype=np.int32)).to(X.device)
+        return state["thr"], state["map"]
+
+    def launches():
+        for k0 in range(0, thresholds.K, CELL_SPELL_MAX):
+            def reduce(X, H, rb, rw, offset, cells=None, k0=k0, **kw):
+                thr, pmap = stored(X, cells)
+                return cell_spell_reduce(X, rb, rw, offset - thresholds.shift, thr[k0:k0 + CELL_SPELL_MAX], plane_of_period=pmap,
+                                         min_length=min_length, stat=stat, side=side, **kw)
+            yield reduce
+
+    return _grouped_totals(ds, variable, aggwt, agglev, weights, backup_aggwt, lists, P, season, None if season is None else grid,
+                           time_values, cells, "relative spell count", "relative spells", _plain_variable, launches(), pass_cells=True)
 
 
 def _rolling_totals(ds, variable, aggwt, agglev, weights, backup_aggwt, lists, P, lengths, stat, of, season, grid, time_values,

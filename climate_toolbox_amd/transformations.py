@@ -26,7 +26,7 @@ from . import aggregations as _agg
 __all__ = ["tas_poly", "tas_poly_aggregate", "snyder_edd", "snyder_gdd", "snyder_edd_aggregate", "snyder_exposure_aggregate",
            "tas_bins_aggregate",
            "tas_hinge_aggregate", "tas_rcspline_aggregate", "tas_spell_aggregate", "tas_rolling_aggregate",
-           "tas_quantile_aggregate",
+           "tas_quantile_aggregate", "tas_relative_spell_aggregate",
            "validate_edd_snyder_agriculture", "ordinal", "remove_leap_days", "convert_kelvin_to_celsius"]
 
 KELVIN = 273.15
@@ -623,6 +623,83 @@ def tas_spell_aggregate(ds, thresholds, aggwt, agglev, weights, min_length=3, st
     rdims, coords = _time_as_period(rdims, coords, labels)
     out = _agg._as_dataset({varname: res}, ("threshold",) + tuple(rdims), dict(coords, threshold=t.copy()), was_xr)
     out[varname].attrs["units"] = "1" if stat == "events" else "days"
+    out[varname].attrs["min_length"] = min_length
+    out[varname].attrs["stat"] = stat
+    out[varname].attrs["side"] = side
+    return out
+
+
+def tas_relative_spell_aggregate(ds, thresholds, aggwt, agglev, weights, min_length=3, stat="days", side="above", tas="tas",
+                                 varname="tas-relative-spell", backup_aggwt="areawt", period="year", planes=None, season=None,
+                                 cells="all", leap_days="keep"):
+    """:func:`tas_spell_aggregate` against thresholds that are each CELL'S OWN: days above the cell's 90th percentile of a
+    baseline (TX90p / TN10p), warm-spell days in runs of at least 6 such days (WSDI / CSDI), heat-wave events above the local
+    95th percentile, and with ``stat="amount"`` on precipitation the rain that falls on days above the cell's 95th wet-day
+    percentile (R95pTOT).  Counted on the device in ONE pass per 64 levels (``wagg_cell_spells_*``), the thresholds read per
+    cell, instead of a boolean grid, a run-length scan and a masked field per level.
+
+    thresholds  a :class:`~climate_toolbox_amd.relative.CellThresholds`: what
+                :func:`~climate_toolbox_amd.relative.cell_quantiles` returned for a baseline, or a caller's own field
+                (``CellThresholds.from_array``).  Its grid is joined to the dataset's ``lat`` / ``lon`` by exact label equality
+                (ValueError for a dataset cell it lacks) and its values are converted to the field's dtype once.  The comparison is
+                :func:`tas_spell_aggregate`'s exact one, with the kernel's offset = the variable's Kelvin shift minus
+                ``thresholds.shift``: exactly 0 when both come from the same Kelvin variable, so raw elements are compared with raw
+                order statistics.  A cell whose threshold is NaN has NO VALUE there and enters the regional mean as a NaN of
+                :func:`tas_quantile_aggregate` does.  More than 64 levels go in several launches.
+    planes      which plane of ``thresholds`` a period reads.  None: there is one plane, or the plane labels equal the period
+                labels one to one.  "month": a period labelled ``year * 100 + month`` reads the plane labelled ``month``.  A
+                callable maps a period label to a plane label.  A period without a plane is ValueError naming the label.  EVERY
+                PERIOD READS ONE PLANE: thresholds that change inside a period (calendar-day percentiles within a year) are not
+                built.
+    stat        "days", "events", "longest" as in :func:`tas_spell_aggregate` (same ``min_length`` rules), or "amount": the sum of
+                the variable over the hot days, "excess": the sum of (variable - threshold) over them (``side="below"``:
+                threshold - variable); the two sums have no run counter, and a ``min_length`` other than 1 or the default is
+                ValueError.  "excess" does not depend on where a Kelvin shift sits.  "AMOUNT" NEEDS THRESHOLDS IN FINAL UNITS
+                (``thresholds.shift == 0``: a variable without a shift such as precipitation, or a baseline handed in through
+                ``from_array``): the kernel adds ONE offset to a day's value, the field's shift minus the thresholds', so with
+                shifted thresholds the sum would be of raw values -- that combination is ValueError, never a wrong number.
+    everything else   exactly as in :func:`tas_spell_aggregate`; RUNS ARE TRUNCATED AT PERIOD BOUNDARIES.
+
+    Returns one Dataset with the variable ``varname`` of dims ``("threshold", "period", agglev)``, the coordinate ``threshold`` =
+    ``thresholds.levels``, ``attrs["units"]`` = ``"days"`` (days, longest), ``"1"`` (events) or the variable's units (amount,
+    excess; ``"C"`` when it carries the Kelvin shift), ``attrs["stat"]``, ``attrs["side"]``, ``attrs["min_length"]``;
+    ``results_on_device()`` is honoured; a counted +-inf raises ValueError."""
+    from .relative import CellThresholds, resolve_planes
+    if not isinstance(thresholds, CellThresholds):
+        raise TypeError("thresholds must be a CellThresholds (relative.cell_quantiles or CellThresholds.from_array), got %r"
+                        % (type(thresholds).__name__,))
+    if stat not in ("days", "events", "longest", "amount", "excess"):
+        raise ValueError("stat must be 'days', 'events', 'longest', 'amount' or 'excess', got %r" % (stat,))
+    if side not in ("above", "below"):
+        raise ValueError("side must be 'above' or 'below', got %r" % (side,))
+    if isinstance(min_length, bool) or not isinstance(min_length, (int, np.integer)) or not 1 <= min_length <= 32767:
+        raise ValueError("min_length must be an integer in 1..32767, got %r" % (min_length,))
+    min_length = int(min_length)
+    if stat in ("longest", "amount", "excess"):
+        if min_length not in (1, 3):
+            raise ValueError("stat=%r does not use min_length (leave it out, or pass 1), got %r" % (stat, min_length))
+        min_length = 1
+    if not (planes is None or planes == "month" or callable(planes)):
+        raise ValueError("planes must be None, 'month' or a callable, got %r" % (planes,))
+    if stat == "amount" and thresholds.shift != 0.0:
+        raise ValueError("stat='amount' needs thresholds in final units (thresholds.shift == 0, got %r): one offset serves the comparison "
+                         "and the sum, so the amount against shifted thresholds would be a sum of raw values; stat='excess' has no such "
+                         "limit" % (thresholds.shift,))
+    re, var, weights, time_values, labels, _, lists = _period_setup("tas_relative_spell_aggregate", "a relative spell count", ds, tas,
+                                                                    weights, period, season, cells, leap_days)
+    pmap = resolve_planes(thresholds.labels, labels, planes)
+    grid = (np.asarray(ds.coords["lat"].values), np.asarray(ds.coords["lon"].values))       # (the grid's own labels: `re` carries the table's)
+    from . import seasons
+    res, rdims, coords, was_xr = seasons._cell_spell_totals(re, tas, aggwt, agglev, weights, backup_aggwt, lists, len(labels), thresholds,
+                                                            pmap, min_length, stat, side, season, grid, time_values, cells=cells)
+    rdims, coords = _time_as_period(rdims, coords, labels)
+    out = _agg._as_dataset({varname: res}, ("threshold",) + tuple(rdims), dict(coords, threshold=thresholds.levels.copy()), was_xr)
+    if stat in ("amount", "excess"):
+        units = "C" if getattr(var, "_xform", None) is not None else _units(var)
+    else:
+        units = "1" if stat == "events" else "days"
+    if units is not None:
+        out[varname].attrs["units"] = units
     out[varname].attrs["min_length"] = min_length
     out[varname].attrs["stat"] = stat
     out[varname].attrs["side"] = side

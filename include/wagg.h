@@ -86,7 +86,8 @@ int wagg_version(void);                 /* 10000*major + 100*minor + patch; 0.4.
                                            0.9.0: packed rows (wagg_pack_rows_*, WAGG_APPLY_COMPACT_ROWS);
                                            0.13.0: spell statistics (wagg_spell_reduce_*);
                                            0.14.0: rolling-window extremes (wagg_rolling_reduce_*);
-                                           0.15.0: period quantiles (wagg_quantile_select_*) */
+                                           0.15.0: period quantiles (wagg_quantile_select_*);
+                                           0.16.0: spells against per-cell thresholds (wagg_cell_spells_*) */
 int wagg_device_count(void);            /* number of visible HIP devices (0 if none), never <0  */
 /* Time-axis sharding rule of the multi-GPU form (one process per GPU; climate_toolbox_amd/timeshard.py):
  * rank `rank` of `world` owns rows [*start, *stop) of T; the first T mod world ranks hold one row more. */
@@ -1007,6 +1008,55 @@ int wagg_quantile_select_f64(const double *X_dev, int64_t T, int64_t n, int64_t 
                              const int32_t *rows_dev, int32_t P, int64_t n_rows, const int32_t *doy_dev, const int32_t *win_dev,
                              double offset, const double *q, int n_q, int method, int32_t max_rows, int flags, double *out_dev,
                              int64_t ldo, int64_t out_pstride, int32_t *status_dev, void *work_dev, int64_t work_bytes, void *stream);
+
+/* ---- spells and exceedances against PER-CELL thresholds, per period and season, in one pass (0.16.0) ----------------------------
+ * Days above the cell's own 90th percentile (TX90p / TN10p), warm-spell days (WSDI / CSDI), events above the local 95th percentile,
+ * precipitation on days above the cell's 95th wet-day percentile (R95pTOT): wagg_spell_reduce_*'s statistics with the threshold
+ * read from a device field -- what wagg_quantile_select_* writes, or a caller's baseline -- for n_thr threshold levels,
+ * 1 <= n_thr <= WAGG_CELL_SPELL_MAX, in one launch, taken in groups of WAGG_CELL_SPELL_GROUP.
+ *   thr_dev            a DEVICE array of the element type, logically (n_thr, M, n):  thr[k][m][j] = thr_dev[k * thr_kstride +
+ *                      m * ldt + j];  ldt >= n, thr_kstride >= M * ldt, M >= 1.  Read once per block, ahead of the rows.
+ *   plane_of_period_dev   a DEVICE int32[P]: period p reads the ONE plane m = plane_of_period_dev[p].  NULL is allowed only for
+ *                      M == 1 (m = 0) and M == P (m = p); otherwise WAGG_EINVAL.  Without WAGG_PERIOD_ROWS_CHECKED the library's
+ *                      blocking look at the lists also checks 0 <= m < M (WAGG_EINVAL).  With the flag the kernel confines itself:
+ *                      a period whose m is out of range writes NaN in every plane and sets bit 2 of status_dev.
+ * Cell j, period p, level k: the entries i of rows[row_begin[p] : row_begin[p + 1]] are walked IN LIST ORDER.  Entry i is HOT when
+ * t = rows[i] lies in [0, T), cell j is in season on doy[t] (when a season is given) and  X[t, j] + offset >= thr[k][m][j]
+ * (below = 0)  or  < thr[k][m][j]  (below = 1).  THE COMPARISON RULE is wagg_spell_reduce_*'s, formed on the device: the kernel
+ * compares the RAW X[t, j] against  c = ceilT((double)thr[k][m][j] - offset)  -- one fp64 subtraction, rounded to nearest, stepped
+ * up once where that lies below -- so a threshold field that is constant over the cells gives wagg_spell_reduce_*'s plane BIT FOR
+ * BIT.  NaN days are never hot; +-inf thresholds compare as they compare (a constant plane is allowed here).  A NaN THRESHOLD MAKES
+ * out[k][p][j] NaN, for every statistic.  Runs, gaps, seasons and bit 0 of status_dev are wagg_spell_reduce_*'s: a gap in the row
+ * numbers, an out-of-season day, a NaN and the end of the list end a run, RUNS ARE TRUNCATED AT PERIOD BOUNDARIES, an in-season
+ * +-inf sets bit 0, a piece none of whose cells is in season is not read but still ends the runs.  With L = min_length, out[k][p][j] is
+ *   WAGG_SPELL_DAYS / WAGG_SPELL_EVENTS / WAGG_SPELL_LONGEST     as for wagg_spell_reduce_* (int32 state, exact in fp32 up to 2^24)
+ *   WAGG_CELL_SPELL_AMOUNT   the sum over the hot entries of  (double)X[t, j] + offset
+ *   WAGG_CELL_SPELL_EXCESS   ... of  ((double)X[t, j] + offset) - (double)thr[k][m][j]   (below = 0), or of
+ *                            (double)thr[k][m][j] - ((double)X[t, j] + offset)            (below = 1)
+ * The two sums have no run counter: min_length must be 1 (WAGG_EINVAL otherwise).  Each term is two separately rounded fp64
+ * operations; the terms are added one at a time IN LIST ORDER to an fp64 accumulator that starts at 0, cast once on the store.
+ * The sequential order is the definition: a NumPy loop reproduces the bits (tests/cell_spell_ref.py).
+ * Arguments otherwise as for wagg_spell_reduce_*.  Rows are read in 16-byte pieces when X_dev AND thr_dev are 16-byte aligned and
+ * ldx, ldt (M > 1) and thr_kstride (n_thr > 1) are multiples of a piece; otherwise element by element, with the same results.
+ * work_dev / work_bytes are IGNORED: a list is never split, and the family has no work-size query.  Every bad argument is
+ * WAGG_EINVAL with a message, decided before any device call.  Plane k of a many-level call is the plane of the call with level
+ * k alone.                                                                                                                       */
+#define WAGG_CELL_SPELL_MAX 64
+#define WAGG_CELL_SPELL_GROUP 4
+#define WAGG_CELL_SPELL_AMOUNT 3
+#define WAGG_CELL_SPELL_EXCESS 4
+int wagg_cell_spells_f32(const float *X_dev, int64_t T, int64_t n, int64_t ldx, const int32_t *row_begin_dev,
+                         const int32_t *rows_dev, int32_t P, int64_t n_rows, const int32_t *doy_dev, const int32_t *win_dev,
+                         double offset, const float *thr_dev, int n_thr, int64_t ldt, int64_t thr_kstride,
+                         const int32_t *plane_of_period_dev, int32_t M, int min_length, int stat, int below, int flags,
+                         float *out_dev, int64_t ldo, int64_t out_pstride, int32_t *status_dev, void *work_dev, int64_t work_bytes,
+                         void *stream);
+int wagg_cell_spells_f64(const double *X_dev, int64_t T, int64_t n, int64_t ldx, const int32_t *row_begin_dev,
+                         const int32_t *rows_dev, int32_t P, int64_t n_rows, const int32_t *doy_dev, const int32_t *win_dev,
+                         double offset, const double *thr_dev, int n_thr, int64_t ldt, int64_t thr_kstride,
+                         const int32_t *plane_of_period_dev, int32_t M, int min_length, int stat, int below, int flags,
+                         double *out_dev, int64_t ldo, int64_t out_pstride, int32_t *status_dev, void *work_dev, int64_t work_bytes,
+                         void *stream);
 
 /* ---- packed rows: only the quads a segment table references, as a device matrix (0.9.0) ---------------------------------------
  * A single segment-table plan with a whole-line chunking (wagg_plan_info.lines) knows the distinct aligned 4-cell QUADS of a
