@@ -55,7 +55,7 @@ EXPORTS = (
     "wagg_spell_reduce_f32", "wagg_spell_reduce_f64", "wagg_spell_work_bytes",
     "wagg_rolling_reduce_f32", "wagg_rolling_reduce_f64", "wagg_rolling_work_bytes",
     "wagg_quantile_select_f32", "wagg_quantile_select_f64",
-    "wagg_cell_spells_f32", "wagg_cell_spells_f64",
+    "wagg_cell_spells_f32", "wagg_cell_spells_f64", "wagg_row_cell_spells_f32", "wagg_row_cell_spells_f64",
     "wagg_plan_compact_info", "wagg_plan_compact_cells", "wagg_pack_rows_f32", "wagg_pack_rows_f64",
     "wagg_pack_rows_host_f32", "wagg_pack_rows_host_f64",
 )
@@ -331,7 +331,7 @@ def load():
     for name in ("wagg_quantile_select_f32", "wagg_quantile_select_f64"):
         getattr(L, name).argtypes = [vp, C.c_int64, C.c_int64, C.c_int64, vp, vp, C.c_int32, C.c_int64, vp, vp, C.c_double, f64p, C.c_int,
                                      C.c_int, C.c_int32, C.c_int, vp, C.c_int64, C.c_int64, vp, vp, C.c_int64, vp]
-    for name in ("wagg_cell_spells_f32", "wagg_cell_spells_f64"):
+    for name in ("wagg_cell_spells_f32", "wagg_cell_spells_f64", "wagg_row_cell_spells_f32", "wagg_row_cell_spells_f64"):
         getattr(L, name).argtypes = [vp, C.c_int64, C.c_int64, C.c_int64, vp, vp, C.c_int32, C.c_int64, vp, vp, C.c_double, vp, C.c_int,
                                      C.c_int64, C.c_int64, vp, C.c_int32, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int64, C.c_int64,
                                      vp, vp, C.c_int64, vp]

@@ -6,9 +6,13 @@ days (WSDI / CSDI), events above the local 95th percentile, precipitation on day
   :func:`cell_quantiles`      per-cell quantiles of a variable (``engine.quantile_select``), NOT aggregated: a :class:`CellThresholds`
   :class:`CellThresholds`     K threshold levels x M planes x grid, in RAW units, with the Kelvin shift of the variable they came from
   :func:`cell_spell_reduce`   the device-level call: ``engine.spell_reduce`` with a (K, M, n) threshold tensor and a plane per period
+                              (``wagg_cell_spells_*``) or per ROW (``plane_of_row=``: ``wagg_row_cell_spells_*``)
+  :func:`calendar_day_rows`   the pooled row lists of a calendar-day baseline (a window of days around every occurrence of a day)
+  :func:`resolve_row_planes`  the plane every day of a dataset reads in a calendar-day baseline
 
 The public call on top is :func:`climate_toolbox_amd.transformations.tas_relative_spell_aggregate`.  :func:`cell_spell_reduce`
-lives here and not in ``engine``: its stream-order and graph-replay probes are tests/test_gpu_cell_spell_streams.py."""
+lives here and not in ``engine``: its stream-order and graph-replay probes are tests/test_gpu_cell_spell_streams.py and, for
+``plane_of_row=``, tests/test_gpu_cell_spell_rows_streams.py."""
 from __future__ import annotations
 
 import ctypes as C
@@ -17,7 +21,7 @@ import numpy as np
 
 from . import _lib, engine as _engine
 
-__all__ = ["CellThresholds", "cell_quantiles", "cell_spell_reduce"]
+__all__ = ["CellThresholds", "cell_quantiles", "cell_spell_reduce", "calendar_day_rows", "resolve_row_planes"]
 
 _STATS = {"days": _lib.SPELL_DAYS, "events": _lib.SPELL_EVENTS, "longest": _lib.SPELL_LONGEST, "amount": _lib.CELL_SPELL_AMOUNT,
           "excess": _lib.CELL_SPELL_EXCESS}
@@ -28,7 +32,7 @@ def _is_tensor(v):
 
 
 def cell_spell_reduce(X, row_begin, rows, offset, thr, plane_of_period=None, min_length=1, stat="days", side="above", doy=None,
-                      windows=None, checked=False, out=None, status=None, stream=None):
+                      windows=None, checked=False, out=None, status=None, stream=None, plane_of_row=None):
     """:func:`engine.spell_reduce` against PER-CELL thresholds, in ONE launch (``wagg_cell_spells_*``).  Entry ``i`` of period
     ``p``'s list is hot for cell ``j`` and level ``k`` when its row ``t`` lies in the field, the cell is in season on ``doy[t]``
     and ``X[t, j] + offset >= thr[k, m, j]`` (``side="above"``) or ``< thr[k, m, j]`` (``"below"``), ``m`` being the period's
@@ -45,7 +49,18 @@ def cell_spell_reduce(X, row_begin, rows, offset, thr, plane_of_period=None, min
     lists and ``checked=False`` the library's blocking look also checks the plane indices, with ``checked=True`` a period whose
     plane index is out of range is NaN and sets bit 2 of the status word.  There is no workspace.  With ``stream=`` everything
     runs there; the map tensor and ``thr`` are kept alive for it like the lists.  Returns ``(out, status)``: the (K, P, n)
-    tensor and the status word (bit 0: an in-season value was +-inf; bit 2: a plane index was out of range)."""
+    tensor and the status word (bit 0: an in-season value was +-inf; bit 2: a plane index was out of range).
+
+    ``plane_of_row`` (not together with ``plane_of_period``: ValueError): T plane indices, host integers or an int32 CUDA tensor --
+    the plane is then picked PER ENTRY, ``m = plane_of_row[rows[i]]`` (``wagg_row_cell_spells_*``): calendar-day thresholds inside
+    a period.  Everything above holds with these changes: the comparison value is formed per row; ``"excess"`` subtracts the
+    threshold of that row; a cell's result is NaN if any COUNTED entry of the period (its row in the field, the cell in season) had
+    a NaN threshold, so a cell with no counted entry in a period gives 0 where the by-period call gives NaN for a NaN threshold
+    even then; host indices are checked against 0..M-1 only at the rows the host lists name (rows no list names need no valid
+    plane); with device lists and ``checked=False`` the library's blocking look checks the listed rows' indices, with
+    ``checked=True`` a period that meets an index out of range is NaN and sets bit 2."""
+    if plane_of_period is not None and plane_of_row is not None:
+        raise ValueError("plane_of_period and plane_of_row exclude each other: a plane per period, or a plane per row")
     import torch
     X = _engine._check_X(X, "TG")
     n = int(X.shape[1])
@@ -80,7 +95,28 @@ def cell_spell_reduce(X, row_begin, rows, offset, thr, plane_of_period=None, min
         raise ValueError("stat=%r has no run counter: min_length must be 1, got %r" % (stat, min_length))
     P = (int(row_begin.numel()) if isinstance(row_begin, torch.Tensor) else len(np.asarray(row_begin))) - 1
     pmap = plane_of_period
-    if pmap is None:
+    if plane_of_row is not None:
+        pmap, T = plane_of_row, int(X.shape[0])
+        if not isinstance(pmap, torch.Tensor):
+            h = np.ascontiguousarray(pmap)
+            if h.ndim != 1 or h.dtype.kind not in "iu":
+                raise TypeError("plane_of_row must be a 1-D integer array or an int32 CUDA tensor")
+            if len(h) != T:
+                raise ValueError("plane_of_row must hold %d entries (one per row of X), got %d" % (T, len(h)))
+            if not isinstance(rows, torch.Tensor) and not isinstance(row_begin, torch.Tensor):      # (the rows the host lists name)
+                rb_h, rw_h = np.asarray(row_begin, dtype=np.int64), np.asarray(rows, dtype=np.int64)
+                named = rw_h[rb_h[0]:rb_h[-1]] if len(rb_h) else rw_h[:0]
+                named = named[(named >= 0) & (named < T)]
+                bad = named[(h[named] < 0) | (h[named] >= M)]
+                if len(bad):
+                    raise ValueError("plane_of_row must lie in 0..%d at every listed row, got %d at row %d"
+                                     % (M - 1, int(h[bad[0]]), int(bad[0])))
+            pmap = torch.from_numpy(np.clip(h, -1, np.iinfo(np.int32).max).astype(np.int32)).to(X.device)
+        if not (pmap.is_cuda and pmap.dtype == torch.int32 and pmap.dim() == 1 and pmap.is_contiguous()):
+            raise TypeError("plane_of_row must be a contiguous int32 CUDA tensor (or host integers)")
+        if int(pmap.numel()) != T:
+            raise ValueError("plane_of_row must hold %d entries (one per row of X), got %d" % (T, int(pmap.numel())))
+    elif pmap is None:
         if M != 1 and M != P:
             raise ValueError("plane_of_period=None needs one plane or one plane per period (M=%d, P=%d)" % (M, P))
     else:
@@ -95,7 +131,8 @@ def cell_spell_reduce(X, row_begin, rows, offset, thr, plane_of_period=None, min
             raise TypeError("plane_of_period must be a contiguous int32 CUDA tensor (or host integers)")
         if int(pmap.numel()) != P:
             raise ValueError("plane_of_period must hold %d entries, got %d" % (P, int(pmap.numel())))
-    res = _engine._grouped_reduce("wagg_cell_spells", (X,), row_begin, rows, doy, windows, checked, offset,
+    res = _engine._grouped_reduce("wagg_cell_spells" if plane_of_row is None else "wagg_row_cell_spells", (X,), row_begin, rows, doy,
+                                  windows, checked, offset,
                                   (C.c_void_p(thr.data_ptr()), K, ldt, kstride, None if pmap is None else C.c_void_p(pmap.data_ptr()), M,
                                    int(min_length), _STATS[stat], 0 if side == "above" else 1),
                                   K, lambda L, *a: 0, out, status, False, stream)
@@ -224,7 +261,84 @@ def resolve_planes(plane_labels, period_labels, planes):
     return out
 
 
-def cell_quantiles(ds, q, tas="tas", period=None, method="linear", season=None, leap_days="keep"):
+def _day_labels(time_values):
+    """``(label, ordinal)`` per time step: ``month * 100 + day``, and a day count on which consecutive days differ by 1 -- from
+    datetime64 values (29 February counts; a record whose leap days were removed steps by 2 there) or from the YYYYDDD integers
+    of ``tas_poly`` on the 365-day calendar (``periods._MONTH_ENDS_365``)"""
+    from .periods import _MONTH_ENDS_365
+    t = np.asarray(time_values)
+    if t.dtype.kind == "M":
+        days = t.astype("datetime64[D]")
+        months = days.astype("datetime64[M]")
+        month = months.astype(np.int64) % 12 + 1
+        day = (days - months.astype("datetime64[D]")).astype(np.int64) + 1
+        return month * 100 + day, days.astype(np.int64)
+    if t.dtype.kind in "iu":
+        t = t.astype(np.int64)
+        year, ddd = t // 1000, t % 1000
+        if len(t) and (year.min() < 1 or ddd.min() < 1 or ddd.max() > 365):
+            raise ValueError("integer time values must be YYYYDDD with DDD in 1..365 (what tas_poly writes)")
+        mi = np.searchsorted(_MONTH_ENDS_365, ddd, side="left")
+        return (mi + 1) * 100 + (ddd - np.concatenate([[0], _MONTH_ENDS_365])[mi]), year * 365 + ddd
+    raise ValueError("calendar days need datetime64 or YYYYDDD integer time values, got dtype %s" % t.dtype)
+
+
+def calendar_day_rows(time_values, window=5):
+    """The pooled row lists of a CALENDAR-DAY baseline (ETCCDI's TX90p / TN10p / WSDI / CSDI; xclim's ``percentile_doy``):
+    ``(labels, row_begin, rows)`` as :func:`~climate_toolbox_amd.periods.period_rows` returns them.  A day's label is ``month *
+    100 + day``; the labels come out ascending -- 365 of them, 366 where the record holds a 29 February.  The list of label ``c``
+    holds, for every row ``t`` labelled ``c`` in ascending ``t``, the rows ``t - h .. t + h`` (``h = window // 2``), clipped to
+    ``[0, T)`` and ascending: the window is POSITIONAL, as xclim's is, and a row stands in several lists, which
+    ``engine.quantile_select`` allows.  ``window``: an odd integer >= 1 (1: ``period_rows`` with these labels), else ValueError.
+    ``time_values``: datetime64, or the YYYYDDD integers of ``tas_poly``; CONSECUTIVE DAYS with no gap and no repeat -- for
+    YYYYDDD on the 365-day calendar; on datetime64 the one step allowed beside a day is the two days across a removed 29
+    February (what ``leap_days="drop"`` leaves) -- else ValueError naming the first offending position."""
+    if isinstance(window, (bool, np.bool_)) or not isinstance(window, (int, np.integer)) or window < 1 or window % 2 != 1:
+        raise ValueError("window must be an odd integer >= 1, got %r" % (window,))
+    lab, ordn = _day_labels(time_values)
+    T, h = len(lab), int(window) // 2
+    step = np.diff(ordn)
+    ok = step == 1
+    if np.asarray(time_values).dtype.kind == "M":    # (a removed 29 February: 28 February, then 1 March)
+        ok = ok | ((step == 2) & (lab[:-1] == 228) & (lab[1:] == 301))
+    if not ok.all():
+        i = int(np.flatnonzero(~ok)[0]) + 1
+        raise ValueError("calendar_day_rows needs consecutive days: time[%d] = %r does not follow time[%d] = %r by one day (a %s)"
+                         % (i, np.asarray(time_values)[i], i - 1, np.asarray(time_values)[i - 1], "repeat" if step[i - 1] <= 0 else "gap"))
+    labels, inv = np.unique(lab, return_inverse=True)
+    order = np.argsort(np.asarray(inv).reshape(-1), kind="stable")                      # rows by label, ascending t within a label
+    win = order[:, None] + np.arange(-h, h + 1)[None, :]
+    keep = (win >= 0) & (win < T)
+    counts = np.bincount(np.asarray(inv).reshape(-1)[order], weights=keep.sum(1), minlength=len(labels)).astype(np.int64)
+    row_begin = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+    return labels, row_begin, win[keep].astype(np.int64)
+
+
+def resolve_row_planes(plane_labels, time_values, rows=None):
+    """The plane every DAY reads in a calendar-day baseline, as T indices into ``plane_labels`` (int32): day ``t`` reads the plane
+    labelled with its own ``month * 100 + day`` (``time_values`` as for :func:`calendar_day_rows`).  ``rows``: the rows the
+    periods list (None: every row) -- a listed day without a plane is ValueError naming the date (29 February in the data against
+    a baseline built with ``leap_days="drop"``); a day no period lists needs none and gets -1."""
+    plane_labels = np.asarray(plane_labels)
+    if plane_labels.dtype.kind not in "iu":
+        raise ValueError("calendar-day planes are labelled month * 100 + day (cell_quantiles(period='calendar_day')), got labels of "
+                         "dtype %s" % plane_labels.dtype)
+    lab, _ = _day_labels(time_values)
+    order = np.argsort(plane_labels, kind="stable")
+    pos = np.searchsorted(plane_labels[order], lab)
+    hit = (pos < len(order)) & (plane_labels[order][np.minimum(pos, max(len(order) - 1, 0))] == lab) if len(order) else np.zeros(len(lab), bool)
+    out = np.where(hit, order[np.minimum(pos, max(len(order) - 1, 0))] if len(order) else 0, -1).astype(np.int32)
+    listed = np.arange(len(lab)) if rows is None else np.unique(np.asarray(rows, dtype=np.int64))
+    missing = listed[out[listed] < 0]
+    if len(missing):
+        t = int(missing[0])
+        raise ValueError("day %r (time[%d], calendar day %d) has no threshold plane: the planes are labelled %r"
+                         % (np.asarray(time_values)[t], t, int(lab[t]), plane_labels.tolist() if len(plane_labels) <= 12 else
+                            "%r ... %r (%d planes)" % (plane_labels[:3].tolist(), plane_labels[-3:].tolist(), len(plane_labels))))
+    return out
+
+
+def cell_quantiles(ds, q, tas="tas", period=None, method="linear", season=None, leap_days="keep", window=None):
     """Per-cell quantiles of ``ds[tas]`` kept on the device and NOT aggregated: a :class:`CellThresholds` with one level per ``q``
     and one plane per period -- the baseline of :func:`~climate_toolbox_amd.transformations.tas_relative_spell_aggregate`.
 
@@ -234,7 +348,13 @@ def cell_quantiles(ds, q, tas="tas", period=None, method="linear", season=None, 
               elements with raw order statistics.  A power or a degree-day variable is ValueError.
     period    None: the whole record is one plane (label 0); "year", "month" or a label per day (``periods.period_rows``): one
               plane per label -- month numbers 1..12 over a 30-year baseline give 12 planes of at most 930 days.  A plane of
-              more than ``_lib.QUANT_ROWS_MAX`` days is ValueError.
+              more than ``_lib.QUANT_ROWS_MAX`` days is ValueError.  "calendar_day": one plane per calendar day, labelled ``month *
+              100 + day``, each the quantile of the days pooled over a ``window``-day window centred on every occurrence of that
+              day (:func:`calendar_day_rows`; 30 years x 5 days: 150 entries a plane, 30 x 31: 930) -- the ETCCDI / xclim
+              ``percentile_doy`` baseline of ``tas_relative_spell_aggregate(planes="calendar_day")``.  ``leap_days="drop"``: 365
+              planes; ``"keep"``: 29 February gets a (thin) plane of its own.
+    window    the pooling window of ``period="calendar_day"`` in days, an odd integer >= 1 (default 5); with any other
+              ``period`` it is ValueError.
     method    "linear", "lower" or "higher".
     season, leap_days   as in :func:`~climate_toolbox_amd.transformations.tas_quantile_aggregate`.
 
@@ -246,6 +366,12 @@ def cell_quantiles(ds, q, tas="tas", period=None, method="linear", season=None, 
         raise ValueError("leap_days must be 'keep' or 'drop', got %r" % (leap_days,))
     if method not in ("linear", "lower", "higher"):
         raise ValueError("method must be 'linear', 'lower' or 'higher', got %r" % (method,))
+    calendar = isinstance(period, str) and period == "calendar_day"
+    if window is not None and not calendar:
+        raise ValueError("window= belongs to period='calendar_day', got period=%r" % (period,))
+    window = 5 if window is None else window
+    if calendar and (isinstance(window, (bool, np.bool_)) or not isinstance(window, (int, np.integer)) or window < 1 or window % 2 != 1):
+        raise ValueError("window must be an odd integer >= 1, got %r" % (window,))
     raw = list(np.atleast_1d(np.asarray(q, dtype=object)))
     if len(raw) < 1:
         raise ValueError("q must be a non-empty sequence of numbers in [0, 1], got %r" % (q,))
@@ -268,6 +394,12 @@ def cell_quantiles(ds, q, tas="tas", period=None, method="linear", season=None, 
     time_values = np.asarray(ds.coords["time"].values)
     if period is None:
         labels, row_begin, rows = np.array([0]), np.array([0, len(time_values)]), np.arange(len(time_values))
+    elif calendar:
+        labels, row_begin, rows = calendar_day_rows(time_values, window)
+        longest = int(np.diff(row_begin).max()) if len(labels) else 0
+        if longest > _lib.QUANT_ROWS_MAX:
+            raise ValueError("a calendar-day plane pools %d days (window=%d over the record's years); at most %d fit a plane"
+                             % (longest, window, _lib.QUANT_ROWS_MAX))
     else:
         labels, row_begin, rows = periods.period_rows(time_values, period)
     lat, lon = np.asarray(ds.coords["lat"].values), np.asarray(ds.coords["lon"].values)

@@ -480,12 +480,13 @@ def _spell_totals(ds, variable, aggwt, agglev, weights, backup_aggwt, lists, P, 
 
 
 def _cell_spell_totals(ds, variable, aggwt, agglev, weights, backup_aggwt, lists, P, thresholds, plane_of_period, min_length, stat, side,
-                       season, grid, time_values, cells="all"):
+                       season, grid, time_values, cells="all", plane_of_row=None):
     """Period totals of the spell / exceedance statistic ``stat`` of ``variable`` against the PER-CELL thresholds of a
     ``relative.CellThresholds`` (``wagg_cell_spells_*``, up to 64 levels a launch) through :func:`_grouped_totals`.  ``variable``:
     as for :func:`_bin_totals`; ``grid``: the dataset's own ``(lat, lon)`` labels (also without a season), to which the
     thresholds' grid is joined by exact labels in the field's stored cell order, converted to the field's dtype once; with
-    ``cells="referenced"`` the packed columns are taken on the device.  ``plane_of_period``: the plane index of every period.
+    ``cells="referenced"`` the packed columns are taken on the device.  ``plane_of_period``: the plane index of every period; or
+    None with ``plane_of_row``: the plane index of every day (``wagg_row_cell_spells_*``: calendar-day thresholds).
     The kernel's offset is the field's shift minus the thresholds' own -- exactly 0 when both come from one Kelvin variable.  A
     cell whose threshold is NaN is NaN there, which the contraction treats as any NaN of a field.  ``stack`` is the (K, P | R,
     R | P) results in the levels' order."""
@@ -497,15 +498,17 @@ def _cell_spell_totals(ds, variable, aggwt, agglev, weights, backup_aggwt, lists
         if "thr" not in state:                       # (behind _gridded_field's checks: once, whatever the number of launches)
             thr = thresholds.stored(grid[0], grid[1], ds._src_dims[variable], ds._lon_perms.get(variable), X.dtype, X.device)
             state["thr"] = thr if cells_of_pos is None else _engine.take_axis(thr, 2, cells_of_pos)
-            state["map"] = _engine.require_gpu().from_numpy(np.ascontiguousarray(plane_of_period, dtype=np.int32)).to(X.device)
+            pmap = plane_of_period if plane_of_row is None else plane_of_row
+            state["map"] = _engine.require_gpu().from_numpy(np.ascontiguousarray(pmap, dtype=np.int32)).to(X.device)
         return state["thr"], state["map"]
 
     def launches():
         for k0 in range(0, thresholds.K, CELL_SPELL_MAX):
             def reduce(X, H, rb, rw, offset, cells=None, k0=k0, **kw):
                 thr, pmap = stored(X, cells)
-                return cell_spell_reduce(X, rb, rw, offset - thresholds.shift, thr[k0:k0 + CELL_SPELL_MAX], plane_of_period=pmap,
-                                         min_length=min_length, stat=stat, side=side, **kw)
+                which = {"plane_of_period": pmap} if plane_of_row is None else {"plane_of_row": pmap}
+                return cell_spell_reduce(X, rb, rw, offset - thresholds.shift, thr[k0:k0 + CELL_SPELL_MAX], min_length=min_length,
+                                         stat=stat, side=side, **which, **kw)
             yield reduce
 
     return _grouped_totals(ds, variable, aggwt, agglev, weights, backup_aggwt, lists, P, season, None if season is None else grid,

@@ -648,9 +648,16 @@ def tas_relative_spell_aggregate(ds, thresholds, aggwt, agglev, weights, min_len
                 :func:`tas_quantile_aggregate` does.  More than 64 levels go in several launches.
     planes      which plane of ``thresholds`` a period reads.  None: there is one plane, or the plane labels equal the period
                 labels one to one.  "month": a period labelled ``year * 100 + month`` reads the plane labelled ``month``.  A
-                callable maps a period label to a plane label.  A period without a plane is ValueError naming the label.  EVERY
-                PERIOD READS ONE PLANE: thresholds that change inside a period (calendar-day percentiles within a year) are not
-                built.
+                callable maps a period label to a plane label.  A period without a plane is ValueError naming the label.  With
+                these, EVERY PERIOD READS ONE PLANE.  "calendar_day": every DAY of the dataset reads the plane labelled with its
+                own ``month * 100 + day`` -- the baseline of ``cell_quantiles(period="calendar_day", window=5)``, ETCCDI's TX90p /
+                TN10p / WSDI / CSDI as published and xclim's ``percentile_doy`` -- so the threshold changes from day to day inside a
+                period (``wagg_row_cell_spells_*``; the kernel reads the listed rows' bytes 1 + K times).  A listed day without
+                a plane is ValueError naming the date (29 February in the data against a baseline built with
+                ``leap_days="drop"`` while this call keeps leap days); days no period lists need none.  A cell's value is NaN
+                if a counted day of the period had a NaN threshold; a cell with no counted day in a period counts 0.  STILL NOT
+                BUILT: the percent-of-days form (divide by the period's days), ETCCDI's in-base bootstrap, runs that continue
+                across a period boundary.
     stat        "days", "events", "longest" as in :func:`tas_spell_aggregate` (same ``min_length`` rules), or "amount": the sum of
                 the variable over the hot days, "excess": the sum of (variable - threshold) over them (``side="below"``:
                 threshold - variable); the two sums have no run counter, and a ``min_length`` other than 1 or the default is
@@ -679,19 +686,26 @@ def tas_relative_spell_aggregate(ds, thresholds, aggwt, agglev, weights, min_len
         if min_length not in (1, 3):
             raise ValueError("stat=%r does not use min_length (leave it out, or pass 1), got %r" % (stat, min_length))
         min_length = 1
-    if not (planes is None or planes == "month" or callable(planes)):
-        raise ValueError("planes must be None, 'month' or a callable, got %r" % (planes,))
+    if not (planes is None or (isinstance(planes, str) and planes in ("month", "calendar_day")) or callable(planes)):
+        raise ValueError("planes must be None, 'month', 'calendar_day' or a callable, got %r" % (planes,))
     if stat == "amount" and thresholds.shift != 0.0:
         raise ValueError("stat='amount' needs thresholds in final units (thresholds.shift == 0, got %r): one offset serves the comparison "
                          "and the sum, so the amount against shifted thresholds would be a sum of raw values; stat='excess' has no such "
                          "limit" % (thresholds.shift,))
     re, var, weights, time_values, labels, _, lists = _period_setup("tas_relative_spell_aggregate", "a relative spell count", ds, tas,
                                                                     weights, period, season, cells, leap_days)
-    pmap = resolve_planes(thresholds.labels, labels, planes)
+    rmap = pmap = None
+    if isinstance(planes, str) and planes == "calendar_day":
+        from .periods import period_rows
+        from .relative import resolve_row_planes
+        rmap = resolve_row_planes(thresholds.labels, time_values, rows=period_rows(time_values, period)[2])
+    else:
+        pmap = resolve_planes(thresholds.labels, labels, planes)
     grid = (np.asarray(ds.coords["lat"].values), np.asarray(ds.coords["lon"].values))       # (the grid's own labels: `re` carries the table's)
     from . import seasons
     res, rdims, coords, was_xr = seasons._cell_spell_totals(re, tas, aggwt, agglev, weights, backup_aggwt, lists, len(labels), thresholds,
-                                                            pmap, min_length, stat, side, season, grid, time_values, cells=cells)
+                                                            pmap, min_length, stat, side, season, grid, time_values, cells=cells,
+                                                            plane_of_row=rmap)
     rdims, coords = _time_as_period(rdims, coords, labels)
     out = _agg._as_dataset({varname: res}, ("threshold",) + tuple(rdims), dict(coords, threshold=thresholds.levels.copy()), was_xr)
     if stat in ("amount", "excess"):

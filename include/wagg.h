@@ -87,7 +87,8 @@ int wagg_version(void);                 /* 10000*major + 100*minor + patch; 0.4.
                                            0.13.0: spell statistics (wagg_spell_reduce_*);
                                            0.14.0: rolling-window extremes (wagg_rolling_reduce_*);
                                            0.15.0: period quantiles (wagg_quantile_select_*);
-                                           0.16.0: spells against per-cell thresholds (wagg_cell_spells_*) */
+                                           0.16.0: spells against per-cell thresholds (wagg_cell_spells_*);
+                                           0.17.0: ... with a threshold plane per row (wagg_row_cell_spells_*) */
 int wagg_device_count(void);            /* number of visible HIP devices (0 if none), never <0  */
 /* Time-axis sharding rule of the multi-GPU form (one process per GPU; climate_toolbox_amd/timeshard.py):
  * rank `rank` of `world` owns rows [*start, *stop) of T; the first T mod world ranks hold one row more. */
@@ -1016,7 +1017,8 @@ int wagg_quantile_select_f64(const double *X_dev, int64_t T, int64_t n, int64_t 
  * 1 <= n_thr <= WAGG_CELL_SPELL_MAX, in one launch, taken in groups of WAGG_CELL_SPELL_GROUP.
  *   thr_dev            a DEVICE array of the element type, logically (n_thr, M, n):  thr[k][m][j] = thr_dev[k * thr_kstride +
  *                      m * ldt + j];  ldt >= n, thr_kstride >= M * ldt, M >= 1.  Read once per block, ahead of the rows.
- *   plane_of_period_dev   a DEVICE int32[P]: period p reads the ONE plane m = plane_of_period_dev[p].  NULL is allowed only for
+ *   plane_of_period_dev   a DEVICE int32[P]: period p reads the ONE plane m = plane_of_period_dev[p] (a plane per ROW -- calendar-day
+ *                      thresholds inside a period -- is wagg_row_cell_spells_*, below).  NULL is allowed only for
  *                      M == 1 (m = 0) and M == P (m = p); otherwise WAGG_EINVAL.  Without WAGG_PERIOD_ROWS_CHECKED the library's
  *                      blocking look at the lists also checks 0 <= m < M (WAGG_EINVAL).  With the flag the kernel confines itself:
  *                      a period whose m is out of range writes NaN in every plane and sets bit 2 of status_dev.
@@ -1057,6 +1059,39 @@ int wagg_cell_spells_f64(const double *X_dev, int64_t T, int64_t n, int64_t ldx,
                          const int32_t *plane_of_period_dev, int32_t M, int min_length, int stat, int below, int flags,
                          double *out_dev, int64_t ldo, int64_t out_pstride, int32_t *status_dev, void *work_dev, int64_t work_bytes,
                          void *stream);
+
+/* ---- ... with a threshold plane PER ROW: calendar-day thresholds inside a period (0.17.0) ---------------------------------------
+ * wagg_cell_spells_* reads one plane per period.  ETCCDI's TX90p / TN10p / WSDI / CSDI compare each day with the percentile of its
+ * own calendar day, so inside an annual period the plane changes from row to row.  wagg_row_cell_spells_* take
+ * wagg_cell_spells_*'s arguments with
+ *   plane_of_row_dev   a DEVICE int32[T], never NULL, in place of plane_of_period_dev: entry i of period p's list, with row
+ *                      t = rows[i] in [0, T), reads plane m = plane_of_row_dev[t] (one scalar per row, as doy_dev[t] is).
+ * THE DEFINITION is wagg_cell_spells_*'s text with these changes.  HOT is  X[t, j] >= c  (below: < c)  with  c = ceilT((double)
+ * thr[k][m][j] - offset)  formed per row by the same rule; with offset == 0, c is the threshold itself.  Runs, gaps, seasons, NaN
+ * days, the truncation at period boundaries and bit 0 of status_dev are unchanged.  A list is never split; work_dev / work_bytes
+ * are ignored.  WAGG_CELL_SPELL_EXCESS subtracts the raw threshold OF THAT ROW; amount and excess stay sequential fp64 sums in list
+ * order.  NaN THRESHOLDS: out[k][p][j] is NaN if any COUNTED entry of period p had a NaN threshold for cell j and level k -- a
+ * counted entry being one whose row lies in the field and on which the cell is in season.  No threshold (and no field value) is
+ * loaded for a 16-byte piece none of whose cells is in season; it still ends the runs.  CONSEQUENCE: a cell with no counted entry
+ * in a period gives 0, where wagg_cell_spells_* writes NaN for a NaN threshold even then.  PLANE INDICES: without
+ * WAGG_PERIOD_ROWS_CHECKED the library's blocking look also checks plane_of_row_dev[rows[i]] in [0, M) for every listed entry whose
+ * row lies in the field (WAGG_EINVAL before any launch); with the flag, a block that meets an out-of-range index reads no threshold
+ * for that row, writes NaN for its whole period in every plane and sets bit 2 of status_dev.  Rows that no list names need no valid
+ * plane.  The kernel reads (1 + n_thr) x the bytes of the listed rows: every counted row reads its own piece of n_thr planes
+ * (tests/cell_spell_rows_ref.py is the NumPy twin).  STILL NOT BUILT: runs that continue across a period boundary, the
+ * percent-of-days form, ETCCDI's in-base bootstrap.                                                                                */
+int wagg_row_cell_spells_f32(const float *X_dev, int64_t T, int64_t n, int64_t ldx, const int32_t *row_begin_dev,
+                              const int32_t *rows_dev, int32_t P, int64_t n_rows, const int32_t *doy_dev, const int32_t *win_dev,
+                              double offset, const float *thr_dev, int n_thr, int64_t ldt, int64_t thr_kstride,
+                              const int32_t *plane_of_row_dev, int32_t M, int min_length, int stat, int below, int flags,
+                              float *out_dev, int64_t ldo, int64_t out_pstride, int32_t *status_dev, void *work_dev,
+                              int64_t work_bytes, void *stream);
+int wagg_row_cell_spells_f64(const double *X_dev, int64_t T, int64_t n, int64_t ldx, const int32_t *row_begin_dev,
+                              const int32_t *rows_dev, int32_t P, int64_t n_rows, const int32_t *doy_dev, const int32_t *win_dev,
+                              double offset, const double *thr_dev, int n_thr, int64_t ldt, int64_t thr_kstride,
+                              const int32_t *plane_of_row_dev, int32_t M, int min_length, int stat, int below, int flags,
+                              double *out_dev, int64_t ldo, int64_t out_pstride, int32_t *status_dev, void *work_dev,
+                              int64_t work_bytes, void *stream);
 
 /* ---- packed rows: only the quads a segment table references, as a device matrix (0.9.0) ---------------------------------------
  * A single segment-table plan with a whole-line chunking (wagg_plan_info.lines) knows the distinct aligned 4-cell QUADS of a
