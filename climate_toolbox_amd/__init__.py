@@ -1,7 +1,7 @@
 """MI355X-native weighted grid->region aggregation engine: a drop-in for the aggregation path of
 ClimateImpactLab/climate_toolbox (``climate_toolbox.aggregations``).  See DESIGN.md."""
 
-__version__ = "0.17.0"
+__version__ = "0.18.0"
 
 from .aggregations import (  # noqa: F401
     weighted_aggregate_grid_to_regions,

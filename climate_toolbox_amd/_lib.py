@@ -53,6 +53,7 @@ EXPORTS = (
     "wagg_hinge_reduce_f32", "wagg_hinge_reduce_f64", "wagg_hinge_work_bytes",
     "wagg_exposure_reduce_f32", "wagg_exposure_reduce_f64", "wagg_exposure_work_bytes",
     "wagg_spell_reduce_f32", "wagg_spell_reduce_f64", "wagg_spell_work_bytes",
+    "wagg_spell_span_f32", "wagg_spell_span_f64", "wagg_spell_span_work_bytes",
     "wagg_rolling_reduce_f32", "wagg_rolling_reduce_f64", "wagg_rolling_work_bytes",
     "wagg_quantile_select_f32", "wagg_quantile_select_f64",
     "wagg_cell_spells_f32", "wagg_cell_spells_f64", "wagg_row_cell_spells_f32", "wagg_row_cell_spells_f64",
@@ -318,11 +319,13 @@ def load():
                                      C.c_int, vp, C.c_int64, C.c_int64, vp, vp, C.c_int64, vp]
     L.wagg_bin_days_work_bytes.argtypes = [C.c_int64, C.c_int32, C.c_int64, C.c_int]
     L.wagg_bin_days_work_bytes.restype = C.c_int64
-    for name in ("wagg_spell_reduce_f32", "wagg_spell_reduce_f64"):
+    for name in ("wagg_spell_reduce_f32", "wagg_spell_reduce_f64", "wagg_spell_span_f32", "wagg_spell_span_f64"):
         getattr(L, name).argtypes = [vp, C.c_int64, C.c_int64, C.c_int64, vp, vp, C.c_int32, C.c_int64, vp, vp, C.c_double, f64p, C.c_int,
                                      C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int64, C.c_int64, vp, vp, C.c_int64, vp]
     L.wagg_spell_work_bytes.argtypes = [C.c_int64, C.c_int32, C.c_int64, C.c_int]
     L.wagg_spell_work_bytes.restype = C.c_int64
+    L.wagg_spell_span_work_bytes.argtypes = [C.c_int64, C.c_int32, C.c_int64, C.c_int]
+    L.wagg_spell_span_work_bytes.restype = C.c_int64
     for name in ("wagg_rolling_reduce_f32", "wagg_rolling_reduce_f64"):
         getattr(L, name).argtypes = [vp, C.c_int64, C.c_int64, C.c_int64, vp, vp, C.c_int32, C.c_int64, vp, vp, C.c_double, i32p, C.c_int,
                                      C.c_int, C.c_int, C.c_int, vp, C.c_int64, C.c_int64, vp, vp, C.c_int64, vp]
@@ -354,7 +357,7 @@ def load():
         fn = getattr(L, name)
         if name not in ("wagg_last_error", "wagg_scratch_bytes", "wagg_period_reduce_work_bytes", "wagg_season_reduce_work_bytes",
                         "wagg_edd_ladder_work_bytes", "wagg_bin_days_work_bytes", "wagg_hinge_work_bytes",
-                        "wagg_exposure_work_bytes", "wagg_spell_work_bytes", "wagg_rolling_work_bytes"):
+                        "wagg_exposure_work_bytes", "wagg_spell_work_bytes", "wagg_spell_span_work_bytes", "wagg_rolling_work_bytes"):
             fn.restype = C.c_int
     _lib = L
     return L

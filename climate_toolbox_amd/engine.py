@@ -1149,7 +1149,7 @@ _SPELL_STATS = {"days": _lib.SPELL_DAYS, "events": _lib.SPELL_EVENTS, "longest":
 
 
 def spell_reduce(X, row_begin, rows, offset, thresholds, min_length=1, stat="days", side="above", doy=None, windows=None, checked=False,
-                 out=None, status=None, stream=None):
+                 out=None, status=None, stream=None, span="period"):
     """Runs of consecutive days past every threshold of a list, per period, in ONE launch (``wagg_spell_reduce_*``).  Entry ``i``
     of period ``p``'s list is hot for cell ``j`` and threshold ``k`` when its row ``t`` lies in the field, the cell is in season
     on ``doy[t]`` and ``X[t, j] + offset >= thresholds[k]`` (``side="above"``) or ``< thresholds[k]`` (``"below"``); a run is a
@@ -1163,7 +1163,22 @@ def spell_reduce(X, row_begin, rows, offset, thresholds, min_length=1, stat="day
     offset)``, so an fp32 field is classified as its exact values would be in fp64; NaN is never hot.  There is no workspace:
     a run does not add across the parts of a list, so a period's list is never split.  Returns ``(counts, status)``: the
     (n_thr, P, n) tensor of ``X``'s dtype (exact in fp32 up to 2^24) and the status word (bit 0: an in-season value was
-    +-inf, hot or not)."""
+    +-inf, hot or not).
+
+    ``span="record"`` (``wagg_spell_span_*``; anything but ``"period"`` or ``"record"`` is ValueError): RUNS ARE NOT
+    TRUNCATED.  The CHAIN is the concatenation of the periods' lists in period order.  Entry ``i`` is hot as above; it JOINS entry
+    ``i - 1`` of the chain when ``rows[i] == rows[i - 1] + 1``, whether or not a period boundary or several empty periods lie
+    between them (empty lists are transparent); a RUN is a maximal stretch of hot, joined entries of the chain; the RUNNING LENGTH
+    ``r_i`` is the entry's position within its run, from 1, or 0 when cold, and is carried over boundaries; ``l`` is the run's
+    WHOLE LENGTH.  With ``L = min_length``, ``out[k, p, j]`` is, for ``"days"``: the hot entries of ``p``'s list whose run has
+    ``l >= L`` (every day counts in its own period; whether it counts is decided by the whole run); ``"events"``: the entries of
+    ``p``'s list with ``r_i == L`` (a run counts once, in the period in which it reaches ``min_length``); ``"longest"``: the
+    greatest ``r_i`` over the entries of ``p``'s list, 0 for an empty list (a spell counts in a period for as long as it has
+    lasted by then, reaching back to its start wherever that lies).  Where no run crosses a boundary the result is
+    ``span="period"``'s bit for bit; summed (``"longest"``: maximised) over the periods it is the ``span="period"`` result of
+    the chain taken as one list.  One launch whose blocks each walk the whole record: the grid has no period dimension."""
+    if span not in ("period", "record"):
+        raise ValueError("span must be 'period' or 'record', got %r" % (span,))
     X = _check_X(X, "TG")
     thr = np.ascontiguousarray(np.atleast_1d(thresholds), dtype=np.float64)
     if thr.ndim != 1 or not 1 <= len(thr) <= _lib.SPELL_MAX:
@@ -1178,7 +1193,8 @@ def spell_reduce(X, row_begin, rows, offset, thresholds, min_length=1, stat="day
         raise ValueError("min_length must be an integer in 1..%d, got %r" % (_lib.SPELL_MIN_LENGTH_MAX, min_length))
     if stat == "longest" and min_length != 1:
         raise ValueError("stat='longest' does not use min_length: it must be 1, got %r" % (min_length,))
-    return _grouped_reduce("wagg_spell_reduce", (X,), row_begin, rows, doy, windows, checked, offset,
+    return _grouped_reduce("wagg_spell_reduce" if span == "period" else "wagg_spell_span", (X,), row_begin, rows, doy, windows,
+                           checked, offset,
                            (_np_ptr(thr, C.c_double), len(thr), int(min_length), _SPELL_STATS[stat], 0 if side == "above" else 1),
                            len(thr), lambda L, *a: L.wagg_spell_work_bytes(*a), out, status, False, stream)
 

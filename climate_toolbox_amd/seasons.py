@@ -464,16 +464,17 @@ def _hinge_totals(ds, variable, aggwt, agglev, weights, backup_aggwt, lists, P, 
 
 
 def _spell_totals(ds, variable, aggwt, agglev, weights, backup_aggwt, lists, P, thresholds, min_length, stat, side, season, grid,
-                  time_values, cells="all"):
+                  time_values, cells="all", span="period"):
     """Period totals of the spell statistic ``stat`` of ``variable`` at EVERY threshold (``wagg_spell_reduce_*``, up to 64
     thresholds a launch) through :func:`_grouped_totals`.  ``variable``: as for :func:`_bin_totals` (the thresholds are in degrees
     C for a shifted one).  A run ends with its period's list: the regional value is the weighted mean of per-cell counts of runs
-    truncated there.  ``stack`` is the (n_thr, P | R, R | P) results in the thresholds' order."""
+    truncated there -- with ``span="record"`` (``wagg_spell_span_*``) of runs that continue across the boundaries, as
+    ``engine.spell_reduce`` defines them.  ``stack`` is the (n_thr, P | R, R | P) results in the thresholds' order."""
     def launches():
         for k0 in range(0, len(thresholds), _SPELL_MAX):
             part = [float(t) for t in thresholds[k0:k0 + _SPELL_MAX]]
             yield lambda X, H, rb, rw, offset, **kw: _engine.spell_reduce(X, rb, rw, offset, part, min_length=min_length, stat=stat,
-                                                                          side=side, **kw)
+                                                                          side=side, span=span, **kw)
 
     return _grouped_totals(ds, variable, aggwt, agglev, weights, backup_aggwt, lists, P, season, grid, time_values, cells, "spell count",
                            "spells", _plain_variable, launches())

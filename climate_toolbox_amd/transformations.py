@@ -570,7 +570,7 @@ def _spell_thresholds(thresholds):
 
 
 def tas_spell_aggregate(ds, thresholds, aggwt, agglev, weights, min_length=3, stat="days", side="above", tas="tas", varname="tas-spell",
-                        backup_aggwt="areawt", period="year", season=None, cells="all", leap_days="keep"):
+                        backup_aggwt="areawt", period="year", season=None, cells="all", leap_days="keep", span="period"):
     """Spell statistics of a cell's daily temperature -- runs of consecutive days past a threshold -- per period (and growing
     season), aggregated to regions: heat-wave and cold-spell days, the number of such events and the longest run (the ETCCDI /
     xclim spell indices; ``tas="tasmax"``, threshold 35 C, ``min_length=3`` is the usual heat wave).  The one temperature
@@ -582,6 +582,7 @@ def tas_spell_aggregate(ds, thresholds, aggwt, agglev, weights, min_length=3, st
     and so does the end of the period: RUNS ARE TRUNCATED AT PERIOD BOUNDARIES (a heat wave over New Year's Eve counts as one
     run in each of the two years; with ``period="month"`` every month starts anew; with labels that join the Januaries of
     several years, a run never reaches from one January into the next).  With ``leap_days="drop"`` 28 February and 1 March are consecutive.
+    That is ``span="period"``, the default; ``span="record"`` (below) lets the runs continue across the boundaries.
 
     thresholds  a non-empty sequence of finite numbers in any order, duplicates allowed, else ValueError; in degrees C when
                 ``ds[tas]`` carries the Kelvin shift of ``convert_kelvin_to_celsius``, otherwise in the field's own units.  More
@@ -597,13 +598,35 @@ def tas_spell_aggregate(ds, thresholds, aggwt, agglev, weights, min_length=3, st
                 (``tas_poly``) or a degree-day variable is ValueError.
     period      "year", "month" or a label per day; required (None is ValueError).
     season, cells, leap_days   exactly as in :func:`tas_bins_aggregate`.
+    span        "period" (runs truncated at period boundaries, as above) or "record", else ValueError.  ``span="record"``
+                (``wagg_spell_span_*``) counts SPELLS THAT RUN ACROSS PERIOD BOUNDARIES.  The CHAIN is the concatenation
+                of the periods' day lists in period order.  A day is hot as above; it JOINS the chain's day before when it is the
+                next day of the record (under ``leap_days="drop"`` 31 December and 1 January of consecutive years join, as 28
+                February and 1 March do), whether or not a period boundary or several empty periods lie between them; a RUN is
+                a maximal stretch of hot, joined days of the chain; the RUNNING LENGTH ``r_i`` of a day is its position within
+                its run, from 1, or 0 when cold, and is carried over boundaries; ``l`` is the run's WHOLE LENGTH.  With ``L =
+                min_length``: "days" counts the hot days of the period whose run has ``l >= L`` -- every day in its own period,
+                whether it counts being decided by the whole run; "events" counts the days of the period with ``r_i == L`` -- a
+                run counts once, in the period in which it reaches ``min_length`` (``L = 1``: in which it starts); "longest"
+                is the greatest ``r_i`` over the days of the period, 0 for an empty one -- a spell counts in a period for as
+                long as it has lasted by then, reaching back to its start wherever that lies: a year wholly inside one dry
+                spell reports at least its own length, a spell from 20 December to 10 January gives 12 and 22.  Where no run
+                crosses a boundary the result is ``span="period"``'s.  ETCCDI's CDD, the longest dry spell, is
+                ``tas="pr", thresholds=[1.0], stat="longest", side="below", span="record"`` for pr in mm/day, and CWD the
+                same with ``side="above"``; both are defined on spells that run through New Year.  Joins are found only
+                between neighbours in the chain, so the mode means something for periods whose lists follow each other in
+                time: "year", "month", ascending labels.  With labels that pool the Januaries of all years nothing joins
+                across the lists and the result equals ``span="period"``; that is not an error.  The per-cell-threshold call
+                (:func:`tas_relative_spell_aggregate`) keeps truncating.
 
     The regional value is the weighted mean of the per-cell counts (for "longest": of the per-cell longest runs).  Returns one
     Dataset with the variable ``varname`` of dims ``("threshold", "period", agglev)`` (the last two in the order the period call
     gives them), the coordinate ``threshold`` = the thresholds as float64 in the caller's order, ``attrs["units"]`` = ``"days"``
-    (days, longest) or ``"1"`` (events) and ``attrs["min_length"]`` (1 for "longest"), ``attrs["stat"]``, ``attrs["side"]``;
-    ``results_on_device()`` is honoured."""
+    (days, longest) or ``"1"`` (events) and ``attrs["min_length"]`` (1 for "longest"), ``attrs["stat"]``, ``attrs["side"]``,
+    ``attrs["span"]``; ``results_on_device()`` is honoured."""
     t = _spell_thresholds(thresholds)
+    if span not in ("period", "record"):
+        raise ValueError("span must be 'period' or 'record', got %r" % (span,))
     if stat not in ("days", "events", "longest"):
         raise ValueError("stat must be 'days', 'events' or 'longest', got %r" % (stat,))
     if side not in ("above", "below"):
@@ -619,13 +642,14 @@ def tas_spell_aggregate(ds, thresholds, aggwt, agglev, weights, min_length=3, st
                                                                      season, cells, leap_days)
     from . import seasons
     res, rdims, coords, was_xr = seasons._spell_totals(re, tas, aggwt, agglev, weights, backup_aggwt, lists, len(labels), t, min_length,
-                                                       stat, side, season, grid, time_values, cells=cells)
+                                                       stat, side, season, grid, time_values, cells=cells, span=span)
     rdims, coords = _time_as_period(rdims, coords, labels)
     out = _agg._as_dataset({varname: res}, ("threshold",) + tuple(rdims), dict(coords, threshold=t.copy()), was_xr)
     out[varname].attrs["units"] = "1" if stat == "events" else "days"
     out[varname].attrs["min_length"] = min_length
     out[varname].attrs["stat"] = stat
     out[varname].attrs["side"] = side
+    out[varname].attrs["span"] = span
     return out
 
 

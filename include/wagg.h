@@ -88,7 +88,8 @@ int wagg_version(void);                 /* 10000*major + 100*minor + patch; 0.4.
                                            0.14.0: rolling-window extremes (wagg_rolling_reduce_*);
                                            0.15.0: period quantiles (wagg_quantile_select_*);
                                            0.16.0: spells against per-cell thresholds (wagg_cell_spells_*);
-                                           0.17.0: ... with a threshold plane per row (wagg_row_cell_spells_*) */
+                                           0.17.0: ... with a threshold plane per row (wagg_row_cell_spells_*);
+                                           0.18.0: spells that run across period boundaries (wagg_spell_span_*) */
 int wagg_device_count(void);            /* number of visible HIP devices (0 if none), never <0  */
 /* Time-axis sharding rule of the multi-GPU form (one process per GPU; climate_toolbox_amd/timeshard.py):
  * rank `rank` of `world` owns rows [*start, *stop) of T; the first T mod world ranks hold one row more. */
@@ -932,6 +933,53 @@ int wagg_spell_reduce_f64(const double *X_dev, int64_t T, int64_t n, int64_t ldx
                           void *stream);
 int64_t wagg_spell_work_bytes(int64_t n, int32_t P, int64_t n_rows, int n_thr);
 
+/* ---- spells that run across period boundaries (0.18.0) -----------------------------------------------------------------------
+ * wagg_spell_reduce_*'s three statistics with the runs NOT truncated at the end of a period's list: CDD / CWD (the longest dry
+ * / wet spell, defined on spells that run through New Year), a December-January heat wave with min_length = 6, every month
+ * end of a monthly call.  The argument list, the constants (WAGG_SPELL_*), the comparison rule, the season and the status word
+ * are wagg_spell_reduce_*'s; wagg_spell_span_work_bytes is 0 and work_dev / work_bytes are ignored.  THE DEFINITION:
+ * The CHAIN is the concatenation of the periods' lists in period order: the entries rows[row_begin[0] : row_begin[P]], row_begin
+ * confined to [0, n_rows] and made ascending as wagg_spell_reduce_* confines it.  For cell j and threshold k:
+ *   HOT     entry i is hot exactly as in wagg_spell_reduce_*: t = rows[i] lies in [0, T), cell j is in season on doy[t] (when a
+ *           season is given) and the raw X[t, j] passes against ceilT(thresholds[k] - offset).  NaN is never hot.
+ *   JOINS   entry i joins entry i - 1 when rows[i] == rows[i - 1] + 1.  It does not matter whether a period boundary, or several
+ *           empty periods, lie between them: empty lists are transparent.
+ *   RUN     a maximal stretch of hot, joined entries of the chain.
+ *   r_i     the RUNNING LENGTH at entry i: its position within its run, starting at 1, or 0 when cold.  It is carried over
+ *           boundaries.
+ *   l       the run's WHOLE LENGTH.
+ * With L = min_length, out[k][p][j] is
+ *   WAGG_SPELL_DAYS      the hot entries of p's list whose run has l >= L.  Every day is counted in its own period; whether it
+ *                        counts is decided by the whole run.
+ *   WAGG_SPELL_EVENTS    the entries of p's list with r_i == L.  A run counts once, in the period in which it reaches
+ *                        min_length; for L = 1 that is the period in which it starts.
+ *   WAGG_SPELL_LONGEST   the greatest r_i over the entries of p's list, and 0 for an empty list.  A spell counts in a period for
+ *                        as long as it has lasted by then, reaching back to its start wherever that lies: a year wholly inside
+ *                        one dry spell reports at least its own length, a spell from 20 December to 10 January gives 12 and 22.
+ *                        min_length must be 1.
+ * THE LAWS that follow: where no run crosses a boundary, all three equal wagg_spell_reduce_* bit for bit; the sum over p of DAYS
+ * and of EVENTS, and the greatest LONGEST over p, equal wagg_spell_reduce_*'s single-period result on the chain taken as one
+ * list; LONGEST is never below the truncating value.  Joins are found only between neighbours in the chain, so the mode means
+ * something for periods whose lists follow each other in time (years, months, ascending labels); with labels that pool the
+ * Januaries of all years nothing joins across lists and the result is wagg_spell_reduce_*'s.
+ * One launch of column block x threshold group blocks -- NO period dimension: a block walks the whole record in order, which is
+ * the cost of the mode (csrc/wagg_spells_span.hip).  DAYS credits the days of a run that lie in earlier periods by a
+ * read-modify-write of what the same thread stored there in this launch: no atomics, no scratch, nothing read from out_dev that
+ * the launch did not write; stream-ordered and capturable.  tests/spell_span_ref.py is the NumPy restatement.  (The names carry no
+ * _reduce: every wagg_*_reduce_f32 / _f64 export is a family of tests/rowlist_layout.py's case table; this call's pitched and
+ * poisoned out_dev is checked in tests/test_gpu_spell_span.py.)                                                                  */
+int wagg_spell_span_f32(const float *X_dev, int64_t T, int64_t n, int64_t ldx, const int32_t *row_begin_dev,
+                               const int32_t *rows_dev, int32_t P, int64_t n_rows, const int32_t *doy_dev, const int32_t *win_dev,
+                               double offset, const double *thresholds, int n_thr, int min_length, int stat, int below, int flags,
+                               float *out_dev, int64_t ldo, int64_t out_pstride, int32_t *status_dev, void *work_dev,
+                               int64_t work_bytes, void *stream);
+int wagg_spell_span_f64(const double *X_dev, int64_t T, int64_t n, int64_t ldx, const int32_t *row_begin_dev,
+                               const int32_t *rows_dev, int32_t P, int64_t n_rows, const int32_t *doy_dev, const int32_t *win_dev,
+                               double offset, const double *thresholds, int n_thr, int min_length, int stat, int below, int flags,
+                               double *out_dev, int64_t ldo, int64_t out_pstride, int32_t *status_dev, void *work_dev,
+                               int64_t work_bytes, void *stream);
+int64_t wagg_spell_span_work_bytes(int64_t n, int32_t P, int64_t n_rows, int n_thr);
+
 /* ---- rolling-window extremes: the greatest / least running sum or mean over W days, per period and season (0.14.0) -------------
  * TXx / TNn (W = 1), the hottest or coldest N-day mean, Rx1day / Rx5day: the extreme over a period of the sum (or mean) of W
  * consecutive days, for windows[k] days,  k = 0 .. n_win - 1,  1 <= n_win <= WAGG_ROLL_MAX_WINDOWS,  1 <= windows[k] <=
@@ -1078,8 +1126,8 @@ int wagg_cell_spells_f64(const double *X_dev, int64_t T, int64_t n, int64_t ldx,
  * row lies in the field (WAGG_EINVAL before any launch); with the flag, a block that meets an out-of-range index reads no threshold
  * for that row, writes NaN for its whole period in every plane and sets bit 2 of status_dev.  Rows that no list names need no valid
  * plane.  The kernel reads (1 + n_thr) x the bytes of the listed rows: every counted row reads its own piece of n_thr planes
- * (tests/cell_spell_rows_ref.py is the NumPy twin).  STILL NOT BUILT: runs that continue across a period boundary, the
- * percent-of-days form, ETCCDI's in-base bootstrap.                                                                                */
+ * (tests/cell_spell_rows_ref.py is the NumPy twin).  STILL NOT BUILT: the percent-of-days form, ETCCDI's in-base
+ * bootstrap; runs that continue across a period boundary are built for the plain thresholds only (wagg_spell_span_*).        */
 int wagg_row_cell_spells_f32(const float *X_dev, int64_t T, int64_t n, int64_t ldx, const int32_t *row_begin_dev,
                               const int32_t *rows_dev, int32_t P, int64_t n_rows, const int32_t *doy_dev, const int32_t *win_dev,
                               double offset, const float *thr_dev, int n_thr, int64_t ldt, int64_t thr_kstride,
