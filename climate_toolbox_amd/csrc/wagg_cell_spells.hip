@@ -46,34 +46,14 @@
 // spread).  With no faster one to keep, the group of 4 stays: the percentile triples this family is for (90 / 95 / 99) fit one
 // group of 4 with one idle slot where a group of 8 computes five, and it holds fewer registers (more waves per SIMD).  The kernel
 // alone (without the public call's host path) has not been timed.
-#include "wagg_rowlist.h"
-
-#include <cmath>
+//
+// The host layer (CellSpellXf and its fill, cell_ceil_to, the argument checks, the pick of the STAT instance, the VEC = 1
+// fallback of the threshold field, the blocking look's host sequence) is wagg_spell.h's, shared with wagg_cell_spells_rows.hip.
+#include "wagg_spell.h"
 
 namespace wagg {
 
 constexpr int CS_G = WAGG_CELL_SPELL_GROUP;
-
-struct CellSpellXf {
-    int n_thr, min_length, below;
-    int32_t M;
-    double offset;
-    int64_t ldt, kstride;
-};
-
-// host ceil_to<T> on the device: the smallest value of T that is not below c (NaN stays NaN)
-template <typename T> __device__ __forceinline__ T cell_ceil_to(double c) {
-    if constexpr (sizeof(T) == 8) {
-        return c;
-    } else {
-        float f = (float)c;                                          // (to nearest; +-inf and what overflows stay / become +-inf)
-        if ((double)f < c) {                                         // one step towards +inf, as nextafterf takes it
-            const uint32_t u = __float_as_uint(f);
-            f = f == 0.0f ? __uint_as_float(1u) : __uint_as_float((u >> 31) != 0 ? u - 1u : u + 1u);      // (-inf steps to -FLT_MAX)
-        }
-        return f;
-    }
-}
 
 // SEASON = false: doy / win are not read.  STAT: WAGG_SPELL_DAYS / _EVENTS / _LONGEST, WAGG_CELL_SPELL_AMOUNT / _EXCESS.
 template <typename T, int VEC, bool SEASON, int STAT>
@@ -207,83 +187,41 @@ __global__ void cell_spell_planes_kernel(const int32_t *__restrict__ plane_of_pe
     if (__ballot(bad) != 0ull && (threadIdx.x & 63) == 0) atomicOr(flag, 1);
 }
 
-static int cell_spell_check_planes(const int32_t *plane_of_period, int32_t P, int32_t M, hipStream_t st) {
-    DevBuf<int> flag;                                                // (blocking, as rowlist_check_rows just was)
-    int bad = 0;
-    WAGG_HIP(flag.alloc(1));
-    WAGG_HIP(hipMemsetAsync(flag.p, 0, sizeof(int), st));
-    hipLaunchKernelGGL(cell_spell_planes_kernel, dim3(64), dim3(256), 0, st, plane_of_period, (int64_t)P, M, flag.p);
-    WAGG_HIP(hipGetLastError());
-    WAGG_HIP(staged_d2h(&bad, flag.p, sizeof(int), st));
-    WAGG_REQUIRE(bad == 0, "plane_of_period: every period's plane index must lie in [0, M = %d)", (int)M);
-    return WAGG_OK;
-}
-
 template <typename T>
 static int cell_spells(const GroupedArgs<T> &a, double offset, const T *thr_dev, int n_thr, int64_t ldt, int64_t kstride,
                        const int32_t *plane_of_period, int32_t M, int min_length, int stat, int below) {
     static const GroupedFamily fam = {"a per-cell spell count", "X_dev", 1, CS_G};
-    constexpr int V = 16 / (int)sizeof(T);
-    const bool sum = stat == WAGG_CELL_SPELL_AMOUNT || stat == WAGG_CELL_SPELL_EXCESS;
     int rc_planes = WAGG_OK;
     const int rc = grouped_reduce<T>(
         fam, a, n_thr,                                               // (not looked at unless n_thr passes the check)
         [&]() -> int {
-            WAGG_REQUIRE(n_thr >= 1 && n_thr <= WAGG_CELL_SPELL_MAX, "n_thr must be 1..%d, got %d", WAGG_CELL_SPELL_MAX, n_thr);
-            WAGG_REQUIRE(M >= 1, "M must be at least 1, got %d", (int)M);
-            WAGG_REQUIRE(thr_dev != nullptr, "thr_dev is NULL");
-            WAGG_REQUIRE(ldt >= a.n, "ldt smaller than n (ldt=%lld, n=%lld)", (long long)ldt, (long long)a.n);
-            WAGG_REQUIRE(ldt <= INT64_MAX / M && kstride >= (int64_t)M * ldt, "thr_kstride smaller than M * ldt");
-            WAGG_REQUIRE(plane_of_period != nullptr || M == 1 || M == a.P,
-                         "plane_of_period_dev is NULL: allowed only for M == 1 or M == P (M=%d, P=%d)", (int)M, (int)a.P);
-            WAGG_REQUIRE(std::isfinite(offset), "offset must be finite");
-            WAGG_REQUIRE(min_length >= 1 && min_length <= WAGG_SPELL_MIN_LENGTH_MAX, "min_length must be 1..%d, got %d",
-                         WAGG_SPELL_MIN_LENGTH_MAX, min_length);
-            WAGG_REQUIRE(stat == WAGG_SPELL_DAYS || stat == WAGG_SPELL_EVENTS || stat == WAGG_SPELL_LONGEST || sum,
-                         "stat must be WAGG_SPELL_DAYS, _EVENTS, _LONGEST or WAGG_CELL_SPELL_AMOUNT, _EXCESS, got %d", stat);
-            WAGG_REQUIRE(stat != WAGG_SPELL_LONGEST || min_length == 1, "WAGG_SPELL_LONGEST does not use min_length: it must be 1, got %d",
-                         min_length);
-            WAGG_REQUIRE(!sum || min_length == 1, "WAGG_CELL_SPELL_AMOUNT / _EXCESS have no run counter: min_length must be 1, got %d",
-                         min_length);
-            WAGG_REQUIRE(below == 0 || below == 1, "below must be 0 or 1, got %d", below);
-            return WAGG_OK;
+            return cell_spell_require(n_thr, M, thr_dev, ldt, a.n, kstride, [&]() -> int {
+                WAGG_REQUIRE(plane_of_period != nullptr || M == 1 || M == a.P,
+                             "plane_of_period_dev is NULL: allowed only for M == 1 or M == P (M=%d, P=%d)", (int)M, (int)a.P);
+                return WAGG_OK;
+            }, offset, min_length, stat, below);
         },
         [&](const RowlistShape &got, bool wide, hipStream_t st) {
             if (plane_of_period != nullptr && !(a.flags & WAGG_PERIOD_ROWS_CHECKED)) {
-                rc_planes = cell_spell_check_planes(plane_of_period, a.P, M, st);
+                rc_planes = spell_flag_look(st, [&](int *flag) {
+                    hipLaunchKernelGGL(cell_spell_planes_kernel, dim3(64), dim3(256), 0, st, plane_of_period, (int64_t)a.P, M, flag);
+                }, "plane_of_period: every period's plane index must lie in [0, M = %d)", M);
                 if (rc_planes != WAGG_OK) return;                    // (nothing is launched)
             }
             RowlistShape sh = got;
             sh.split = 1;                                            // (no workspace went in; a run does not add across parts)
-            if (wide && !((reinterpret_cast<uintptr_t>(thr_dev) & 15) == 0 && (M == 1 || ldt % V == 0) && (n_thr == 1 || kstride % V == 0))) {
-                wide = false;                                        // the thresholds cannot be read in 16-byte pieces: VEC = 1 for both
-                sh.n_colblk = (int32_t)((sh.n + RL_BLOCK - 1) / RL_BLOCK);
-                if ((int64_t)sh.n_colblk * sh.P * sh.aux >= (int64_t)0x7fffffff) {
-                    set_error("too many pieces x periods x groups for one launch");
-                    rc_planes = WAGG_EINVAL;
-                    return;
-                }
+            if (!cell_spell_narrow<T>(sh, wide, thr_dev, n_thr, ldt, kstride, M)) {
+                rc_planes = WAGG_EINVAL;
+                return;
             }
-            CellSpellXf xf;
-            xf.n_thr = n_thr;
-            xf.min_length = min_length;
-            xf.below = below;
-            xf.M = M;
-            xf.offset = offset;
-            xf.ldt = ldt;
-            xf.kstride = kstride;
+            const CellSpellXf xf = cell_spell_xf(n_thr, ldt, kstride, M, offset, min_length, below);
             grouped_launch<T>(sh, wide, a, [&](auto vec, auto season, dim3 grid, auto *out, int64_t ldo, int64_t pstride) {
                 if constexpr (std::is_same_v<std::remove_pointer_t<decltype(out)>, T>) {      // (split = 1: never the workspace)
-                    auto go = [&](auto stat_c) {
+                    spell_with_stat<true>(stat, [&](auto stat_c) {
                         hipLaunchKernelGGL((cell_spell_kernel<T, decltype(vec)::value, decltype(season)::value, decltype(stat_c)::value>),
                                            grid, dim3(RL_BLOCK), 0, st, a.X, sh, a.row_begin, a.rows, a.doy, a.win, thr_dev, plane_of_period,
                                            xf, out, ldo, pstride, a.status);
-                    };
-                    if (stat == WAGG_SPELL_DAYS) go(std::integral_constant<int, WAGG_SPELL_DAYS>{});
-                    else if (stat == WAGG_SPELL_EVENTS) go(std::integral_constant<int, WAGG_SPELL_EVENTS>{});
-                    else if (stat == WAGG_SPELL_LONGEST) go(std::integral_constant<int, WAGG_SPELL_LONGEST>{});
-                    else if (stat == WAGG_CELL_SPELL_AMOUNT) go(std::integral_constant<int, WAGG_CELL_SPELL_AMOUNT>{});
-                    else go(std::integral_constant<int, WAGG_CELL_SPELL_EXCESS>{});
+                    });
                 }
             });
         });

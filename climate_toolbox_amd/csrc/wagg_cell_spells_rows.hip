@@ -10,7 +10,7 @@
 // plane_of_row[t] (wave-uniform: one scalar per row, as doy[t] is).  Entry i is HOT when t lies in [0, T), cell j is in season on
 // doy[t] (when a season is given) and X[t, j] + offset >= thr[k][m][j] (below = 0) or < thr[k][m][j] (below = 1).  The comparison is
 // the bins' exact rule, formed ON THE DEVICE PER ROW: c = ceilT((double)thr[k][m][j] - offset) -- one fp64 subtraction, rounded to
-// nearest, stepped up once where that lies below, wagg_cell_spells.hip's cell_ceil_to<T> -- and the hot test is x >= c / x < c on
+// nearest, stepped up once where that lies below, cell_ceil_to<T> of wagg_spell.h -- and the hot test is x >= c / x < c on
 // the RAW element.  With offset == 0, c is the threshold itself, and the kernel takes it without the arithmetic (a block-uniform
 // branch: ceilT((double)thr - 0) is thr, bit for bit).  +-inf thresholds compare as they compare.  Runs, gaps, seasons, NaN days
 // and bit 0 of the status word are wagg_cell_spells.hip's: a gap in the row numbers, an out-of-season day, a NaN and the end of the
@@ -31,8 +31,8 @@
 // names need no valid plane.
 //
 // THE FRAME is spell_kernel's, copied as the sibling copied it: a lane owns one 16-byte piece of a row (VEC = 1 for unaligned
-// rows), the grid is column block x period x group, strict list order, the wave-uniform gap test, the sibling's wide-route
-// conditions on thr_dev, ldt and thr_kstride.  A LIST IS NEVER SPLIT and there is no workspace.  What differs:
+// rows), the grid is column block x period x group, strict list order, the wave-uniform gap test; the wide-route
+// conditions on thr_dev, ldt and thr_kstride are the sibling's too (wagg_spell.h holds them once).  A LIST IS NEVER SPLIT and there is no workspace.  What differs:
 //   RAGGED GROUPS   kg, the levels a block owns, is block-uniform: the kernel branches on it once into a body instantiated for kg
 //                   = 1 .. CSR_G, so a ragged group issues no load and does no arithmetic for a level it does not own (TX90p's
 //                   single level: two 16-byte loads a row, not five).
@@ -55,34 +55,14 @@
 //   excess                110 / 0 / 4     40 / 0 / 8      76 / 0 / 6      41 / 0 / 8
 // No instance uses scratch, none spills an SGPR (at most 102), no AGPRs, no LDS.  fp32 VEC = 4 holds 30 to 40 registers more than
 // the sibling (a row's thresholds beside its values, where the sibling keeps one converted set for the whole list).
-#include "wagg_rowlist.h"
-
-#include <cmath>
+//
+// The host layer (CellSpellXf and its fill, cell_ceil_to, the argument checks, the pick of the STAT instance, the VEC = 1
+// fallback of the threshold field, the blocking look's host sequence) is wagg_spell.h's, shared with wagg_cell_spells.hip.
+#include "wagg_spell.h"
 
 namespace wagg {
 
 constexpr int CSR_G = WAGG_CELL_SPELL_GROUP;
-
-struct CellSpellRowsXf {
-    int n_thr, min_length, below;
-    int32_t M;
-    double offset;
-    int64_t ldt, kstride;
-};
-
-// host ceil_to<T> on the device: the smallest value of T that is not below c (NaN stays NaN) -- wagg_cell_spells.hip's cell_ceil_to
-template <typename T> __device__ __forceinline__ T cell_rows_ceil_to(double c) {
-    if constexpr (sizeof(T) == 8) {
-        return c;
-    } else {
-        float f = (float)c;                                          // (to nearest; +-inf and what overflows stay / become +-inf)
-        if ((double)f < c) {                                         // one step towards +inf, as nextafterf takes it
-            const uint32_t u = __float_as_uint(f);
-            f = f == 0.0f ? __uint_as_float(1u) : __uint_as_float((u >> 31) != 0 ? u - 1u : u + 1u);      // (-inf steps to -FLT_MAX)
-        }
-        return f;
-    }
-}
 
 // the row loop and the stores of a block that owns KG levels, k0 .. k0 + KG - 1 (col < sh.n); PLAIN: offset == 0, c is the threshold
 // itself.  True: the lane saw an in-season +-inf
@@ -90,7 +70,7 @@ template <typename T, int VEC, bool SEASON, int STAT, int KG, bool PLAIN>
 __device__ __forceinline__ bool cell_spell_rows_body(const T *__restrict__ X, const RowlistShape &sh, const int32_t *__restrict__ rows,
                                                      const int32_t *__restrict__ doy, const int32_t *__restrict__ win,
                                                      const T *__restrict__ thr_dev, const int32_t *__restrict__ plane_of_row,
-                                                     const CellSpellRowsXf &xf, T *__restrict__ out, int64_t ldo, int64_t pstride,
+                                                     const CellSpellXf &xf, T *__restrict__ out, int64_t ldo, int64_t pstride,
                                                      int32_t *__restrict__ status, int32_t p, int32_t k0, int64_t col, int64_t b, int64_t e) {
 #pragma clang fp contract(off)
     constexpr bool SUM = STAT == WAGG_CELL_SPELL_AMOUNT || STAT == WAGG_CELL_SPELL_EXCESS;
@@ -213,7 +193,7 @@ __device__ __forceinline__ bool cell_spell_rows_body(const T *__restrict__ X, co
                 const T raw = in[c] ? th[k][c] : T(0);               // (a counted entry: in the field, in season)
                 nan_thr |= raw != raw ? 1u << (k * VEC + c) : 0u;
                 T cmp = raw;                                         // ceilT((double)thr - offset): what the raw element is compared with
-                if constexpr (!PLAIN) cmp = cell_rows_ceil_to<T>((double)raw - off);
+                if constexpr (!PLAIN) cmp = cell_ceil_to<T>((double)raw - off);
                 const bool hot = below ? v < cmp : v >= cmp;
                 if constexpr (SUM) {
                     double term = a;
@@ -245,7 +225,7 @@ template <typename T, int VEC, bool SEASON, int STAT>
 __global__ void __launch_bounds__(RL_BLOCK)
 cell_spell_rows_kernel(const T *__restrict__ X, RowlistShape sh, const int32_t *__restrict__ row_begin, const int32_t *__restrict__ rows,
                        const int32_t *__restrict__ doy, const int32_t *__restrict__ win, const T *__restrict__ thr_dev,
-                       const int32_t *__restrict__ plane_of_row, CellSpellRowsXf xf, T *__restrict__ out, int64_t ldo, int64_t pstride,
+                       const int32_t *__restrict__ plane_of_row, CellSpellXf xf, T *__restrict__ out, int64_t ldo, int64_t pstride,
                        int32_t *__restrict__ status) {
     static_assert(CSR_G == 4, "the dispatch below names the group sizes 1..4");
     WAGG_ROWLIST_BLOCK(sh, cb, p, sg);
@@ -292,84 +272,41 @@ __global__ void cell_spell_row_planes_kernel(const int32_t *__restrict__ row_beg
     if (__ballot(bad) != 0ull && (threadIdx.x & 63) == 0) atomicOr(flag, 1);
 }
 
-static int cell_spell_check_row_planes(const int32_t *row_begin, int32_t P, const int32_t *rows, int64_t n_rows, int64_t T,
-                                       const int32_t *plane_of_row, int32_t M, hipStream_t st) {
-    DevBuf<int> flag;                                                // (blocking, as rowlist_check_rows just was)
-    int bad = 0;
-    if (n_rows == 0) return WAGG_OK;
-    WAGG_HIP(flag.alloc(1));
-    WAGG_HIP(hipMemsetAsync(flag.p, 0, sizeof(int), st));
-    hipLaunchKernelGGL(cell_spell_row_planes_kernel, dim3(64), dim3(256), 0, st, row_begin, P, rows, n_rows, T, plane_of_row, M, flag.p);
-    WAGG_HIP(hipGetLastError());
-    WAGG_HIP(staged_d2h(&bad, flag.p, sizeof(int), st));
-    WAGG_REQUIRE(bad == 0, "plane_of_row: the plane index of every listed row must lie in [0, M = %d)", (int)M);
-    return WAGG_OK;
-}
-
 template <typename T>
 static int cell_spells_rows(const GroupedArgs<T> &a, double offset, const T *thr_dev, int n_thr, int64_t ldt, int64_t kstride,
                             const int32_t *plane_of_row, int32_t M, int min_length, int stat, int below) {
     static const GroupedFamily fam = {"a per-cell spell count", "X_dev", 1, CSR_G};
-    constexpr int V = 16 / (int)sizeof(T);
-    const bool sum = stat == WAGG_CELL_SPELL_AMOUNT || stat == WAGG_CELL_SPELL_EXCESS;
     int rc_planes = WAGG_OK;
     const int rc = grouped_reduce<T>(
         fam, a, n_thr,                                               // (not looked at unless n_thr passes the check)
         [&]() -> int {
-            WAGG_REQUIRE(n_thr >= 1 && n_thr <= WAGG_CELL_SPELL_MAX, "n_thr must be 1..%d, got %d", WAGG_CELL_SPELL_MAX, n_thr);
-            WAGG_REQUIRE(M >= 1, "M must be at least 1, got %d", (int)M);
-            WAGG_REQUIRE(thr_dev != nullptr, "thr_dev is NULL");
-            WAGG_REQUIRE(ldt >= a.n, "ldt smaller than n (ldt=%lld, n=%lld)", (long long)ldt, (long long)a.n);
-            WAGG_REQUIRE(ldt <= INT64_MAX / M && kstride >= (int64_t)M * ldt, "thr_kstride smaller than M * ldt");
-            WAGG_REQUIRE(plane_of_row != nullptr, "plane_of_row_dev is NULL");
-            WAGG_REQUIRE(std::isfinite(offset), "offset must be finite");
-            WAGG_REQUIRE(min_length >= 1 && min_length <= WAGG_SPELL_MIN_LENGTH_MAX, "min_length must be 1..%d, got %d",
-                         WAGG_SPELL_MIN_LENGTH_MAX, min_length);
-            WAGG_REQUIRE(stat == WAGG_SPELL_DAYS || stat == WAGG_SPELL_EVENTS || stat == WAGG_SPELL_LONGEST || sum,
-                         "stat must be WAGG_SPELL_DAYS, _EVENTS, _LONGEST or WAGG_CELL_SPELL_AMOUNT, _EXCESS, got %d", stat);
-            WAGG_REQUIRE(stat != WAGG_SPELL_LONGEST || min_length == 1, "WAGG_SPELL_LONGEST does not use min_length: it must be 1, got %d",
-                         min_length);
-            WAGG_REQUIRE(!sum || min_length == 1, "WAGG_CELL_SPELL_AMOUNT / _EXCESS have no run counter: min_length must be 1, got %d",
-                         min_length);
-            WAGG_REQUIRE(below == 0 || below == 1, "below must be 0 or 1, got %d", below);
-            return WAGG_OK;
+            return cell_spell_require(n_thr, M, thr_dev, ldt, a.n, kstride, [&]() -> int {
+                WAGG_REQUIRE(plane_of_row != nullptr, "plane_of_row_dev is NULL");
+                return WAGG_OK;
+            }, offset, min_length, stat, below);
         },
         [&](const RowlistShape &got, bool wide, hipStream_t st) {
-            if (!(a.flags & WAGG_PERIOD_ROWS_CHECKED)) {
-                rc_planes = cell_spell_check_row_planes(a.row_begin, a.P, a.rows, a.n_rows, a.Ttot, plane_of_row, M, st);
+            if (!(a.flags & WAGG_PERIOD_ROWS_CHECKED) && a.n_rows != 0) {
+                rc_planes = spell_flag_look(st, [&](int *flag) {
+                    hipLaunchKernelGGL(cell_spell_row_planes_kernel, dim3(64), dim3(256), 0, st, a.row_begin, a.P, a.rows, a.n_rows, a.Ttot,
+                                       plane_of_row, M, flag);
+                }, "plane_of_row: the plane index of every listed row must lie in [0, M = %d)", M);
                 if (rc_planes != WAGG_OK) return;                    // (nothing is launched)
             }
             RowlistShape sh = got;
             sh.split = 1;                                            // (no workspace went in; a run does not add across parts)
-            if (wide && !((reinterpret_cast<uintptr_t>(thr_dev) & 15) == 0 && (M == 1 || ldt % V == 0) && (n_thr == 1 || kstride % V == 0))) {
-                wide = false;                                        // the thresholds cannot be read in 16-byte pieces: VEC = 1 for both
-                sh.n_colblk = (int32_t)((sh.n + RL_BLOCK - 1) / RL_BLOCK);
-                if ((int64_t)sh.n_colblk * sh.P * sh.aux >= (int64_t)0x7fffffff) {
-                    set_error("too many pieces x periods x groups for one launch");
-                    rc_planes = WAGG_EINVAL;
-                    return;
-                }
+            if (!cell_spell_narrow<T>(sh, wide, thr_dev, n_thr, ldt, kstride, M)) {
+                rc_planes = WAGG_EINVAL;
+                return;
             }
-            CellSpellRowsXf xf;
-            xf.n_thr = n_thr;
-            xf.min_length = min_length;
-            xf.below = below;
-            xf.M = M;
-            xf.offset = offset;
-            xf.ldt = ldt;
-            xf.kstride = kstride;
+            const CellSpellXf xf = cell_spell_xf(n_thr, ldt, kstride, M, offset, min_length, below);
             grouped_launch<T>(sh, wide, a, [&](auto vec, auto season, dim3 grid, auto *out, int64_t ldo, int64_t pstride) {
                 if constexpr (std::is_same_v<std::remove_pointer_t<decltype(out)>, T>) {      // (split = 1: never the workspace)
-                    auto go = [&](auto stat_c) {
+                    spell_with_stat<true>(stat, [&](auto stat_c) {
                         hipLaunchKernelGGL((cell_spell_rows_kernel<T, decltype(vec)::value, decltype(season)::value, decltype(stat_c)::value>),
                                            grid, dim3(RL_BLOCK), 0, st, a.X, sh, a.row_begin, a.rows, a.doy, a.win, thr_dev, plane_of_row,
                                            xf, out, ldo, pstride, a.status);
-                    };
-                    if (stat == WAGG_SPELL_DAYS) go(std::integral_constant<int, WAGG_SPELL_DAYS>{});
-                    else if (stat == WAGG_SPELL_EVENTS) go(std::integral_constant<int, WAGG_SPELL_EVENTS>{});
-                    else if (stat == WAGG_SPELL_LONGEST) go(std::integral_constant<int, WAGG_SPELL_LONGEST>{});
-                    else if (stat == WAGG_CELL_SPELL_AMOUNT) go(std::integral_constant<int, WAGG_CELL_SPELL_AMOUNT>{});
-                    else go(std::integral_constant<int, WAGG_CELL_SPELL_EXCESS>{});
+                    });
                 }
             });
         });

@@ -48,19 +48,15 @@
 // with the uniform branch that zeroes the runs behind a gap, 101-116 = 4 waves with a select in its place: hipcc then holds
 // both rows' compares across the run updates.  One row at 5 waves per SIMD keeps 5 loads in flight per SIMD where two rows at
 // 3 waves keep 6, with 32 integer operations per cell and row to hide them behind -- reasoning, not measurement.
-#include "wagg_rowlist.h"
-
-#include <cmath>
+//
+// The host layer (SpellXf and its fill, the argument checks, the pick of the STAT instance) is wagg_spell.h's, shared with the
+// three sibling units.
+#include "wagg_spell.h"
 
 namespace wagg {
 
 constexpr int SP_G = WAGG_SPELL_GROUP;
 constexpr int SP_UNROLL = 1;
-
-template <typename T> struct SpellXf {
-    int n_thr, min_length, below;
-    T c[WAGG_SPELL_MAX];                        // ceilT(thresholds[k] - offset)
-};
 
 // SEASON = false: doy / win are not read, every valid listed row counts.  STAT: WAGG_SPELL_DAYS / _EVENTS / _LONGEST.
 template <typename T, int VEC, bool SEASON, int STAT>
@@ -154,41 +150,18 @@ static int spell_reduce(const GroupedArgs<T> &a, double offset, const double *th
     static const GroupedFamily fam = {"a spell count", "X_dev", 1, SP_G};
     return grouped_reduce<T>(
         fam, a, n_thr,                                               // (not looked at unless n_thr passes the check)
-        [&]() -> int {
-            WAGG_REQUIRE(n_thr >= 1 && n_thr <= WAGG_SPELL_MAX, "n_thr must be 1..%d, got %d", WAGG_SPELL_MAX, n_thr);
-            WAGG_REQUIRE(thresholds != nullptr, "thresholds is NULL");
-            WAGG_REQUIRE(std::isfinite(offset), "offset must be finite");
-            for (int k = 0; k < n_thr; ++k) {
-                WAGG_REQUIRE(thresholds[k] == thresholds[k], "threshold %d is NaN", k);
-                WAGG_REQUIRE(!std::isinf(thresholds[k]), "threshold %d is infinite (a constant plane)", k);
-            }
-            WAGG_REQUIRE(min_length >= 1 && min_length <= WAGG_SPELL_MIN_LENGTH_MAX, "min_length must be 1..%d, got %d",
-                         WAGG_SPELL_MIN_LENGTH_MAX, min_length);
-            WAGG_REQUIRE(stat == WAGG_SPELL_DAYS || stat == WAGG_SPELL_EVENTS || stat == WAGG_SPELL_LONGEST,
-                         "stat must be WAGG_SPELL_DAYS, _EVENTS or _LONGEST, got %d", stat);
-            WAGG_REQUIRE(stat != WAGG_SPELL_LONGEST || min_length == 1, "WAGG_SPELL_LONGEST does not use min_length: it must be 1, got %d",
-                         min_length);
-            WAGG_REQUIRE(below == 0 || below == 1, "below must be 0 or 1, got %d", below);
-            return WAGG_OK;
-        },
+        [&]() -> int { return spell_require(n_thr, thresholds, offset, min_length, stat, below); },
         [&](const RowlistShape &got, bool wide, hipStream_t st) {
             RowlistShape sh = got;
-            if (sh.split != 1) sh.split = 1;                         // (no workspace went in: rowlist_geometry cannot cut a list; a run
-            SpellXf<T> xf;                                           //  does not add across parts, so one part it is, whatever it said)
-            xf.n_thr = n_thr;
-            xf.min_length = min_length;
-            xf.below = below;
-            for (int k = 0; k < WAGG_SPELL_MAX; ++k) xf.c[k] = ceil_to<T>(thresholds[k < n_thr ? k : n_thr - 1] - offset);
+            sh.split = 1;                                            // (no workspace went in: rowlist_geometry cannot cut a list; a run
+            const SpellXf<T> xf = spell_xf<T>(thresholds, n_thr, offset, min_length, below);      // does not add across parts)
             grouped_launch<T>(sh, wide, a, [&](auto vec, auto season, dim3 grid, auto *out, int64_t ldo, int64_t pstride) {
                 if constexpr (std::is_same_v<std::remove_pointer_t<decltype(out)>, T>) {      // (split = 1: never the workspace)
-                    auto go = [&](auto stat_c) {
+                    spell_with_stat<false>(stat, [&](auto stat_c) {
                         hipLaunchKernelGGL((spell_kernel<T, decltype(vec)::value, decltype(season)::value, decltype(stat_c)::value>), grid,
                                            dim3(RL_BLOCK), 0, st, a.X, sh, a.row_begin, a.rows, a.doy, a.win, xf, out, ldo, pstride,
                                            a.status);
-                    };
-                    if (stat == WAGG_SPELL_DAYS) go(std::integral_constant<int, WAGG_SPELL_DAYS>{});
-                    else if (stat == WAGG_SPELL_EVENTS) go(std::integral_constant<int, WAGG_SPELL_EVENTS>{});
-                    else go(std::integral_constant<int, WAGG_SPELL_LONGEST>{});
+                    });
                 }
             });
         });

@@ -63,18 +63,13 @@
 // masks; with that the entry loop's block (523 instructions for fp32 VEC = 4) reads 14-38 spilled scalars back per entry and
 // writes none.  Tried and dropped, by register count: the credit walk per threshold (107 VGPRs = 4 waves for fp32 VEC = 4) and
 // a one-VGPR bit mask of the runs that reached L (116 = 4 waves: hipcc then holds the eight plane pointers across the walk).
-#include "wagg_rowlist.h"
-
-#include <cmath>
+//
+// The host layer is wagg_spell.h's: wagg_spell_reduce_*'s SpellXf, its checks in its order, the pick of the STAT instance.
+#include "wagg_spell.h"
 
 namespace wagg {
 
 constexpr int SS_G = WAGG_SPELL_GROUP;
-
-template <typename T> struct SpellSpanXf {
-    int n_thr, min_length, below;
-    T c[WAGG_SPELL_MAX];                        // ceilT(thresholds[k] - offset)
-};
 
 // [b, e) = period p's list, confined to the list's extent as WAGG_ROWLIST_ROWS confines it (one part)
 #define WAGG_SPAN_LIST(sh, row_begin, p, b, e)                                                \
@@ -87,7 +82,7 @@ template <typename T> struct SpellSpanXf {
 template <typename T, int VEC, bool SEASON, int STAT>
 __global__ void __launch_bounds__(RL_BLOCK)
 spell_span_kernel(const T *__restrict__ X, RowlistShape sh, const int32_t *__restrict__ row_begin, const int32_t *__restrict__ rows,
-                  const int32_t *__restrict__ doy, const int32_t *__restrict__ win, SpellSpanXf<T> xf, T *out, int64_t ldo,
+                  const int32_t *__restrict__ doy, const int32_t *__restrict__ win, SpellXf<T> xf, T *out, int64_t ldo,
                   int64_t pstride, int32_t *__restrict__ status) {
     const int32_t cb = (int32_t)(blockIdx.x % (unsigned)sh.n_colblk);
     const int32_t k0 = (int32_t)(blockIdx.x / (unsigned)sh.n_colblk) * SS_G;
@@ -202,60 +197,28 @@ spell_span_kernel(const T *__restrict__ X, RowlistShape sh, const int32_t *__res
     if (__ballot(saw_inf) != 0ull && (threadIdx.x & 63) == 0) atomicOr(status, 1);
 }
 
-// the launch: one block per column block and threshold group (grouped_launch's grid has the period dimension this kernel walks)
-template <typename T>
-static void spell_span_launch(const RowlistShape &sh, bool wide, const GroupedArgs<T> &a, const SpellSpanXf<T> &xf, int stat,
-                              hipStream_t st) {
-    const dim3 grid((unsigned)((int64_t)sh.n_colblk * sh.aux));
-    auto go = [&](auto vec, auto season, auto stat_c) {
-        hipLaunchKernelGGL((spell_span_kernel<T, decltype(vec)::value, decltype(season)::value, decltype(stat_c)::value>), grid,
-                           dim3(RL_BLOCK), 0, st, a.X, sh, a.row_begin, a.rows, a.doy, a.win, xf, a.out, a.ldo, a.pstride, a.status);
-    };
-    auto with_stat = [&](auto vec, auto season) {
-        if (stat == WAGG_SPELL_DAYS) go(vec, season, std::integral_constant<int, WAGG_SPELL_DAYS>{});
-        else if (stat == WAGG_SPELL_EVENTS) go(vec, season, std::integral_constant<int, WAGG_SPELL_EVENTS>{});
-        else go(vec, season, std::integral_constant<int, WAGG_SPELL_LONGEST>{});
-    };
-    auto with_season = [&](auto vec) {
-        if (a.doy != nullptr) with_stat(vec, std::true_type{});
-        else with_stat(vec, std::false_type{});
-    };
-    if (wide) with_season(std::integral_constant<int, 16 / (int)sizeof(T)>{});
-    else with_season(std::integral_constant<int, 1>{});
-}
-
 template <typename T>
 static int spell_span_reduce(const GroupedArgs<T> &a, double offset, const double *thresholds, int n_thr, int min_length, int stat,
                              int below) {
     static const GroupedFamily fam = {"a spell count", "X_dev", 1, SS_G};
     return grouped_reduce<T>(
         fam, a, n_thr,                                               // (not looked at unless n_thr passes the check)
-        [&]() -> int {                                               // wagg_spell_reduce_*'s checks, in its order
-            WAGG_REQUIRE(n_thr >= 1 && n_thr <= WAGG_SPELL_MAX, "n_thr must be 1..%d, got %d", WAGG_SPELL_MAX, n_thr);
-            WAGG_REQUIRE(thresholds != nullptr, "thresholds is NULL");
-            WAGG_REQUIRE(std::isfinite(offset), "offset must be finite");
-            for (int k = 0; k < n_thr; ++k) {
-                WAGG_REQUIRE(thresholds[k] == thresholds[k], "threshold %d is NaN", k);
-                WAGG_REQUIRE(!std::isinf(thresholds[k]), "threshold %d is infinite (a constant plane)", k);
-            }
-            WAGG_REQUIRE(min_length >= 1 && min_length <= WAGG_SPELL_MIN_LENGTH_MAX, "min_length must be 1..%d, got %d",
-                         WAGG_SPELL_MIN_LENGTH_MAX, min_length);
-            WAGG_REQUIRE(stat == WAGG_SPELL_DAYS || stat == WAGG_SPELL_EVENTS || stat == WAGG_SPELL_LONGEST,
-                         "stat must be WAGG_SPELL_DAYS, _EVENTS or _LONGEST, got %d", stat);
-            WAGG_REQUIRE(stat != WAGG_SPELL_LONGEST || min_length == 1, "WAGG_SPELL_LONGEST does not use min_length: it must be 1, got %d",
-                         min_length);
-            WAGG_REQUIRE(below == 0 || below == 1, "below must be 0 or 1, got %d", below);
-            return WAGG_OK;
-        },
+        [&]() -> int { return spell_require(n_thr, thresholds, offset, min_length, stat, below); },
         [&](const RowlistShape &got, bool wide, hipStream_t st) {
             RowlistShape sh = got;
             sh.split = 1;                                            // (no workspace went in; rowlist_finish then has nothing to add)
-            SpellSpanXf<T> xf;
-            xf.n_thr = n_thr;
-            xf.min_length = min_length;
-            xf.below = below;
-            for (int k = 0; k < WAGG_SPELL_MAX; ++k) xf.c[k] = ceil_to<T>(thresholds[k < n_thr ? k : n_thr - 1] - offset);
-            spell_span_launch<T>(sh, wide, a, xf, stat, st);
+            const SpellXf<T> xf = spell_xf<T>(thresholds, n_thr, offset, min_length, below);
+            // one block per column block and threshold group: grouped_launch's grid has the period dimension this kernel walks
+            const dim3 grid((unsigned)((int64_t)sh.n_colblk * sh.aux));
+            grouped_launch<T>(sh, wide, a, [&](auto vec, auto season, dim3, auto *out, int64_t ldo, int64_t pstride) {
+                if constexpr (std::is_same_v<std::remove_pointer_t<decltype(out)>, T>) {      // (split = 1: never the workspace)
+                    spell_with_stat<false>(stat, [&](auto stat_c) {
+                        hipLaunchKernelGGL((spell_span_kernel<T, decltype(vec)::value, decltype(season)::value, decltype(stat_c)::value>),
+                                           grid, dim3(RL_BLOCK), 0, st, a.X, sh, a.row_begin, a.rows, a.doy, a.win, xf, out, ldo, pstride,
+                                           a.status);
+                    });
+                }
+            });
         });
 }
 

@@ -1148,6 +1148,26 @@ def bin_days_reduce(X, row_begin, rows, offset, edges, doy=None, windows=None, c
 _SPELL_STATS = {"days": _lib.SPELL_DAYS, "events": _lib.SPELL_EVENTS, "longest": _lib.SPELL_LONGEST}
 
 
+def _check_side(side):
+    if side not in ("above", "below"):
+        raise ValueError("side must be 'above' or 'below', got %r" % (side,))
+
+
+def _spell_codes(stats, stat, side, min_length):
+    """``stat`` (a key of ``stats``, the table of a spell call's statistics), ``side`` and ``min_length`` of a spell call, checked
+    in that order -- else ValueError; ``"longest"`` takes no ``min_length`` but 1.  Returns what the call's ``middle`` ends with:
+    ``(min_length, stat code, below)``."""
+    if stat not in stats:
+        names = [repr(s) for s in stats]
+        raise ValueError("stat must be %s or %s, got %r" % (", ".join(names[:-1]), names[-1], stat))
+    _check_side(side)
+    if isinstance(min_length, bool) or not isinstance(min_length, (int, np.integer)) or not 1 <= min_length <= _lib.SPELL_MIN_LENGTH_MAX:
+        raise ValueError("min_length must be an integer in 1..%d, got %r" % (_lib.SPELL_MIN_LENGTH_MAX, min_length))
+    if stat == "longest" and min_length != 1:
+        raise ValueError("stat='longest' does not use min_length: it must be 1, got %r" % (min_length,))
+    return int(min_length), stats[stat], 0 if side == "above" else 1
+
+
 def spell_reduce(X, row_begin, rows, offset, thresholds, min_length=1, stat="days", side="above", doy=None, windows=None, checked=False,
                  out=None, status=None, stream=None, span="period"):
     """Runs of consecutive days past every threshold of a list, per period, in ONE launch (``wagg_spell_reduce_*``).  Entry ``i``
@@ -1185,17 +1205,9 @@ def spell_reduce(X, row_begin, rows, offset, thresholds, min_length=1, stat="day
         raise ValueError("1..%d thresholds per call, got %s" % (_lib.SPELL_MAX, thr.shape))
     if not np.isfinite(thr).all():
         raise ValueError("thresholds must be finite, got %r" % (thr.tolist(),))
-    if stat not in _SPELL_STATS:
-        raise ValueError("stat must be 'days', 'events' or 'longest', got %r" % (stat,))
-    if side not in ("above", "below"):
-        raise ValueError("side must be 'above' or 'below', got %r" % (side,))
-    if isinstance(min_length, bool) or not isinstance(min_length, (int, np.integer)) or not 1 <= min_length <= _lib.SPELL_MIN_LENGTH_MAX:
-        raise ValueError("min_length must be an integer in 1..%d, got %r" % (_lib.SPELL_MIN_LENGTH_MAX, min_length))
-    if stat == "longest" and min_length != 1:
-        raise ValueError("stat='longest' does not use min_length: it must be 1, got %r" % (min_length,))
+    codes = _spell_codes(_SPELL_STATS, stat, side, min_length)
     return _grouped_reduce("wagg_spell_reduce" if span == "period" else "wagg_spell_span", (X,), row_begin, rows, doy, windows,
-                           checked, offset,
-                           (_np_ptr(thr, C.c_double), len(thr), int(min_length), _SPELL_STATS[stat], 0 if side == "above" else 1),
+                           checked, offset, (_np_ptr(thr, C.c_double), len(thr)) + codes,
                            len(thr), lambda L, *a: L.wagg_spell_work_bytes(*a), out, status, False, stream)
 
 
@@ -1318,8 +1330,7 @@ def hinge_reduce(X, row_begin, rows, offset, knots, power=1, side="above", tail=
         raise ValueError("knots must be finite, got %r" % (k.tolist(),))
     if power not in (1, 2, 3):
         raise ValueError("power must be 1, 2 or 3, got %r" % (power,))
-    if side not in ("above", "below"):
-        raise ValueError("side must be 'above' or 'below', got %r" % (side,))
+    _check_side(side)
     tk = ta = tb = None
     if tail is not None:
         tk, ta, tb = (np.ascontiguousarray(np.atleast_1d(v), dtype=np.float64) for v in tail)

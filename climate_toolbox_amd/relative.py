@@ -31,6 +31,28 @@ def _is_tensor(v):
     return type(v).__module__.startswith("torch")
 
 
+def _plane_map(pmap, name, count, per, device, on_host):
+    """A plane map (``plane_of_period`` / ``plane_of_row``: ``name``, for the messages) as the contiguous int32 tensor of
+    ``count`` entries on ``device`` the library reads.  Host integers are uploaded: ``on_host(h, holds)`` makes the map's own
+    checks of the 1-D integer array ``h`` ahead of that and returns what is uploaded (``holds(len(h))``: the count check, for a
+    map that wants it ahead of its own).  ``per``: what follows "entries" in the count message."""
+    import torch
+
+    def holds(got):
+        if got != count:
+            raise ValueError("%s must hold %d entries%s, got %d" % (name, count, per, got))
+
+    if not isinstance(pmap, torch.Tensor):
+        h = np.ascontiguousarray(pmap)
+        if h.ndim != 1 or h.dtype.kind not in "iu":
+            raise TypeError("%s must be a 1-D integer array or an int32 CUDA tensor" % name)
+        pmap = torch.from_numpy(on_host(h, holds).astype(np.int32)).to(device)
+    if not (pmap.is_cuda and pmap.dtype == torch.int32 and pmap.dim() == 1 and pmap.is_contiguous()):
+        raise TypeError("%s must be a contiguous int32 CUDA tensor (or host integers)" % name)
+    holds(int(pmap.numel()))
+    return pmap
+
+
 def cell_spell_reduce(X, row_begin, rows, offset, thr, plane_of_period=None, min_length=1, stat="days", side="above", doy=None,
                       windows=None, checked=False, out=None, status=None, stream=None, plane_of_row=None):
     """:func:`engine.spell_reduce` against PER-CELL thresholds, in ONE launch (``wagg_cell_spells_*``).  Entry ``i`` of period
@@ -83,26 +105,16 @@ def cell_spell_reduce(X, row_begin, rows, offset, thr, plane_of_period=None, min
     kstride = int(thr.stride(0)) if K > 1 else max(M * ldt, 1)
     if ldt < n or kstride < M * ldt:
         raise ValueError("thr must be laid out (K, M, n) with strides (>= M * stride(1), >= n, 1), got %r" % (tuple(thr.stride()),))
-    if stat not in _STATS:
-        raise ValueError("stat must be 'days', 'events', 'longest', 'amount' or 'excess', got %r" % (stat,))
-    if side not in ("above", "below"):
-        raise ValueError("side must be 'above' or 'below', got %r" % (side,))
-    if isinstance(min_length, bool) or not isinstance(min_length, (int, np.integer)) or not 1 <= min_length <= _lib.SPELL_MIN_LENGTH_MAX:
-        raise ValueError("min_length must be an integer in 1..%d, got %r" % (_lib.SPELL_MIN_LENGTH_MAX, min_length))
-    if stat == "longest" and min_length != 1:
-        raise ValueError("stat='longest' does not use min_length: it must be 1, got %r" % (min_length,))
+    codes = _engine._spell_codes(_STATS, stat, side, min_length)
     if stat in ("amount", "excess") and min_length != 1:
         raise ValueError("stat=%r has no run counter: min_length must be 1, got %r" % (stat, min_length))
     P = (int(row_begin.numel()) if isinstance(row_begin, torch.Tensor) else len(np.asarray(row_begin))) - 1
-    pmap = plane_of_period
+    pmap = None
     if plane_of_row is not None:
-        pmap, T = plane_of_row, int(X.shape[0])
-        if not isinstance(pmap, torch.Tensor):
-            h = np.ascontiguousarray(pmap)
-            if h.ndim != 1 or h.dtype.kind not in "iu":
-                raise TypeError("plane_of_row must be a 1-D integer array or an int32 CUDA tensor")
-            if len(h) != T:
-                raise ValueError("plane_of_row must hold %d entries (one per row of X), got %d" % (T, len(h)))
+        T = int(X.shape[0])
+
+        def rows_on_host(h, holds):
+            holds(len(h))
             if not isinstance(rows, torch.Tensor) and not isinstance(row_begin, torch.Tensor):      # (the rows the host lists name)
                 rb_h, rw_h = np.asarray(row_begin, dtype=np.int64), np.asarray(rows, dtype=np.int64)
                 named = rw_h[rb_h[0]:rb_h[-1]] if len(rb_h) else rw_h[:0]
@@ -111,31 +123,23 @@ def cell_spell_reduce(X, row_begin, rows, offset, thr, plane_of_period=None, min
                 if len(bad):
                     raise ValueError("plane_of_row must lie in 0..%d at every listed row, got %d at row %d"
                                      % (M - 1, int(h[bad[0]]), int(bad[0])))
-            pmap = torch.from_numpy(np.clip(h, -1, np.iinfo(np.int32).max).astype(np.int32)).to(X.device)
-        if not (pmap.is_cuda and pmap.dtype == torch.int32 and pmap.dim() == 1 and pmap.is_contiguous()):
-            raise TypeError("plane_of_row must be a contiguous int32 CUDA tensor (or host integers)")
-        if int(pmap.numel()) != T:
-            raise ValueError("plane_of_row must hold %d entries (one per row of X), got %d" % (T, int(pmap.numel())))
-    elif pmap is None:
+            return np.clip(h, -1, np.iinfo(np.int32).max)
+
+        pmap = _plane_map(plane_of_row, "plane_of_row", T, " (one per row of X)", X.device, rows_on_host)
+    elif plane_of_period is None:
         if M != 1 and M != P:
             raise ValueError("plane_of_period=None needs one plane or one plane per period (M=%d, P=%d)" % (M, P))
     else:
-        if not isinstance(pmap, torch.Tensor):
-            h = np.ascontiguousarray(pmap)
-            if h.ndim != 1 or h.dtype.kind not in "iu":
-                raise TypeError("plane_of_period must be a 1-D integer array or an int32 CUDA tensor")
+        def periods_on_host(h, holds):
             if len(h) and (h.min() < 0 or h.max() >= M):
                 raise ValueError("plane_of_period must lie in 0..%d, got %r" % (M - 1, h.tolist()))
-            pmap = torch.from_numpy(h.astype(np.int32)).to(X.device)
-        if not (pmap.is_cuda and pmap.dtype == torch.int32 and pmap.dim() == 1 and pmap.is_contiguous()):
-            raise TypeError("plane_of_period must be a contiguous int32 CUDA tensor (or host integers)")
-        if int(pmap.numel()) != P:
-            raise ValueError("plane_of_period must hold %d entries, got %d" % (P, int(pmap.numel())))
+            return h
+
+        pmap = _plane_map(plane_of_period, "plane_of_period", P, "", X.device, periods_on_host)
     res = _engine._grouped_reduce("wagg_cell_spells" if plane_of_row is None else "wagg_row_cell_spells", (X,), row_begin, rows, doy,
                                   windows, checked, offset,
-                                  (C.c_void_p(thr.data_ptr()), K, ldt, kstride, None if pmap is None else C.c_void_p(pmap.data_ptr()), M,
-                                   int(min_length), _STATS[stat], 0 if side == "above" else 1),
-                                  K, lambda L, *a: 0, out, status, False, stream)
+                                  (C.c_void_p(thr.data_ptr()), K, ldt, kstride, None if pmap is None else C.c_void_p(pmap.data_ptr()), M)
+                                  + codes, K, lambda L, *a: 0, out, status, False, stream)
     if stream is not None:                           # the map (uploaded here, perhaps) and thr must outlive the kernel on the
         for t in (pmap, thr):                        # caller's stream
             if t is not None:

@@ -458,14 +458,18 @@ def tas_bins_aggregate(ds, edges, aggwt, agglev, weights, tas="tas", varname="ta
     return out
 
 
+def _check_side(side):
+    if side not in ("above", "below"):
+        raise ValueError("side must be 'above' or 'below', got %r" % (side,))
+
+
 def _hinge_call(name, ds, knots, tail, power, side, aggwt, agglev, weights, tas, backup_aggwt, period, season, cells, leap_days):
     """what :func:`tas_hinge_aggregate` and :func:`tas_rcspline_aggregate` do alike behind their own checks of the knots: the
     remaining argument checks, the period lists and ``seasons._hinge_totals``.  Returns ``(stack, rdims, coords, was_xarray,
     units)`` with "time" already renamed to "period"."""
     if power not in (1, 2, 3):
         raise ValueError("power must be 1, 2 or 3, got %r" % (power,))
-    if side not in ("above", "below"):
-        raise ValueError("side must be 'above' or 'below', got %r" % (side,))
+    _check_side(side)
     re, var, weights, time_values, labels, grid, lists = _period_setup(name, "a hinge total", ds, tas, weights, period, season, cells,
                                                                        leap_days)
     from . import seasons
@@ -569,6 +573,33 @@ def _spell_thresholds(thresholds):
     return t
 
 
+def _spell_options(stat, side, min_length, stats, unset):
+    """``stat`` (one of ``stats``), ``side`` and ``min_length`` of a public spell call, checked in that order -- else ValueError.
+    The statistics of ``unset`` do not use ``min_length``: its default 3 counts as unset there, anything but that or 1 is
+    ValueError.  Returns the ``min_length`` the device call gets."""
+    if stat not in stats:
+        raise ValueError("stat must be %s or %r, got %r" % (", ".join(repr(s) for s in stats[:-1]), stats[-1], stat))
+    _check_side(side)
+    if isinstance(min_length, bool) or not isinstance(min_length, (int, np.integer)) or not 1 <= min_length <= 32767:
+        raise ValueError("min_length must be an integer in 1..32767, got %r" % (min_length,))
+    if stat in unset:
+        if min_length not in (1, 3):
+            raise ValueError("stat=%r does not use min_length (leave it out, or pass 1), got %r" % (stat, int(min_length)))
+        return 1
+    return int(min_length)
+
+
+def _spell_attrs(attrs, stat, side, min_length, sum_units=None):
+    """what the two public spell calls say of a result: units by statistic (``sum_units`` for the two sums; None: not said),
+    ``min_length``, ``stat``, ``side``"""
+    units = sum_units if stat in ("amount", "excess") else "1" if stat == "events" else "days"
+    if units is not None:
+        attrs["units"] = units
+    attrs["min_length"] = min_length
+    attrs["stat"] = stat
+    attrs["side"] = side
+
+
 def tas_spell_aggregate(ds, thresholds, aggwt, agglev, weights, min_length=3, stat="days", side="above", tas="tas", varname="tas-spell",
                         backup_aggwt="areawt", period="year", season=None, cells="all", leap_days="keep", span="period"):
     """Spell statistics of a cell's daily temperature -- runs of consecutive days past a threshold -- per period (and growing
@@ -627,17 +658,7 @@ def tas_spell_aggregate(ds, thresholds, aggwt, agglev, weights, min_length=3, st
     t = _spell_thresholds(thresholds)
     if span not in ("period", "record"):
         raise ValueError("span must be 'period' or 'record', got %r" % (span,))
-    if stat not in ("days", "events", "longest"):
-        raise ValueError("stat must be 'days', 'events' or 'longest', got %r" % (stat,))
-    if side not in ("above", "below"):
-        raise ValueError("side must be 'above' or 'below', got %r" % (side,))
-    if isinstance(min_length, bool) or not isinstance(min_length, (int, np.integer)) or not 1 <= min_length <= 32767:
-        raise ValueError("min_length must be an integer in 1..32767, got %r" % (min_length,))
-    min_length = int(min_length)
-    if stat == "longest":
-        if min_length not in (1, 3):
-            raise ValueError("stat='longest' does not use min_length (leave it out, or pass 1), got %r" % (min_length,))
-        min_length = 1
+    min_length = _spell_options(stat, side, min_length, ("days", "events", "longest"), ("longest",))
     re, _, weights, time_values, labels, grid, lists = _period_setup("tas_spell_aggregate", "a spell count", ds, tas, weights, period,
                                                                      season, cells, leap_days)
     from . import seasons
@@ -645,10 +666,7 @@ def tas_spell_aggregate(ds, thresholds, aggwt, agglev, weights, min_length=3, st
                                                        stat, side, season, grid, time_values, cells=cells, span=span)
     rdims, coords = _time_as_period(rdims, coords, labels)
     out = _agg._as_dataset({varname: res}, ("threshold",) + tuple(rdims), dict(coords, threshold=t.copy()), was_xr)
-    out[varname].attrs["units"] = "1" if stat == "events" else "days"
-    out[varname].attrs["min_length"] = min_length
-    out[varname].attrs["stat"] = stat
-    out[varname].attrs["side"] = side
+    _spell_attrs(out[varname].attrs, stat, side, min_length)
     out[varname].attrs["span"] = span
     return out
 
@@ -699,17 +717,7 @@ def tas_relative_spell_aggregate(ds, thresholds, aggwt, agglev, weights, min_len
     if not isinstance(thresholds, CellThresholds):
         raise TypeError("thresholds must be a CellThresholds (relative.cell_quantiles or CellThresholds.from_array), got %r"
                         % (type(thresholds).__name__,))
-    if stat not in ("days", "events", "longest", "amount", "excess"):
-        raise ValueError("stat must be 'days', 'events', 'longest', 'amount' or 'excess', got %r" % (stat,))
-    if side not in ("above", "below"):
-        raise ValueError("side must be 'above' or 'below', got %r" % (side,))
-    if isinstance(min_length, bool) or not isinstance(min_length, (int, np.integer)) or not 1 <= min_length <= 32767:
-        raise ValueError("min_length must be an integer in 1..32767, got %r" % (min_length,))
-    min_length = int(min_length)
-    if stat in ("longest", "amount", "excess"):
-        if min_length not in (1, 3):
-            raise ValueError("stat=%r does not use min_length (leave it out, or pass 1), got %r" % (stat, min_length))
-        min_length = 1
+    min_length = _spell_options(stat, side, min_length, ("days", "events", "longest", "amount", "excess"), ("longest", "amount", "excess"))
     if not (planes is None or (isinstance(planes, str) and planes in ("month", "calendar_day")) or callable(planes)):
         raise ValueError("planes must be None, 'month', 'calendar_day' or a callable, got %r" % (planes,))
     if stat == "amount" and thresholds.shift != 0.0:
@@ -732,15 +740,7 @@ def tas_relative_spell_aggregate(ds, thresholds, aggwt, agglev, weights, min_len
                                                             plane_of_row=rmap)
     rdims, coords = _time_as_period(rdims, coords, labels)
     out = _agg._as_dataset({varname: res}, ("threshold",) + tuple(rdims), dict(coords, threshold=thresholds.levels.copy()), was_xr)
-    if stat in ("amount", "excess"):
-        units = "C" if getattr(var, "_xform", None) is not None else _units(var)
-    else:
-        units = "1" if stat == "events" else "days"
-    if units is not None:
-        out[varname].attrs["units"] = units
-    out[varname].attrs["min_length"] = min_length
-    out[varname].attrs["stat"] = stat
-    out[varname].attrs["side"] = side
+    _spell_attrs(out[varname].attrs, stat, side, min_length, "C" if getattr(var, "_xform", None) is not None else _units(var))
     return out
 
 
